@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Foldclass search benchmark: queries/sec of the exact 128-d cosine top-k scan on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: starts its own ranks as children)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: starts its own ranks as children)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -942,6 +942,30 @@ def write_full(doc):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, scores, rows, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: the top-level step's result as its caller receives it -- top-k scores [nq, k] -> out_dir/scores.npy (float32)
+    and global row indices [nq, k] -> out_dir/rows.npy (float64: exact for every index below 2^53).  The inputs are seeded, so two
+    builds run with the same arguments can be compared file for file.  When the files would exceed `limit` bytes, the same fixed
+    sample of query rows (seed 0, ascending) is written for every build, and out_dir/query_rows.npy (float64) names it."""
+    scores, rows = np.asarray(scores, dtype=np.float32), np.asarray(rows, dtype=np.float64)
+    nq = scores.shape[0]
+    per_query = scores[:1].nbytes + rows[:1].nbytes
+    arrays = {"scores": scores, "rows": rows}
+    if nq * per_query > limit:
+        keep = max(1, (limit - 1024) // (per_query + 8))              # (+ 8: the query's entry in query_rows; 1 KB for the .npy headers)
+        sel = np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+        arrays = {"scores": scores[sel], "rows": rows[sel], "query_rows": sel.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    if "query_rows" not in arrays and os.path.exists(os.path.join(out_dir, "query_rows.npy")):
+        os.remove(os.path.join(out_dir, "query_rows.npy"))              # (a sample's index of an earlier, larger run would misname these)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 PREFLIGHT_DEADLINE_S = 60.0
 
 
@@ -1059,8 +1083,8 @@ def pipelined_rate(bench, steps, depth=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps of the top-level line (default 200; 10 with --shape c4)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps before them (default 30; 2 with --shape c4)")
     ap.add_argument("--rows", type=int, default=None, help="TOTAL database rows, sharded over the ranks (default: 1M at N=1; 45,625,000 PER GPU at N>1)")
     ap.add_argument("--nq", type=int, default=None, help="queries per step (default 256 at N=1, 4096 at N>1)")
     ap.add_argument("--k", type=int, default=10)
@@ -1077,7 +1101,13 @@ def main():
     ap.add_argument("--no-prefilter", action="store_true", help="skip the `prefiltered` blocks (the top-level line is the fp32 scan either way)")
     ap.add_argument("--exercise-exchange", action="store_true",
                     help="run the multi-GPU exchange + shard merge even on one GPU (validates that code path; slower)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the top-level line returned to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without an outer launcher: start the N ranks as a FRESH child process tree
@@ -1134,10 +1164,13 @@ def main():
     weak = world > 1 and args.rows is None
     if world > 1 and args.shape == "c2":
         raise SystemExit("--shape c2 is the one-GPU workload; --gpus N > 1 always runs the C4 shape (weak scaling)")
-    if world == 1 and args.shape == "c4":
+    c4_one_rank = world == 1 and args.shape == "c4"
+    if args.steps is None:
+        args.steps = 10 if c4_one_rank else 200                           # (C4 shape: 0.34 s per step)
+    if args.warmup is None:
+        args.warmup = 2 if c4_one_rank else 30
+    if c4_one_rank:
         n_total, nq = args.rows or int(os.environ.get("MS_BENCH_ROWS_PER_GPU", C4_ROWS_PER_GPU)), args.nq or C4_NQ
-        if args.steps == ap.get_default("steps"):
-            args.steps, args.warmup = 10, 2                               # 0.34 s per step
     elif world == 1:
         n_total, nq = args.rows or 1_000_000, args.nq or 256
     else:
@@ -1150,6 +1183,9 @@ def main():
     bench = SearchBench(torch, dist, ops, syn, sharded, dev, rank, world, n_total, lo, hi, nq, k, exchange=args.exercise_exchange)
     steps = args.steps
     elapsed, scan_ms, res = bench.run(steps, args.warmup)        # the fp32 scan: the reference's arithmetic, data-independent
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res[0].cpu().numpy(), res[1].cpu().numpy())   # (before later blocks reuse the output buffers)
+        log("outputs of the last timed step: %s" % os.path.abspath(args.dump_outputs))
     checks = bench.check(res, sharded)
     # N > 1 (weak scaling): the same ranks' shard scans without the exchange -- the curve's one-rank reference from the same build
     local_ref = bench.local_rate(max(2, min(steps, 10))) if world > 1 else None

@@ -114,3 +114,36 @@ def test_write_full_round_trips(tmp_path, monkeypatch):
     assert path == str(tmp_path / "bench_full.json")
     with open(path) as fh:
         assert json.load(fh) == doc
+
+
+def test_dump_outputs_writes_the_result_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    """--dump-outputs: scores float32 and global rows float64, as returned; over the byte limit the same seeded sample of query rows
+    every time (named by query_rows.npy), within the limit; a later unsampled dump into the same directory drops that index."""
+    import numpy as np
+    rng = np.random.default_rng(5)
+    nq, k = 1000, 10
+    scores = np.sort(rng.random((nq, k), dtype=np.float32), axis=1)[:, ::-1]
+    rows = rng.integers(0, 365_000_000, size=(nq, k), dtype=np.int64)
+    d = tmp_path / "full"
+    assert bench.dump_outputs(str(d), scores, rows) == ["rows", "scores"]
+    s, r = np.load(d / "scores.npy"), np.load(d / "rows.npy")
+    assert s.dtype == np.float32 and r.dtype == np.float64
+    assert np.array_equal(s.view(np.uint32), scores.view(np.uint32)) and np.array_equal(r.astype(np.int64), rows)
+    limit = 20_000
+    for d in (tmp_path / "a", tmp_path / "b"):
+        assert bench.dump_outputs(str(d), scores, rows, limit=limit) == ["query_rows", "rows", "scores"]
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("scores", "rows", "query_rows")}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in ("scores", "rows", "query_rows")}
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in a) <= limit
+    assert a["query_rows"].dtype == np.float64 and np.all(np.diff(a["query_rows"]) > 0) and 0 < len(a["query_rows"]) < nq
+    sel = a["query_rows"].astype(np.int64)
+    assert np.array_equal(a["scores"], scores[sel]) and np.array_equal(a["rows"].astype(np.int64), rows[sel])
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    bench.dump_outputs(str(tmp_path / "a"), scores[:5], rows[:5])
+    assert not (tmp_path / "a" / "query_rows.npy").exists() and np.load(tmp_path / "a" / "rows.npy").shape == (5, k)
+
+
+def test_steps_below_one_are_refused_before_anything_runs():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

@@ -138,34 +138,34 @@ def _c5_database_pdbs(tmp_path, count, seed=21):
     return pd2, str(dbdir)
 
 
-def _c5_on_eight_ranks(tmp_path, launcher_argv, env, count):
-    """C5 as BASELINE.json words it (easy-search of AF-Q96PD2, README chopping, -k 10) on EIGHT ranks under torchrun against the same
-    command in one process, fed by createdb on eight ranks against createdb in one process: database files and TSVs identical."""
+def _c5_on_many_ranks(tmp_path, launcher_argv, env, count, world=8):
+    """C5 as BASELINE.json words it (easy-search of AF-Q96PD2, README chopping, -k 10) on `world` ranks under torchrun against the same
+    command in one process, fed by createdb on `world` ranks against createdb in one process: database files and TSVs identical."""
     from conftest import free_port
     pd2, dbdir = _c5_database_pdbs(tmp_path, count)
     port = free_port(4)
-    for nproc, tag in ((8, "db8"), (1, "db1")):
-        r = _torchrun(nproc, launcher_argv + ["createdb", dbdir, str(tmp_path / tag), "--layout", "faiss"], env, port + (0 if nproc == 8 else 1))
+    for nproc, tag in ((world, "dbN"), (1, "db1")):
+        r = _torchrun(nproc, launcher_argv + ["createdb", dbdir, str(tmp_path / tag), "--layout", "faiss"], env, port + (0 if nproc == world else 1))
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     import json
-    info8, info1 = json.load(open(tmp_path / "db8.json")), json.load(open(tmp_path / "db1.json"))
-    assert info8["DB_SIZE"] == info1["DB_SIZE"] == count + 3
+    infoN, info1 = json.load(open(tmp_path / "dbN.json")), json.load(open(tmp_path / "db1.json"))
+    assert infoN["DB_SIZE"] == info1["DB_SIZE"] == count + 3
     for key in ("dbfname_IP", "db_names_f", "sif", "sdf", "cif", "cdf"):          # every file of the faiss layout, byte for byte
-        a, b = open(tmp_path / info8[key], "rb").read(), open(tmp_path / info1[key], "rb").read()
+        a, b = open(tmp_path / infoN[key], "rb").read(), open(tmp_path / info1[key], "rb").read()
         assert a == b, key
-    search = ["easy-search", pd2, str(tmp_path / "db8"), None, str(tmp_path / "tmp"), "-k", "10", "-s", "-1", "--chopping", C5_CHOPPING, "--output_headers"]
-    for nproc, out in ((8, "eight"), (1, "one")):
-        r = _torchrun(nproc, launcher_argv + [a if a is not None else str(tmp_path / out) for a in search], env, port + (2 if nproc == 8 else 3))
+    search = ["easy-search", pd2, str(tmp_path / "dbN"), None, str(tmp_path / "tmp"), "-k", "10", "-s", "-1", "--chopping", C5_CHOPPING, "--output_headers"]
+    for nproc, out in ((world, "many"), (1, "one")):
+        r = _torchrun(nproc, launcher_argv + [a if a is not None else str(tmp_path / out) for a in search], env, port + (2 if nproc == world else 3))
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    one, eight = open(str(tmp_path / "one") + "_search.tsv").read(), open(str(tmp_path / "eight") + "_search.tsv").read()
-    assert one == eight                                                            # byte-identical
+    one, many = open(str(tmp_path / "one") + "_search.tsv").read(), open(str(tmp_path / "many") + "_search.tsv").read()
+    assert one == many                                                            # byte-identical
     rows = [l.split("\t") for l in one.splitlines()[1:]]
     assert len(rows) == 30 and {r_[0] for r_ in rows} == {"AF-Q96PD2-F1-model_v4_ca_merizo_0%d" % i for i in (1, 2, 3)}
     for j, dom in enumerate(("71-189", "190-290", "291-453")):                     # every domain finds its own copy first
         top = rows[10 * j]
         assert top[1] == dom and top[4] == "0" and top[5] == "AF-Q96PD2-F1-model_v4_TED%02d" % (j + 1), top
-    seg1, seg8 = _segment_rows_without_runtime(str(tmp_path / "one") + "_segment.tsv"), _segment_rows_without_runtime(str(tmp_path / "eight") + "_segment.tsv")
-    assert seg1 == seg8 and seg1[1][:5] == ["AF-Q96PD2-F1-model_v4_ca", "775", "383", "392", "3"]
+    seg1, segN = _segment_rows_without_runtime(str(tmp_path / "one") + "_segment.tsv"), _segment_rows_without_runtime(str(tmp_path / "many") + "_segment.tsv")
+    assert seg1 == segN and seg1[1][:5] == ["AF-Q96PD2-F1-model_v4_ca", "775", "383", "392", "3"]
 
 
 def test_c5_easy_search_af_q96pd2_on_eight_ranks_gloo_oracle(tmp_path):
@@ -173,7 +173,7 @@ def test_c5_easy_search_af_q96pd2_on_eight_ranks_gloo_oracle(tmp_path):
     shim = tmp_path / "shim.py"
     shim.write_text(_CLI_SHIM)
     env = dict(os.environ, MERIZO_DIST_BACKEND="gloo", OMP_NUM_THREADS="1")
-    _c5_on_eight_ranks(tmp_path, [str(shim), REPO], env, count=21)
+    _c5_on_many_ranks(tmp_path, [str(shim), REPO], env, count=21)
 
 
 def test_ranks_wait_out_rank0_postprocessing_beyond_the_group_timeout(tmp_path):
@@ -230,6 +230,10 @@ def test_balance_by_cost_is_a_partition_and_balanced():
 
 
 # ---------------------------------------------------------------------------- GPU ------
+# Child ranks that share cuda:0 in one test.  The suite keeps at most six processes on one GPU at a time: these ranks, plus the pytest
+# process, which has the GPU open from the tests before.
+GPU_SHARING_RANKS = 4
+
 @pytest.mark.gpu
 def test_run_dbsearch_sharded_equals_one_rank_hip_engine_two_ranks(tmp_path):
     """Two fresh child ranks on cuda:0 over gloo with the HIP engine: sharded scan -> all-gather ->
@@ -242,15 +246,17 @@ def test_run_dbsearch_sharded_equals_one_rank_hip_engine_two_ranks(tmp_path):
 
 
 @pytest.mark.gpu
-def test_run_dbsearch_sharded_equals_one_rank_hip_engine_eight_ranks(tmp_path):
-    """The C4 / C5 rank count on the hardware there is: EIGHT child ranks sharing cuda:0 over gloo (MERIZO_SAME_DEVICE), the HIP
-    engine on every shard, one all-gather of 8 packed blocks, ms_topk_merge_strided at S = 8 -- == the one-rank run bit for bit
-    (resident, streamed, and the `.pt` cosine path; the prefiltered search across 8 ranks: test_bench_gpus_8_...)."""
+def test_run_dbsearch_sharded_equals_one_rank_hip_engine_four_ranks(tmp_path):
+    """FOUR child ranks sharing cuda:0 over gloo (MERIZO_SAME_DEVICE), the HIP engine on every shard, one all-gather of 4 packed
+    blocks, ms_topk_merge_strided at S = 4 -- == the one-rank run bit for bit (resident, streamed, and the `.pt` cosine path; the
+    prefiltered search across 4 ranks: test_bench_gpus_4_...).  (Four, not the C4 / C5 count of eight: with the pytest process that
+    is at most GPU_SHARING_RANKS + 1 processes on the one GPU.  Eight ranks through the drivers: the gloo + oracle tests above; the merge
+    at S = 8 on the GPU: tests/test_search_gpu.py.)"""
     work = str(tmp_path / "case")
     _make_case(work, n=200_003, nq=70, k=10, batch=30_000)
     _run_ranks(work, 1, "hip")
-    _run_ranks(work, 8, "hip")
-    _compare(work, 8)
+    _run_ranks(work, GPU_SHARING_RANKS, "hip")
+    _compare(work, GPU_SHARING_RANKS)
 
 
 @pytest.mark.gpu
@@ -292,14 +298,15 @@ def test_cli_under_torchrun_two_ranks_on_one_gpu(tmp_path):
 
 
 @pytest.mark.gpu
-def test_c5_easy_search_af_q96pd2_on_eight_ranks_one_gpu(tmp_path):
-    """C5 verbatim on the hardware there is: `torchrun --nproc-per-node 8 -m merizo_search_amd.cli easy-search AF-Q96PD2 ... --chopping
-    71-189,190-290,291-453 -k 10` (eight ranks sharing cuda:0 over gloo: MERIZO_SAME_DEVICE / MERIZO_DIST_BACKEND; the HIP engine on every
+def test_c5_easy_search_af_q96pd2_on_four_ranks_one_gpu(tmp_path):
+    """C5 verbatim on one GPU: `torchrun --nproc-per-node 4 -m merizo_search_amd.cli easy-search AF-Q96PD2 ... --chopping
+    71-189,190-290,291-453 -k 10` (four ranks sharing cuda:0 over gloo: MERIZO_SAME_DEVICE / MERIZO_DIST_BACKEND; the HIP engine on every
     shard, 16 rows per shard -- fewer than k + the padded lists through the all-gather) against the one-process run: `_search.tsv`
-    byte-identical, `_segment.tsv` identical but for its wall-clock column; the database comes from createdb on 8 ranks and is byte-identical
-    to the one createdb writes in one process."""
+    byte-identical, `_segment.tsv` identical but for its wall-clock column; the database comes from createdb on 4 ranks and is byte-identical
+    to the one createdb writes in one process.  (C5 on eight ranks: the gloo + oracle test above; four here for the reason
+    GPU_SHARING_RANKS gives.)"""
     env = dict(os.environ, MERIZO_DIST_BACKEND="gloo", MERIZO_SAME_DEVICE="1", MERIZO_ALLOW_SYNTHETIC_WEIGHTS="1", PYTHONPATH=REPO, GLOO_SOCKET_IFNAME="lo")
-    _c5_on_eight_ranks(tmp_path, ["-m", "merizo_search_amd.cli"], env, count=125)
+    _c5_on_many_ranks(tmp_path, ["-m", "merizo_search_amd.cli"], env, count=16 * GPU_SHARING_RANKS - 3, world=GPU_SHARING_RANKS)
 
 
 @pytest.mark.gpu
@@ -397,17 +404,20 @@ def test_bench_gpus_2_self_launches_and_is_exact(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bench_gpus_8_self_launches_on_tiny_shards(tmp_path):
-    """`python bench.py --gpus 8` (the driver's scaling run) end to end on one GPU: eight ranks on cuda:0 over gloo, 100,000 rows
-    each; exact, and the prefiltered block of the same step identical to the fp32 scan across the 8-way exchange."""
+def test_bench_gpus_4_self_launches_on_tiny_shards(tmp_path):
+    """`python bench.py --gpus 4` (the driver's scaling run, at the rank count GPU_SHARING_RANKS allows on one GPU) end to end: four
+    ranks on cuda:0 over gloo, 100,000 rows each; exact, and the prefiltered block of the same step identical to the fp32 scan across
+    the 4-way exchange."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MS_BENCH_SAME_DEVICE="1", MS_BENCH_BACKEND="gloo")
-    r = _run_bench(["--gpus", "8", "--rows", "800000", "--nq", "96", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], env, 400)
+    world = GPU_SHARING_RANKS
+    r = _run_bench(["--gpus", str(world), "--rows", str(100000 * world), "--nq", "96", "--steps", "2", "--warmup", "1", "--no-extras",
+                    "--no-cpu-baseline"], env, 400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _bench_line(r.stdout)
-    assert line["n_gpus"] == 8 and line["config"]["rows_per_gpu"] == 100000
-    assert line["collective"]["backend"] == "gloo" and line["collective"]["world"] == 8 and line["collective"]["distinct_devices"] == 1
+    assert line["n_gpus"] == world and line["config"]["rows_per_gpu"] == 100000
+    assert line["collective"]["backend"] == "gloo" and line["collective"]["world"] == world and line["collective"]["distinct_devices"] == 1
     assert line["weak_scaling_ref_q_per_s"] > 0 and line["vs_ref"] > 0
     assert line["recall_at_k"] == 1.0 and line["planted_recall"] == 1.0
     assert line["topk_identical_to_torch_bruteforce"].startswith("96 of 96")
@@ -445,6 +455,31 @@ def test_bench_shape_c4_is_the_one_rank_point_of_the_weak_scaling_curve(tmp_path
     line = _bench_line(r.stdout)
     assert line["config"]["workload"].startswith("C4 shape, ONE rank") and line["config"]["queries_per_step"] == 4096
     assert line["config"]["db_rows"] == 2_000_000 and line["recall_at_k"] == 1.0 and line["prefiltered"]["identical_to_fp32"] is True
+
+
+@pytest.mark.gpu
+def test_bench_steps_are_as_given_and_dump_outputs_is_the_timed_result(tmp_path):
+    """`--steps 200 --shape c4` times 200 steps (200 is also the default of the C2 shape, which once made the C4 shape replace it with
+    its own default), and `--dump-outputs DIR` holds exactly what the top-level step returns for the same seeded inputs."""
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    from merizo_search_amd import ops
+    from merizo_search_amd.foldclass import sharded, synthetic as syn
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    n, nq, k = 300_000, 96, 10
+    out = tmp_path / "dump"
+    r = _run_bench(["--shape", "c4", "--rows", str(n), "--nq", str(nq), "--k", str(k), "--steps", "200", "--warmup", "1", "--no-cpu-baseline",
+                    "--no-prefilter", "--no-pipelined", "--dump-outputs", str(out)], env, 400)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line = _bench_line(r.stdout)
+    assert line["steps"] == 200 and line["warmup"] == 1 and line["config"]["db_rows"] == n and line["recall_at_k"] == 1.0
+    assert sorted(os.listdir(out)) == ["rows.npy", "scores.npy"]
+    s, i = np.load(out / "scores.npy"), np.load(out / "rows.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (nq, k)
+    b = bench.SearchBench(torch, None, ops, syn, sharded, torch.device("cuda", 0), 0, 1, n, 0, n, nq, k)
+    s_ref, i_ref = (t.cpu().numpy() for t in b.step())
+    assert np.array_equal(s.view(np.uint32), s_ref.view(np.uint32)) and np.array_equal(i.astype(np.int64), i_ref)
 
 
 @pytest.mark.gpu

@@ -76,31 +76,16 @@ static_assert(P_LAYER % 4 == 0 && P_W2F % 4 == 0 && P_WC % 4 == 0 && P_B1 % 4 ==
 // x = hi + mid + lo EXACTLY, each part a bf16 (the upper 16 bits of what is left: 8 + 8 + 8 significant bits).  A product x * w
 // over the parts has nine terms; hi.hi, hi.mid, mid.hi, hi.lo, lo.hi, mid.mid are kept -- what is dropped (mid.lo, lo.mid,
 // lo.lo) is below 2^-23 |x w|, the size of one fp32 rounding.  bf16 x bf16 products are exact in the fp32 accumulator.
-#ifndef MS_EGNN_SPLIT_PK
-#define MS_EGNN_SPLIT_PK 0          // round 6: packed residual subtractions in split3_pair -- 16 fewer vector instructions per block pair and 1.2 % SLOWER (three
-#endif                             // same-box passes: 57.7-57.8 against 57.0-57.1 ms per 1,000 domains, profiles/r06_egnn_split_pk_ab.log): not the default
 typedef __bf16 bf16x8_e __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4_e __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split3_pair(float x0, float x1, uint32_t &hi, uint32_t &mid, uint32_t &lo) {
     const uint32_t a = __float_as_uint(x0), b = __float_as_uint(x1);
     hi = __builtin_amdgcn_perm(b, a, 0x07060302u);                  // upper halves of x1 : x0
-#if MS_EGNN_SPLIT_PK
-    // Round 6 (VERDICT r05 #5a), measured and NOT the default: both residual subtractions of the pair as ONE packed fp32 instruction each
-    // (v_pk_add_f32 with the second operand negated) -- 9 vector instructions per pair instead of 11, the same bits (x - trunc(x) is exact
-    // either way), but the packed add wants its operands in aligned register pairs and issues no faster than two scalar ones here
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    const f32x2_ r = f32x2_{x0, x1} - f32x2_{__uint_as_float(a & 0xFFFF0000u), __uint_as_float(b & 0xFFFF0000u)};
-    const uint32_t c = __float_as_uint(r.x), d = __float_as_uint(r.y);
-    mid = __builtin_amdgcn_perm(d, c, 0x07060302u);
-    const f32x2_ s = r - f32x2_{__uint_as_float(c & 0xFFFF0000u), __uint_as_float(d & 0xFFFF0000u)};
-    lo = __builtin_amdgcn_perm(__float_as_uint(s.y), __float_as_uint(s.x), 0x07060302u);
-#else
     const float r0 = x0 - __uint_as_float(a & 0xFFFF0000u), r1 = x1 - __uint_as_float(b & 0xFFFF0000u);
     const uint32_t c = __float_as_uint(r0), d = __float_as_uint(r1);
     mid = __builtin_amdgcn_perm(d, c, 0x07060302u);
     const float s0 = r0 - __uint_as_float(c & 0xFFFF0000u), s1 = r1 - __uint_as_float(d & 0xFFFF0000u);
     lo = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-#endif
 }
 
 __device__ __forceinline__ float silu_f(float x) {
@@ -338,27 +323,13 @@ struct EdgeParams {
 // cluster behind the stage's 160 MFMAs, kept there by a scheduling fence (hipcc would spread it through the MFMAs).
 constexpr int W_STAGE_F4 = STAGE_G * 8 * 64;                      // float4 per W2 stage (40 KiB)
 constexpr int EDGE_LDS = 2 * W_STAGE_F4 * 16;                     // two ring slots: 80 KiB per workgroup, two workgroups per CU
-#ifndef MS_EGNN_W8
-#define MS_EGNN_W8 0            // round 5 A/B (profiles/r05_egnn_variants_ab.log): the 8-wave workgroup is correct and no faster (58.2-58.3 against 57.4-57.9 ms)
-#endif
-#ifndef MS_EGNN_BPREFETCH
-#define MS_EGNN_BPREFETCH 1
-#endif
-#ifndef MS_EGNN_LOAD_NT
-#define MS_EGNN_LOAD_NT 4       // the channel tile of a k block behind which the projections of block b + 2 are requested: their registers are free
-                                // from tile 4 on, and three tiles more of lead cover the L2 round trip (tile 7, round 4: 59.1 -> 57.7 ms)
-#endif
-// split form, MS_EGNN_W8=1 (round 5, built, parity-green, NOT the default): ONE workgroup of EIGHT waves per CU -- two 128-edge tiles side
-// by side (waves 0-3 / 4-7) over ONE W2S ring of six 24 KiB slots, a barrier every SECOND k block, every W2S block crossing L2 -> LDS
-// once per CU instead of twice.  Round 4's stamps had the waves of a SIMD waiting at their barriers 28 % of the time; halving the
-// barriers and sharing the ring changed NOTHING (same-box A/B, profiles/r05_egnn_variants_ab.log) -- the wait is not the barrier's.
-// The default stays round 4's form: two workgroups of four waves per CU, a ring of three slots each, a barrier per block.
-constexpr bool EGNN_W8 = MS_EGNN_W8 != 0;
-constexpr int EDGE_RING_SPLIT = EGNN_W8 ? 6 : 3;
-#ifndef MS_EGNN_DYNPRIO
-#define MS_EGNN_DYNPRIO 0
-#endif
-constexpr int EDGE_LDS_SPLIT = EDGE_RING_SPLIT * W2S_BLOCK_BYTES; // split form: slots of one k block (24 KiB) each: 144 KiB (72 KiB with 3)
+constexpr int EDGE_LOAD_NT = 4;   // the channel tile of a k block behind which the projections of block b + 2 are requested: their registers are free
+                                  // from tile 4 on, and three tiles more of lead cover the L2 round trip (tile 7, round 4: 59.1 -> 57.7 ms)
+// split form: two workgroups of four waves per CU, a ring of three slots each, a barrier per block.  Round 4's stamps had the waves of a
+// SIMD waiting at their barriers 28 % of the time; halving the barriers and sharing one ring between eight waves changed nothing (round 5,
+// profiles/r05_egnn_variants_ab.log) -- the wait is not the barrier's.
+constexpr int EDGE_RING_SPLIT = 3;
+constexpr int EDGE_LDS_SPLIT = EDGE_RING_SPLIT * W2S_BLOCK_BYTES; // split form: slots of one k block (24 KiB) each: 72 KiB
 
 // SPLIT (round 4): the same GEMM on the bf16 matrix instruction -- v_mfma_f32_32x32x16_bf16 at 16 x the rate of the fp32 one --
 // with both operands split three ways (split3_pair): per 16 k and 32 channels SIX matrix instructions (hi.hi, hi.mid, mid.hi,
@@ -368,17 +339,14 @@ constexpr int EDGE_LDS_SPLIT = EDGE_RING_SPLIT * W2S_BLOCK_BYTES; // split form:
 // that computes it (~45 vector instructions per 8 values, in the shadow of the 48 matrix instructions of a k block: next to the
 // bf16 matrix instruction vector instructions are NOT additive).  One barrier per k block.
 template <bool SPLIT>
-__global__ __launch_bounds__((SPLIT && EGNN_W8) ? 512 : 256, 2) void ms_egnn_edge_kernel(const EdgeParams p) {
+__global__ __launch_bounds__(256, 2) void ms_egnn_edge_kernel(const EdgeParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4 *Wring = reinterpret_cast<f32x4 *>(smem);                 // [2 slots][5 g][8 nt][64 lanes]
-    constexpr bool W8 = SPLIT && EGNN_W8;
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..7 with eight waves: DMA pieces are dealt over all of them
-    const int wave = W8 ? (wave_all & 3) : wave_all;                // this wave's 32 rows inside ITS tile
-    const int T_raw = W8 ? 2 * (int)blockIdx.x + (wave_all >> 2) : (int)blockIdx.x;
-    const bool tile_valid = T_raw < p.n_tiles;                      // (an odd number of tiles: the last workgroup's second half only loads and synchronises)
-    const int T = tile_valid ? T_raw : p.n_tiles - 1;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // this wave's 32 rows of the tile
+    const bool tile_valid = (int)blockIdx.x < p.n_tiles;            // (one workgroup per tile: a guard, clamped to the last tile)
+    const int T = tile_valid ? (int)blockIdx.x : p.n_tiles - 1;
     const int d = find_segment(p.tile_pre, p.nb, T);
     const int off = p.offsets[d];
     const int n = p.offsets[d + 1] - off;
@@ -504,9 +472,9 @@ __global__ __launch_bounds__((SPLIT && EGNN_W8) ? 512 : 256, 2) void ms_egnn_edg
         const u32x4_e *Sring = reinterpret_cast<const u32x4_e *>(smem);      // [3 slots][8 nt][3 parts][64 lanes] of 16 bytes
         const u32x4_e *w2s = reinterpret_cast<const u32x4_e *>(p.prep + P_W2S);
         constexpr int BLK_V = 8 * 3 * 64;                                    // 16-byte vectors per k block
-        constexpr int PPW = W8 ? 3 : 6;                                      // 1 KiB pieces of a block per wave (24 in all)
+        constexpr int PPW = 6;                                               // 1 KiB pieces of a block per wave (24 in all)
         auto dma_s = [&](int b, int piece) {                                 // pieces PPW w .. PPW w + PPW - 1 of block b -> slot b % ring
-            const int pidx = wave_all * PPW + piece;
+            const int pidx = wave * PPW + piece;
             const uint64_t base = (uint64_t)(uintptr_t)w2s + ((uint64_t)b * BLK_V + (uint64_t)pidx * 64) * 16;
             const uint32_t dst = (uint32_t)__builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(((b % EDGE_RING_SPLIT) * BLK_V + pidx * 64) * 16));
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(dst), "v"(voff_w), "s"(base) : "memory", "m0");
@@ -544,15 +512,9 @@ __global__ __launch_bounds__((SPLIT && EGNN_W8) ? 512 : 256, 2) void ms_egnn_edg
             }
             ah = __builtin_bit_cast(bf16x8_e, hi); am = __builtin_bit_cast(bf16x8_e, mid); al = __builtin_bit_cast(bf16x8_e, lo);
         };
-#if MS_EGNN_DYNPRIO
-        uint32_t *prio_cnt = reinterpret_cast<uint32_t *>(smem + EDGE_LDS_SPLIT);      // (64 bytes behind the ring)
-        if (tid == 0) *prio_cnt = 0u;
-        __syncthreads();
-#endif
-        // prologue: the first blocks of the ring are requested before anything else (8 waves: four blocks ahead; 4 waves: two)
-        constexpr int AHEAD = W8 ? 4 : 2;
+        // prologue: the first two blocks of the ring are requested before anything else
 #pragma unroll
-        for (int b0 = 0; b0 < AHEAD; ++b0)
+        for (int b0 = 0; b0 < 2; ++b0)
 #pragma unroll
             for (int pc_ = 0; pc_ < PPW; ++pc_) dma_s(b0, pc_);
         load6(0);
@@ -564,41 +526,21 @@ __global__ __launch_bounds__((SPLIT && EGNN_W8) ? 512 : 256, 2) void ms_egnn_edg
         for (int b = 0; b < KB16; ++b) {
             // W2S block b has landed for every wave (each waited for its own pieces in the middle of the last iteration), and every
             // wave is done reading slot (b - 1) % 3, which block b + 2 is about to overwrite.
-            // Eight waves, six slots: ONE barrier per PAIR of blocks -- before blocks 2p, 2p + 1 every wave has waited for its pieces of
-            // both (they were requested four blocks ahead; the vmcnt(0) in the middle of block 2p - 1 covers everything requested up to
-            // block 2p - 2, i.e. blocks <= 2p + 2) and is done with the pair before; during block b the pieces of block b + 4 go to
-            // slot (b + 4) % 6 = (b - 2) % 6, a slot of the PREVIOUS pair, which nobody reads any more.
-#if MS_EGNN_DYNPRIO
-            if constexpr (!W8) {
-                // Round 6 experiment: the wave that arrives LAST at a block's barrier -- the one its workgroup waited for -- takes the higher
-                // issue priority for the next block's chain, the others the lower one (arrival order from a counter in LDS: 4 adds per block)
-                uint32_t ord_ = 0;
-                if (lane == 0) ord_ = __hip_atomic_fetch_add(prio_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                ord_ = (uint32_t)__builtin_amdgcn_readfirstlane((int)ord_) & 3u;
-                __syncthreads();
-                if (ord_ == 3u) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0);
-            } else
-#endif
-            if (!W8 || (b & 1) == 0) __syncthreads();
+            __syncthreads();
             EST(tB1)
             const u32x4_e *Sl = Sring + (b % EDGE_RING_SPLIT) * BLK_V + lane;
             // (round 5: the three B fragments of channel tile nt + 1 are requested BEFORE the six matrix instructions of tile nt -- hipcc
             //  left every ds_read_b128 right in front of its first use with an s_waitcnt behind it: eight exposed LDS round trips per
-            //  block and wave; MS_EGNN_BPREFETCH=0 at build time keeps that form)
+            //  block and wave)
             u32x4_e bq[3] = {Sl[0], Sl[64], Sl[128]};
 #pragma unroll
             for (int nt = 0; nt < 8; ++nt) {
-#if MS_EGNN_BPREFETCH
                 const u32x4_e c0 = bq[0], c1 = bq[1], c2 = bq[2];
                 if (nt + 1 < 8) {
                     bq[0] = Sl[((nt + 1) * 3 + 0) * 64]; bq[1] = Sl[((nt + 1) * 3 + 1) * 64]; bq[2] = Sl[((nt + 1) * 3 + 2) * 64];
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const bf16x8_e bh = __builtin_bit_cast(bf16x8_e, c0), bm = __builtin_bit_cast(bf16x8_e, c1), bl = __builtin_bit_cast(bf16x8_e, c2);
-#else
-                const bf16x8_e bh = __builtin_bit_cast(bf16x8_e, Sl[(nt * 3 + 0) * 64]), bm = __builtin_bit_cast(bf16x8_e, Sl[(nt * 3 + 1) * 64]),
-                               bl = __builtin_bit_cast(bf16x8_e, Sl[(nt * 3 + 2) * 64]);
-#endif
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[nt], 0, 0, 0);
                 acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[nt], 0, 0, 0);
@@ -611,12 +553,8 @@ __global__ __launch_bounds__((SPLIT && EGNN_W8) ? 512 : 256, 2) void ms_egnn_edg
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     make_a(nh, nm, nl);
                 }
-                if constexpr (W8) {
-                    if (nt >= 5 && b + 4 < KB16) dma_s(b + 4, nt - 5);
-                } else {
-                    if (nt >= 5 && b + 2 < KB16) { dma_s(b + 2, 2 * (nt - 5)); dma_s(b + 2, 2 * (nt - 5) + 1); }
-                }
-                if (nt == MS_EGNN_LOAD_NT && b + 2 < KB16) load6(b + 2);
+                if (nt >= 5 && b + 2 < KB16) { dma_s(b + 2, 2 * (nt - 5)); dma_s(b + 2, 2 * (nt - 5) + 1); }
+                if (nt == EDGE_LOAD_NT && b + 2 < KB16) load6(b + 2);
             }
             EST(tM)
             ah = nh; am = nm; al = nl;
@@ -945,7 +883,7 @@ int ms_egnn_embed(const void *prepared, const float *pe, int pe_len, const float
     MS_LAUNCH_CHECK("ms_egnn_init_nodes_kernel");
     // the edge GEMM: split-bf16 matrix instructions (default; fp32-grade results) or MS_EGNN_SPLIT=0: the fp32 ones
     static const int split_form = [] { const char *e = getenv("MS_EGNN_SPLIT"); return e ? atoi(e) : 1; }();
-    const size_t edge_lds = split_form ? (size_t)EDGE_LDS_SPLIT + (MS_EGNN_DYNPRIO ? 64 : 0) : (size_t)EDGE_LDS;
+    const size_t edge_lds = split_form ? (size_t)EDGE_LDS_SPLIT : (size_t)EDGE_LDS;
     if (split_form)
         MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_egnn_edge_kernel<true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)edge_lds));
@@ -966,8 +904,7 @@ int ms_egnn_embed(const void *prepared, const float *pe, int pe_len, const float
 #ifdef MS_STAMP
         ep.stamps = ms_egnn_stamp_buffer();
 #endif
-        if (split_form && EGNN_W8) hipLaunchKernelGGL(ms_egnn_edge_kernel<true>, dim3((unsigned)((tiles + 1) / 2)), dim3(512), edge_lds, st, ep);
-        else if (split_form) hipLaunchKernelGGL(ms_egnn_edge_kernel<true>, dim3((unsigned)tiles), dim3(256), edge_lds, st, ep);
+        if (split_form) hipLaunchKernelGGL(ms_egnn_edge_kernel<true>, dim3((unsigned)tiles), dim3(256), edge_lds, st, ep);
         else hipLaunchKernelGGL(ms_egnn_edge_kernel<false>, dim3((unsigned)tiles), dim3(256), edge_lds, st, ep);
         MS_LAUNCH_CHECK("ms_egnn_edge_kernel");
         NodeParams np;

@@ -205,11 +205,9 @@ __device__ __forceinline__ float ms_wave_sum_xor(float v) {       // the butterf
     return v;
 }
 
-// (MS_BODY_DMA_AUX: the rows of a few-query search are read ONCE, by one workgroup -- the non-temporal policy, `nt`, of the guide's
+// (BODY_DMA_AUX: the rows of a few-query search are read ONCE, by one workgroup -- the non-temporal policy, `nt`, of the guide's
 //  weight streams: 6.4 -> 6.5-6.8 TB/s there)
-#ifndef MS_BODY_DMA_AUX
-#define MS_BODY_DMA_AUX 2
-#endif
+constexpr int BODY_DMA_AUX = 2;
 // One wave = one (query tile, row stream) pair, one wave per SIMD; waves never synchronise
 // with each other inside the scan.  The loop over 32-row tiles is software-pipelined around
 // the dependent chain of 64 v_mfma_f32_32x32x2_f32 of tile t (4096 cycles of matrix pipe):
@@ -369,13 +367,11 @@ __device__ __forceinline__ void ms_pair_insert(ScanState<KL> &st, float cand, ui
 
 // insertion steps for one 32-row tile whose (scaled, masked) scores are sc[16]; rows in ascending
 // order: row 8 g + 4 hh + j lives in lanes of half hh, register 4 g + j
-#ifndef MS_STATIC_INSERT_MAX_KL
-#define MS_STATIC_INSERT_MAX_KL 32
-#endif
+constexpr int STATIC_INSERT_MAX_KL = 32;       // longest list that gets one static copy of the step per row (without the histogram)
 template <int KL, bool HIST = false, bool LOOP = false>      // LOOP: the runtime-loop form whatever the list length (small code)
 __device__ __forceinline__ void ms_tile_insert(ScanState<KL> &st, const float (&sc)[16], const uint64_t (&m)[16],
                                                int64_t sub_row0, int r, int h, const ScanHist *hg = nullptr) {
-    if (!LOOP && KL <= (HIST ? 16 : MS_STATIC_INSERT_MAX_KL)) {
+    if (!LOOP && KL <= (HIST ? 16 : STATIC_INSERT_MAX_KL)) {
         // short lists (k <= 10, the common case): one static copy of the step per row
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -453,11 +449,7 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
 #pragma unroll
     for (int j = 0; j < KL; ++j) { st.ls[j] = -INFINITY; st.li[j] = MS_IDX_NONE; }
     st.floor = -INFINITY;
-#ifdef MS_DEBUG_NO_INSERT
-    st.tau = INFINITY;
-#else
     st.tau = -INFINITY;
-#endif
 
     // MAXONLY (sample pass): no lists, only this lane's best row so far (its half of every tile)
     float smax = -INFINITY;
@@ -474,9 +466,7 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
             // below it cannot reach the top k; rows that tie with it still can
             const float lb = p.lb_s[qidx];
             st.floor = (lb == -INFINITY) ? -INFINITY : nextafterf(lb, -INFINITY);
-#ifndef MS_DEBUG_NO_INSERT
             st.tau = st.floor;
-#endif
         }
         // padding queries of the last tile never pass the filter: threshold +inf (one compare per score)
         if (!q_valid) { st.floor = INFINITY; st.tau = INFINITY; }
@@ -508,7 +498,7 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
                 for (int it = 0; it < 16; ++it) {
                     const char *src = tile_src + it * 1024 + off8[it & 7];
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                     (__attribute__((address_space(3))) void *)(dst + it * 64), 16, 0, MS_BODY_DMA_AUX);
+                                                     (__attribute__((address_space(3))) void *)(dst + it * 64), 16, 0, BODY_DMA_AUX);
                 }
             } else {   // last tile of the database: clamp rows past the end (their scores are discarded)
 #pragma unroll
@@ -517,7 +507,7 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
                     if (row >= p.n) row = p.n - 1;
                     const char *src = reinterpret_cast<const char *>(p.db) + row * 512 + 16 * ((r ^ h) ^ ((2 * it) & 15));
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                                     (__attribute__((address_space(3))) void *)(dst + it * 64), 16, 0, MS_BODY_DMA_AUX);
+                                                     (__attribute__((address_space(3))) void *)(dst + it * 64), 16, 0, BODY_DMA_AUX);
                 }
             }
         };
@@ -683,7 +673,7 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
                 // of this one.  vmcnt(8): everything but the 8 pieces of tile t+2 issued so far.
                 if (tt == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(dma_src + tt * 1024 + off8[tt & 7]),
-                                                 (__attribute__((address_space(3))) void *)(dma_dst + tt * 64), 16, 0, MS_BODY_DMA_AUX);
+                                                 (__attribute__((address_space(3))) void *)(dma_dst + tt * 64), 16, 0, BODY_DMA_AUX);
                 if (tt == 15) issue_aux_dma(tnext);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qreg[4 * tt + 2], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qreg[4 * tt + 3], acc, 0, 0, 0);
@@ -984,25 +974,15 @@ __device__ __forceinline__ void ms_scan_body(const ScanParams &p_in) {
 //   * filter of tile t-1: 8 v_max3 fold the lane's 16 scores into one maximum, ONE compare per tile;
 //   * slot base of tile t+1: one v_add; loader flag: one ds_read_b32 + v_readfirstlane; consumed counter: ds_add
 //     under an EXEC mask set by scalar moves.  11 vector instructions per tile in inner-product mode.
-#ifndef MS_HIST_PERIOD
-#define MS_HIST_PERIOD 16        // tiles between two looks at the shared bound's counters (a power of two)
-#endif
-#ifndef MS_LDR_R
-#define MS_LDR_R 8
-#endif
-#ifndef MS_LDR_D
-#define MS_LDR_D 3
-#endif
-constexpr int LDR_R = MS_LDR_R;  // ring slots (tiles)
-constexpr int LDR_D = MS_LDR_D;  // tiles the loader keeps in flight before publishing the oldest
+constexpr int HIST_PERIOD = 16;  // tiles between two looks at the shared bound's counters (a power of two)
+constexpr int LDR_R = 8;         // ring slots (tiles)
+constexpr int LDR_D = 3;         // tiles the loader keeps in flight before publishing the oldest
 constexpr int LDR_AUX = 2 * LDR_R;   // aux (row scale / length) ring: a tile's aux data is read up to two stages after its slot was
                                      // released, while the loader may run LDR_R - 1 tiles ahead of the slowest wave
 constexpr int LDR_LDS = LDR_R * 16384 + LDR_AUX * 256 + 64;
 // Append-and-flush rare path (lists of 16 / 32 entries per lane, k > 20): candidate buffers, LDR_CAND entries of 8 bytes per lane
 // and compute wave, behind the counters
-#ifndef MS_APPEND_MIN_KL
-#define MS_APPEND_MIN_KL 32
-#endif
+constexpr int APPEND_MIN_KL = 32;
 constexpr int LDR_CAND = 8;
 constexpr int LDR_LDS_APPEND = LDR_LDS + 4 * LDR_CAND * 512;
 
@@ -1017,10 +997,6 @@ constexpr int LDR_LDS_APPEND = LDR_LDS + 4 * LDR_CAND * 512;
 template <int IMM>
 __device__ __forceinline__ void ms_glds_s16(uint32_t lds_addr, uint32_t lane_off, uint64_t sbase) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(lds_addr - (uint32_t)IMM), "v"(lane_off), "s"(sbase), "i"(IMM) : "memory", "m0");
-}
-template <int IMM>      // the same with the non-temporal policy (rows that ONE workgroup reads once)
-__device__ __forceinline__ void ms_glds_s16_nt(uint32_t lds_addr, uint32_t lane_off, uint64_t sbase) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3 nt" ::"s"(lds_addr - (uint32_t)IMM), "v"(lane_off), "s"(sbase), "i"(IMM) : "memory", "m0");
 }
 template <int IMM>      // the same with sc1: past this CU's L1 (counters other workgroups are adding to)
 __device__ __forceinline__ void ms_glds_s16_sc1(uint32_t lds_addr, uint32_t lane_off, uint64_t sbase) {
@@ -1044,11 +1020,6 @@ __device__ __forceinline__ void ms_vmcnt_tiles() {   // wait until at most N til
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-#ifdef MS_ABL_NOFLAG
-#define MS_ABL_NOFLAG_ 1
-#else
-#define MS_ABL_NOFLAG_ 0
-#endif
 // Pinned instructions of the compute waves' stage (volatile asm statements keep their program order).
 #define MS_MFMA(ACC, A, B) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(B))
 #define MS_MFMA_Z(ACC, A, B) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, 0" : "=v"(ACC) : "v"(A), "v"(B))   // C = 0 inline: a new chain
@@ -1147,11 +1118,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
 #endif
         for (int t = 0; t < ntl; ++t) {
             if (t >= LDR_R) {                          // slot t % R is free once everybody has read tile t - R
-#ifdef MS_ABL_EXEC1
-                const uint32_t need = (uint32_t)(t - LDR_R + 1);
-#else
                 const uint32_t need = (uint32_t)(t - LDR_R + 1) * 64u;      // (every lane of a compute wave adds: units of 64)
-#endif
                 for (uint32_t spins = 0;; ++spins) {
                     const uint32_t c0 = consumed[0], c1 = consumed[1], c2 = consumed[2], c3 = consumed[3];
                     const uint32_t m01 = c0 < c1 ? c0 : c1, m23 = c2 < c3 ? c2 : c3;
@@ -1179,14 +1146,10 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
             const uint32_t b_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);        // (the builtin returns int:
             const uint32_t b_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));  //  no sign extension)
             const uint64_t sb = ((uint64_t)b_hi << 32) | (uint64_t)b_lo;
-#ifdef MS_ABL_NODMA
-#define MS_PIECE(IT)
-#else
             // (prefilter: 64 idle cycles behind every piece -- a burst of 16 VMEM instructions holds the SIMD's vector issue port
             //  against the compute wave it shares with, whose stage is vector-issue bound there: 4-6 % of the call; the fp32 stage,
             //  bound by the matrix pipe, is faster with the burst)
 #define MS_PIECE(IT) ms_glds_s16<32 * (IT)>(slot_lds + (IT) * 1024, voff, sb); if (PF) __builtin_amdgcn_s_sleep(1);
-#endif
             MS_PIECE(0) MS_PIECE(1) MS_PIECE(2) MS_PIECE(3) MS_PIECE(4) MS_PIECE(5) MS_PIECE(6) MS_PIECE(7)
             MS_PIECE(8) MS_PIECE(9) MS_PIECE(10) MS_PIECE(11) MS_PIECE(12) MS_PIECE(13) MS_PIECE(14) MS_PIECE(15)
 #undef MS_PIECE
@@ -1222,19 +1185,13 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
 #pragma unroll
     for (int j = 0; j < (SAMPLE ? 1 : KL); ++j) { st.ls[j] = -INFINITY; st.li[j] = MS_IDX_NONE; }
     st.floor = -INFINITY;
-#ifdef MS_DEBUG_NO_INSERT
-    st.tau = INFINITY;
-#else
     st.tau = -INFINITY;
-#endif
     const int qidx = qtile * 32 + r;
     const bool q_valid = qidx < p.nq;
     if (!SAMPLE && p.lb_s != nullptr) {
         const float lb = p.lb_s[qidx];
         st.floor = (lb == -INFINITY) ? -INFINITY : nextafterf(lb, -INFINITY);
-#ifndef MS_DEBUG_NO_INSERT
         st.tau = st.floor;
-#endif
     }
     if (!q_valid) { st.floor = INFINITY; st.tau = INFINITY; }   // padding queries never pass the filter
     ScanHist hg;
@@ -1328,7 +1285,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
     //   registers), and at the end of the stream, the buffers are emptied: per round every query takes the candidate with the
     //   smaller row of its two lanes' buffer heads (rows ascend within a buffer: a two-way merge, so ties still go to the lower
     //   row) and ONE insertion step serves all 32 queries (ms_pair_insert).  Thresholds move at flushes and with the shared bound.
-    constexpr bool APPEND = KL >= MS_APPEND_MIN_KL && !SAMPLE && !PF;
+    constexpr bool APPEND = KL >= APPEND_MIN_KL && !SAMPLE && !PF;
     typedef __attribute__((address_space(3))) ms_u32x2 lds_cand_t;
     uint32_t ccnt = 0;
 #ifdef MS_STAMP_FLUSH
@@ -1415,7 +1372,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
     // loader's counter into `flag` for the next pair.  The chain itself contains no branch and no scalar dependency.
     auto ensure_landed = [&](int t) {            // before the first stage of a pair: tiles t+1 and t+2 (as far as they exist)
         const uint32_t need = (uint32_t)((t + 3 < ntl) ? t + 3 : ntl);
-        if (__builtin_expect(!MS_ABL_NOFLAG_ && landed_seen < need, 0)) {
+        if (__builtin_expect(landed_seen < need, 0)) {
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(flag) :: "memory");
             landed_seen = __builtin_amdgcn_readfirstlane(flag);
             if (landed_seen < need) {                                         // normally long since published
@@ -1444,11 +1401,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
         if (FIRST) {
             // (the look at the loader's counter for this pair sits in front of the stage, in `ensure_landed`)
         } else {
-#ifdef MS_ABL_EXEC1
-            asm volatile("s_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1" ::"v"(cons_addr), "v"(two) : "memory");
-#else
             asm volatile("ds_add_u32 %0, %1" ::"v"(cons_addr), "v"(two) : "memory");     // tiles t-1 and t are in registers
-#endif
         }
         const uint32_t slot_off = (uint32_t)((t + 1) % LDR_R) * 16384u;
         float mx;
@@ -1464,30 +1417,20 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
         if (SCALE_IN_CHAIN) { __builtin_amdgcn_sched_barrier(0); scale_group(prev, t - 1, 2); scale_group(prev, t - 1, 3); __builtin_amdgcn_sched_barrier(0); }
         MS_GROUP(3, false)
         // the lane's maximum over the 16 scores of tile t-1 (the running maximum of the whole sample in SAMPLE mode)
-#ifdef MS_ABL_NOMAX
-        mx = prev[0];
-#define MS_MAX3_(M, A, B)
-#else
-#define MS_MAX3_(M, A, B) MS_MAX3(M, A, B)
-#endif
         if (SAMPLE) {
             MS_MAX3(smax, prev[0], prev[1]); MS_MAX3(smax, prev[2], prev[3]); MS_MAX3(smax, prev[4], prev[5]); MS_MAX3(smax, prev[6], prev[7]);
         } else {
-#ifndef MS_ABL_NOMAX
             asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(mx) : "v"(prev[0]), "v"(prev[1]), "v"(prev[2]));
-#endif
-            MS_MAX3_(mx, prev[3], prev[4]); MS_MAX3_(mx, prev[5], prev[6]); MS_MAX3_(mx, prev[7], prev[8]);
+            MS_MAX3(mx, prev[3], prev[4]); MS_MAX3(mx, prev[5], prev[6]); MS_MAX3(mx, prev[7], prev[8]);
         }
         MS_GROUP(4, false)
         if (SAMPLE) {
             MS_MAX3(smax, prev[8], prev[9]); MS_MAX3(smax, prev[10], prev[11]); MS_MAX3(smax, prev[12], prev[13]); MS_MAX3(smax, prev[14], prev[15]);
         } else {
-            MS_MAX3_(mx, prev[9], prev[10]); MS_MAX3_(mx, prev[11], prev[12]); MS_MAX3_(mx, prev[13], prev[14]);
-#ifndef MS_ABL_NOMAX
+            MS_MAX3(mx, prev[9], prev[10]); MS_MAX3(mx, prev[11], prev[12]); MS_MAX3(mx, prev[13], prev[14]);
             asm volatile("v_max_f32 %0, %0, %1" : "+v"(mx) : "v"(prev[15]));
-#endif
         }
-        if (!FIRST && !MS_ABL_NOFLAG_) asm volatile("ds_read_b32 %0, %1" : "=v"(flag) : "v"(landed_addr) : "memory");     // for the next pair
+        if (!FIRST) asm volatile("ds_read_b32 %0, %1" : "=v"(flag) : "v"(landed_addr) : "memory");     // for the next pair
         MS_GROUP(5, false)
         MS_GROUP(6, false)
         asm volatile("v_add_u32 %0, %1, %2" : "=v"(rbase) : "s"(slot_off), "v"(lin0));
@@ -1500,7 +1443,6 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
         if (LATE_WAIT) {    // fragments 12..15 of THIS tile: everything older than this stage's own LDS operations (8 refill reads; the
                             // second stage of a pair also issued its counter add and re-read) has returned
             if (FIRST) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(areg[12]), "+v"(areg[13]), "+v"(areg[14]), "+v"(areg[15]) :: "memory");
-            else if (MS_ABL_NOFLAG_) asm volatile("s_waitcnt lgkmcnt(9)" : "+v"(areg[12]), "+v"(areg[13]), "+v"(areg[14]), "+v"(areg[15]) :: "memory");
             else asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(areg[12]), "+v"(areg[13]), "+v"(areg[14]), "+v"(areg[15]) :: "memory");
         }
         MS_GROUP(12, false) MS_REFILL(12)
@@ -1509,17 +1451,10 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
         MS_GROUP(15, false) MS_REFILL(15)
 #undef MS_GROUP
 #undef MS_REFILL
-#undef MS_MAX3_
 #undef MS_AREG_ALL
         __builtin_amdgcn_sched_barrier(0);
-#ifdef MS_ABL_NOCMP
-        asm volatile("" ::"v"(mx));
-        if (false) {
-            if (false) {
-#else
         if (!SAMPLE) {
             if (__builtin_expect(__ballot(mx > st.tau) != 0 || (AUXM == 2 && neg_tau), 0)) {
-#endif
 #ifdef MS_STAMP
                 const unsigned long long i0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1731,7 +1666,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
             // (asm: four loads, asynchronous, no wait here.  The insertion path -- compiler-scheduled code -- may run while they are
             //  in flight, and a register the hardware fills behind the compiler's back is not safe there: it starts with a
             //  wait for them, see `stage`.  The prefilter's stage is compiler-scheduled throughout and uses atomic loads.)
-            if (hist_on && (t & (MS_HIST_PERIOD - 1)) == MS_HIST_PERIOD / 2) {
+            if (hist_on && (t & (HIST_PERIOD - 1)) == HIST_PERIOD / 2) {
                 const uint32_t *hp = hg.counters != nullptr ? hg.counters : p.hist;
                 if (PF) {
                     uint32_t c_[16];
@@ -1750,7 +1685,7 @@ __global__ __launch_bounds__(320, 2) void ms_scan_loader_kernel(const ScanParams
             run_stage(std::false_type{}, t + 1, acc1, acc0);
             int t2 = t;
             asm volatile("" : "+s"(t2));
-            if (hist_on && (t2 & (MS_HIST_PERIOD - 1)) == MS_HIST_PERIOD / 2) {
+            if (hist_on && (t2 & (HIST_PERIOD - 1)) == HIST_PERIOD / 2) {
                 // the highest bucket edge with at least k rows at or above it (counted by all waves so far) bounds the k-th best
                 if (!PF) {     // (compiler-scheduled arithmetic follows: the counters and the stage's last fragment reads must have landed)
                     asm volatile("s_waitcnt vmcnt(0)" : "+v"(hc0), "+v"(hc1), "+v"(hc2), "+v"(hc3) :: "memory");
@@ -1894,7 +1829,7 @@ int launch_scan_variant(const ScanPlan &pl, const ScanParams &sp, hipStream_t st
         }
         if (sp.qwb == 4 && loader_wave_setting()) {     // MFMA-bound batches
 #define MS_LAUNCH_LOADER(AUXM)                                                                                           \
-            constexpr int lds_ = KL >= MS_APPEND_MIN_KL ? LDR_LDS_APPEND : LDR_LDS;       /* (the candidate buffers of the append-and-flush rare path) */ \
+            constexpr int lds_ = KL >= APPEND_MIN_KL ? LDR_LDS_APPEND : LDR_LDS;       /* (the candidate buffers of the append-and-flush rare path) */ \
             MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_loader_kernel<KL, AUXM, false>),     \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_));                         \
             hipLaunchKernelGGL((ms_scan_loader_kernel<KL, AUXM, false>), dim3(pl.grid), dim3(320), lds_, st, sp);

@@ -38,18 +38,9 @@
 #pragma once
 #include "ms_scan.h"
 
-#ifndef MS_PF2_R
-#define MS_PF2_R 8
-#endif
-#ifndef MS_PF2_D
-#define MS_PF2_D 6
-#endif
-#ifndef MS_PF2_W
-#define MS_PF2_W 3
-#endif
-constexpr int PF2_R = MS_PF2_R;                // ring slots (16 KiB tiles)
-constexpr int PF2_D = MS_PF2_D;                // a wave issues its pieces of tile t + D during stage t
-constexpr int PF2_W = MS_PF2_W;                // ... then waits for its pieces of tiles <= t + W (issued D - W stages ago: HBM latency) and
+constexpr int PF2_R = 8;                       // ring slots (16 KiB tiles)
+constexpr int PF2_D = 6;                       // a wave issues its pieces of tile t + D during stage t
+constexpr int PF2_W = 3;                       // ... then waits for its pieces of tiles <= t + W (issued D - W stages ago: HBM latency) and
                                                // publishes them
 // No "consumed" counters: no wave starts stage t before every wave has published tile t + 1, which a wave does near the end of its
 // stage t + 1 - W, with tile t + 1 - W in its registers and all but the last two fragments of tile t + 2 - W read.  So when a wave
@@ -60,11 +51,7 @@ static_assert(PF2_W >= 2 && PF2_D - PF2_W >= 1 && PF2_R >= PF2_D + PF2_W - 1, "r
 constexpr int PF2_AUXR = 16;                   // aux ring: the row lengths of a tile (256 B per slot), cosine mode
 constexpr int PF2_CAND = 4;                    // candidates a lane buffers before the lists take them
 constexpr int PF2_OFF_AUX = PF2_R * 16384;
-#ifndef MS_PF2_HIST_AREAS
-#define MS_PF2_HIST_AREAS 4
-#endif
-constexpr int PF2_HIST_AREAS = MS_PF2_HIST_AREAS;               // 4: waves w and w + 4 take turns at area w & 3 (half a period of 16 tiles apart); 8: one per wave
-static_assert(PF2_HIST_AREAS == 4 || PF2_HIST_AREAS == 8, "staging areas of the shared bound");
+constexpr int PF2_HIST_AREAS = 4;                               // waves w and w + 4 take turns at area w & 3 (half a period of 16 tiles apart)
 constexpr int PF2_OFF_HIST = PF2_OFF_AUX + PF2_AUXR * 256;      // the shared bound's counters of a wave's 32 queries, staged by LDS-DMA: 2 KiB per area
 constexpr int PF2_OFF_CAND = PF2_OFF_HIST + PF2_HIST_AREAS * 2048;           // [wave][slot][lane] (score, row): 512 B per slot
 constexpr int PF2_ARR = 16;                                     // arrival counters: one per tile modulo 16, counting up by NW per reuse
@@ -73,7 +60,7 @@ constexpr int PF2_OFF_DUMMY = PF2_OFF_CNT + 64;                 // cosine mode: 
 constexpr int PF2_LDS = PF2_OFF_DUMMY + 7 * 256;
 static_assert(PF2_ARR > PF2_R + PF2_W, "a counter is not reused while anybody may still wait for its previous tile");
 static_assert(PF2_LDS <= 160 * 1024, "LDS of one CU");
-static_assert(MS_HIST_PERIOD >= 16, "eight waves take turns at four staging areas: phases 2 w and 2 w + 2 of a period");
+static_assert(HIST_PERIOD >= 16, "eight waves take turns at four staging areas: phases 2 w and 2 w + 2 of a period");
 
 typedef uint32_t ms_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -144,11 +131,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf2_kernel(const Scan
             // (uniform values that live across branches: say so again, or the "s" operands of the asm may be handed vector registers)
             const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane(it_dst);
             const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)it_sb), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(it_sb >> 32));
-#ifdef MS_PF2_NT
-            ms_glds_s16_nt<1024 * I>(d + 1024 * I, voff, ((uint64_t)hi << 32) | (uint64_t)lo);
-#else
             ms_glds_s16<1024 * I>(d + 1024 * I, voff, ((uint64_t)hi << 32) | (uint64_t)lo);
-#endif
         }
     };
     auto issue_aux = [&](int t) __attribute__((always_inline)) {
@@ -174,32 +157,18 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf2_kernel(const Scan
     // publication: this wave's pieces of tile t have landed -> one more arrival at the tile's counter
     const uint32_t arr_lds = ring_lds + PF2_OFF_CNT;
     auto publish = [&](int t) __attribute__((always_inline)) {
-#ifdef MS_PF2_PUBLISH_C
-        if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t *)(arrived + (t & (PF2_ARR - 1))), 1u, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
         // (one lane adds, under an EXEC mask set by scalar moves -- the code is wave-uniform here, EXEC is all ones: five
         //  instructions; hipcc's `if (lane == 0) atomic add` is fifteen, with two branches, in every stage)
         const uint32_t a_ = arr_lds + 4u * (uint32_t)(t & (PF2_ARR - 1));
         uint32_t pub_a, pub_one;
         asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, 1\n\ts_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1"
                      : "=&v"(pub_a), "=&v"(pub_one) : "s"(a_) : "memory");
-#endif
     };
     // every wave's pieces of tile t have landed: its counter has been raised NW times per use of it
     uint32_t seen = 0;                                  // the counter of the tile the next stage needs, as last read
     auto read_arrived = [&](int t) __attribute__((always_inline)) { seen = arrived[t & (PF2_ARR - 1)]; };
     auto wait_arrived = [&](int t) __attribute__((always_inline)) {
         const uint32_t need = (uint32_t)NW * (uint32_t)(t / PF2_ARR + 1);
-#ifdef MS_PF2_WAIT_C
-        uint32_t spins = 0;
-#pragma unroll 1
-        for (; (uint32_t)__builtin_amdgcn_readfirstlane(seen) < need && spins < (1u << 24); ++spins) {
-            __builtin_amdgcn_s_sleep(1);
-            read_arrived(t);
-        }
-        if (__builtin_expect(spins >= (1u << 24), 0)) __builtin_trap();      // never a silent hang
-#else
         // ONE asm statement: the snapshot is good -> four instructions and a short forward branch (hipcc's loop around the same
         // test is nineteen instructions with a taken branch even when there is nothing to wait for).  Bounded: never a silent hang.
         uint32_t sv_, spins_, av_;
@@ -226,10 +195,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf2_kernel(const Scan
                      "s_trap 2\n\t"                        // never a silent hang
                      "2:"
                      : "=&s"(sv_), "=&s"(spins_), "+v"(seen), "=&v"(av_) : "s"(t), "s"(need), "s"(arr_lds) : "memory", "scc");
-#endif
         asm volatile("" ::: "memory");          // (the tile's fragment reads stay behind the wait)
     };
-    (void)arr_lds;
     // ---- prologue: the first D tiles are requested before anything else (HBM latency overlaps the query set-up)
 #pragma unroll
     for (int t = 0; t < PF2_D; ++t)
@@ -445,12 +412,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf2_kernel(const Scan
                 "v_max3_f32 %0, %0, %10, %11\n\tv_max3_f32 %0, %0, %12, %13\n\tv_max3_f32 %0, %0, %14, %15\n\tv_max_f32 %0, %0, %16"
                 : "=&v"(mx) : "v"(pv[0]), "v"(pv[1]), "v"(pv[2]), "v"(pv[3]), "v"(pv[4]), "v"(pv[5]), "v"(pv[6]), "v"(pv[7]), "v"(pv[8]), "v"(pv[9]),
                   "v"(pv[10]), "v"(pv[11]), "v"(pv[12]), "v"(pv[13]), "v"(pv[14]), "v"(pv[15]));
-#ifdef MS_PF2_NOVISIT
-            asm volatile("" ::"v"(mx));
-            if (false) {
-#else
             if (__builtin_expect(__ballot(mx > st.tau) != 0 || neg_tau, 0)) {
-#endif
                 PF2_T0();
                 if (t > 0) visit(pv, t - 1, false);
                 if (mask_on) neg_tau = __ballot(st.tau < 0.0f) != 0;
@@ -479,15 +441,15 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf2_kernel(const Scan
             for (int f = 0; f < 16; ++f) fr[f] = src[64 * f];
         }
         read_arrived(1);
-        // Shared bound, every MS_HIST_PERIOD tiles: the 16 bucket counters of this wave's 32 queries are fetched by LDS-DMA (sc1:
+        // Shared bound, every HIST_PERIOD tiles: the 16 bucket counters of this wave's 32 queries are fetched by LDS-DMA (sc1:
         // past this CU's L1) -- no destination register, nothing the compiler has to wait for; the counted vector-memory waits of
         // the stages cover them -- and read back one iteration later: the highest bucket edge with at least k rows at or above
         // it (counted by all waves so far) bounds the k-th best.  Waves w and w + 4 share staging area w & 3: wave w fetches in
         // phase 2 w of a period and reads in phase 2 w + 2, so the two are half a period (>= 8 tiles) apart, and no wave runs
         // more than max(W - 1, R - D) tiles ahead of another.
-        const int fetch_phase = 2 * wave, read_phase = (2 * wave + 2) & (MS_HIST_PERIOD - 1);
+        const int fetch_phase = 2 * wave, read_phase = (2 * wave + 2) & (HIST_PERIOD - 1);
         auto hist_step = [&](int t) __attribute__((always_inline)) {
-            const int phase = t & (MS_HIST_PERIOD - 1);
+            const int phase = t & (HIST_PERIOD - 1);
             if (phase == fetch_phase) {
                 const uint64_t hb = (uint64_t)(uintptr_t)p.hist + (uint64_t)qtile * 2048u;
                 const uint32_t hb_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)hb);

@@ -35,48 +35,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr uint32_t MS_PF16_MAGIC = 0x3631464du;       // "MF16"
 #define MS_PF_ERR_F16X2 5.5e-4f
 #define MS_PF_ERR_F16X1 1.05e-3f
-#ifndef MS_PF16_SHADOW
-#define MS_PF16_SHADOW 0
-#endif
-// Ablation builds (WRONG results; tools/pf_scan_only.py): what does each part of the steady stage cost?
-//   MS_PF16_ABL_NOMFMA  no matrix instructions (the accumulators are kept alive through an empty asm)
-//   MS_PF16_ABL_NOFILTER  no lane maxima / threshold compare (the rare path is never taken)
-//   MS_PF16_ABL_NODMA  no LDS-DMA pieces after the prologue (stale tiles; publication and waits unchanged)
-#ifdef MS_PF16_HALF_LDS          // (diagnostic build, WRONG results: only half of a tile's fragments are read from LDS -- what do the LDS reads cost?)
-#define MS_PF16_SECOND_READ(B)
-#else
-#define MS_PF16_SECOND_READ(B) fr[2 * (B) + 1] = src[64 * (2 * (B) + 1)];
-#endif
-// Round 6 (MS_PF16_DYNPRIO, default on): the wave that finds its next tile complete on arrival -- the one the workgroup is waiting for, e.g.
-// after a visit of the rare path -- takes the higher issue priority for its next chain, a wave that has to wait the lower one: -2 to -2.5 % on
-// long streams in two interleaved same-box passes (16M x 1024: 3.48 -> 3.40 ms; 4M x 256: 0.252 -> 0.246 ms), C2 unchanged
-// (profiles/r06_pf16_dynprio_ab.log)
-#ifndef MS_PF16_DYNPRIO
-#define MS_PF16_DYNPRIO 1
-#endif
-#ifndef MS_PF16_ILV
-#define MS_PF16_ILV 0
-#endif
-#if MS_PF16_DYNPRIO
-#define MS_PF16_PRIO_BEHIND "s_setprio 2\n\t"
-#define MS_PF16_PRIO_AHEAD "s_setprio 0\n\t"
-#else
-#define MS_PF16_PRIO_BEHIND
-#define MS_PF16_PRIO_AHEAD
-#endif
-#ifndef MS_PF16_HIST_PERIOD
-#define MS_PF16_HIST_PERIOD MS_HIST_PERIOD     // tiles between two looks at the shared bound in this kernel (8 needs MS_PF2_HIST_AREAS = 8)
-#endif
-#ifndef MS_PF16_LEAD_LOAD
-#define MS_PF16_LEAD_LOAD 0        // 1: eight-wave workgroups, only waves 0-3 issue the LDS-DMA pieces -- measured: no change on five shapes
-                                   // (profiles/r06_pf16_lead_load_ab.log); 0 (default): every wave two pieces, as in rounds 4-5
-#endif
-#ifndef MS_PF16_VISIT2
-#define MS_PF16_VISIT2 1           // the rare path as straight-line predicated code (0: the ballot-and-select-tree form of rounds 4-5)
-#endif
-#ifndef MS_PF16_GROUPED
-#define MS_PF16_GROUPED 1          // the rare path looks for candidates group of four registers by group (0: sixteen ballots, rounds 4-5)
-#endif
 
 // The approximate score of (row, query): one accumulator chain per half tile, k blocks in order, per block rowh.qh [, rowh.ql].
 // The sample pass and the full pass run exactly this sequence (the sample's bound must hold bit for bit).
@@ -85,11 +43,7 @@ template <int KL, int NW, bool SAMPLE, bool MASK, int NQP>
 __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const ScanParams p) {
     static_assert(NQP == 1 || NQP == 2, "query parts");
     static_assert(NW == 4 || NW == 8, "one or two waves per SIMD");
-    // Round 6 experiment (MS_PF16_LEAD_LOAD=1, not the default: no gain): with eight waves only the FOUR OLDER ones (w < 4: they win the matrix pipe, run ahead and wait ~500 cycles per
-    // tile for the others) issue the LDS-DMA pieces, four each; the younger four -- the critical path -- issue none and only vouch for
-    // their progress at the arrival counters.  The requests also leave earlier (the leaders are up to two tiles ahead).
-    constexpr int LW = (NW == 8 && MS_PF16_LEAD_LOAD) ? 4 : NW;      // waves that load
-    constexpr int PPW = 16 / LW;                       // LDS-DMA pieces of a tile per loading wave
+    constexpr int PPW = 16 / NW;                       // LDS-DMA pieces of a tile per wave
 #ifdef MS_STAMP
     const unsigned long long tl_entry = __builtin_amdgcn_s_memrealtime();
     unsigned long long tl_setup = 0, tl_first = 0, tl_loop = 0;
@@ -130,14 +84,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
     const uint64_t img0 = (uint64_t)(uintptr_t)p.pf_image + (uint64_t)(row_begin >> 6) * 16384u + (uint32_t)(1024 * PPW) * (uint32_t)wave;
     // (cosine mode: EVERY wave issues one more piece per tile so that the counted waits are the same for all of them; only wave 0's
     //  -- the rows' lengths -- is read)
-#ifdef MS_PF16_ABL_NODMA
-    bool abl_prologue_done = false;
-#endif
     uint64_t it_sb = 0;            // base address and LDS destination of the tile being issued (uniform)
     uint32_t it_dst = 0;
-    const bool loads = (LW == NW) ? true : (wave < LW);      // (uniform; a constant when every wave loads: no branch around the pieces)
     auto issue_prep = [&](int t) __attribute__((always_inline)) {
-        if (!loads) return;
         const uint64_t b = img0 + (uint64_t)t * 16384u;
         const uint32_t b_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
         const uint32_t b_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
@@ -147,23 +96,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
     auto issue_piece = [&](auto i_c) __attribute__((always_inline)) {
         constexpr int I = decltype(i_c)::value;
         if constexpr (I < PPW) {
-            if (!loads) return;
             // (uniform values that live across branches: say so again, or the "s" operands of the asm may be handed vector registers)
             const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane(it_dst);
             const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)it_sb), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(it_sb >> 32));
-#ifdef MS_PF16_ABL_NODMA
-            if (abl_prologue_done) { asm volatile("" :: "s"(d), "s"(lo), "s"(hi)); return; }
-#endif
-#ifdef MS_PF2_NT
-            ms_glds_s16_nt<1024 * I>(d + 1024 * I, voff, ((uint64_t)hi << 32) | (uint64_t)lo);
-#else
             ms_glds_s16<1024 * I>(d + 1024 * I, voff, ((uint64_t)hi << 32) | (uint64_t)lo);
-#endif
         }
     };
     auto issue_aux = [&](int t) __attribute__((always_inline)) {
         if constexpr (MASK) {
-            if (!loads) return;
             int64_t row = row_begin + (int64_t)t * 64 + lane;        // (64 rows per tile: one length per lane)
             if (row >= p.n) row = p.n - 1;
             const uint32_t dst = wave == 0 ? ring_lds + PF2_OFF_AUX + (uint32_t)(t % PF2_AUXR) * 256u
@@ -177,54 +117,40 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         issue_piece(std::integral_constant<int, 2>{}); issue_piece(std::integral_constant<int, 3>{});
         issue_aux(t);
     };
-    // own pieces of every tile but the youngest N issued have landed (a wave that loads nothing has nothing to wait for)
+    // own pieces of every tile but the youngest N issued have landed
     auto wait_own = [&](auto n_c) __attribute__((always_inline)) {
         constexpr int N = decltype(n_c)::value;
-        if (loads) ms_pf2_vmcnt<(PPW + (MASK ? 1 : 0)) * N>();
-    };
-    // ... the same in front of the shared bound's staging area (its two pieces are this wave's own whether it loads tiles or not)
-    auto wait_own_hist = [&]() __attribute__((always_inline)) {
-        if (loads) ms_pf2_vmcnt<(PPW + (MASK ? 1 : 0)) * 2>(); else ms_pf2_vmcnt<0>();
+        ms_pf2_vmcnt<(PPW + (MASK ? 1 : 0)) * N>();
     };
     // publication: this wave's pieces of tile t have landed -> one more arrival at the tile's counter
     const uint32_t arr_lds = ring_lds + PF2_OFF_CNT;
     auto publish = [&](int t) __attribute__((always_inline)) {
-#ifdef MS_PF2_PUBLISH_C
-        if (lane == 0) __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t *)(arrived + (t & (PF2_ARR - 1))), 1u, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
         // (one lane adds, under an EXEC mask set by scalar moves -- the code is wave-uniform here, EXEC is all ones: five
         //  instructions; hipcc's `if (lane == 0) atomic add` is fifteen, with two branches, in every stage)
         const uint32_t a_ = arr_lds + 4u * (uint32_t)(t & (PF2_ARR - 1));
         uint32_t pub_a, pub_one;
         asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, 1\n\ts_mov_b64 exec, 1\n\tds_add_u32 %0, %1\n\ts_mov_b64 exec, -1"
                      : "=&v"(pub_a), "=&v"(pub_one) : "s"(a_) : "memory");
-#endif
     };
     // every wave's pieces of tile t have landed: its counter has been raised NW times per use of it
     uint32_t seen = 0;                                  // the counter of the tile the next stage needs, as last read
     auto read_arrived = [&](int t) __attribute__((always_inline)) { seen = arrived[t & (PF2_ARR - 1)]; };
     auto wait_arrived = [&](int t) __attribute__((always_inline)) {
         const uint32_t need = (uint32_t)NW * (uint32_t)(t / PF2_ARR + 1);
-#ifdef MS_PF2_WAIT_C
-        uint32_t spins = 0;
-#pragma unroll 1
-        for (; (uint32_t)__builtin_amdgcn_readfirstlane(seen) < need && spins < (1u << 24); ++spins) {
-            __builtin_amdgcn_s_sleep(1);
-            read_arrived(t);
-        }
-        if (__builtin_expect(spins >= (1u << 24), 0)) __builtin_trap();      // never a silent hang
-#else
         // ONE asm statement: the snapshot is good -> four instructions and a short forward branch (hipcc's loop around the same
         // test is nineteen instructions with a taken branch even when there is nothing to wait for).  Bounded: never a silent hang.
+        // Round 6: the wave that finds its next tile complete on arrival -- the one the workgroup is waiting for, e.g. after a visit of
+        // the rare path -- takes the higher issue priority for its next chain, a wave that has to wait the lower one: -2 to -2.5 % on
+        // long streams in two interleaved same-box passes (16M x 1024: 3.48 -> 3.40 ms; 4M x 256: 0.252 -> 0.246 ms), C2 unchanged
+        // (profiles/r06_pf16_dynprio_ab.log)
         uint32_t sv_, spins_, av_;
         static_assert(PF2_ARR == 16, "the mask below");
         asm volatile("s_waitcnt lgkmcnt(0)\n\t"
                      "v_readfirstlane_b32 %0, %2\n\t"
                      "s_cmp_ge_u32 %0, %5\n\t"
-                     MS_PF16_PRIO_BEHIND                   // (nothing to wait for: this wave is the one the others wait for)
+                     "s_setprio 2\n\t"                     // (nothing to wait for: this wave is the one the others wait for)
                      "s_cbranch_scc1 2f\n\t"
-                     MS_PF16_PRIO_AHEAD                    // (it has to wait: it is ahead)
+                     "s_setprio 0\n\t"                     // (it has to wait: it is ahead)
                      "s_and_b32 %0, %4, 15\n\t"           // (the counter's address: only needed on this path)
                      "s_lshl_b32 %0, %0, 2\n\t"
                      "s_add_u32 %0, %0, %6\n\t"
@@ -243,10 +169,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
                      "s_trap 2\n\t"                        // never a silent hang
                      "2:"
                      : "=&s"(sv_), "=&s"(spins_), "+v"(seen), "=&v"(av_) : "s"(t), "s"(need), "s"(arr_lds) : "memory", "scc");
-#endif
         asm volatile("" ::: "memory");          // (the tile's fragment reads stay behind the wait)
     };
-    (void)arr_lds;
     // ---- set-up loads: ALL requested here, in front of the prologue's LDS-DMA pieces, and consumed behind them, so that they share ONE
     //      round trip with the first tiles (measured neutral against requesting them behind the prologue: 54.9 / 110.9 us against 54.4 /
     //      111.7 at 140k / 1M rows -- the ~7.5 us between a wave's entry and its first stage at C2 are not these loads)
@@ -275,9 +199,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
     for (int t = 0; t < PF2_D; ++t)
         if (t < ntl) issue_tile(t);
 
-#ifdef MS_PF16_ABL_NODMA
-    abl_prologue_done = true;
-#endif
     if (!has_q) {
         // loading-only wave (the workgroup's last query tiles are padding): issue, publish, keep pace with the readers
         // (it waits for the same arrivals as a wave that computes: that is what keeps it from overwriting a slot in use)
@@ -360,13 +281,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float c = fminf(fmaxf(x[j], -65504.0f), 65504.0f);
-#ifdef MS_PF16_ABL_BF16
-                const _Float16 hi16 = __builtin_bit_cast(_Float16, (__bf16)c);
-#elif defined(MS_PF16_ABL_F16R8)
-                const _Float16 hi16 = (_Float16)(float)(__bf16)c;
-#else
                 const _Float16 hi16 = (_Float16)c;                     // round to nearest even
-#endif
                 qh[b][j] = hi16;
                 if constexpr (NQP == 2) ql[b][j] = (_Float16)(c - (float)hi16);
             }
@@ -446,7 +361,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
     // Round 6: the rare path as straight-line predicated code.  The form below it (rounds 4-5) finds the candidate registers with a chain of
     // ballots, then loops over them with a uniform index and a 15-select tree: ~130 instructions of which most are scalar-after-vector
     // dependencies (v_cmp -> s_cmp -> s_cselect -> s_or ...), 1,400 cycles per visit -- and a visit of ANY of the eight waves delays the whole
-    // workgroup (no wave has spare speed to catch up: the diagnostic build without visits runs 19-27 % faster, profiles/r06_pf16_diag_*).
+    // workgroup (no wave has spare speed to catch up).
     // Here: group maxima (8 instructions), one test per group of four registers, and per register of a hit group `v_cmp; s_and_saveexec;
     // s_cbranch_execz` around a body that runs for the passing lanes only (count in the histogram, append, mark the register taken).  A lane
     // whose buffer is full does not append: it raises `ovf`, the buffers are flushed into the lists and the tile is visited again -- the
@@ -454,7 +369,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
     // Measured (profiles/r06_pf16_visit2_ab.log): k = 10 shapes unchanged (the visits that actually run cost 8 % of the C2 launch and 2 % of
     // a long stream: MS_PF_DEBUG=1), k = 32 (16-entry lists) 6 % faster.  The cosine + mask instantiations with the query split hi / lo or with
     // 16-entry lists spill 330-1,250 bytes per lane around this form and keep the older one.
-    constexpr bool VISIT2 = MS_PF16_VISIT2 && !(MASK && (NQP == 2 || KL >= 16));
+    constexpr bool VISIT2 = !(MASK && (NQP == 2 || KL >= 16));
     auto visit_v2 = [&](f32x16 &sc_v, int t, int half, bool check_rows) __attribute__((always_inline)) {
         if (mask_on) apply_mask(sc_v, t, half);
         const uint32_t sub_row0 = (uint32_t)(row_begin + (int64_t)t * 64) + (uint32_t)(32 * half + 4 * h);
@@ -497,7 +412,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         if (mask_on) apply_mask(sc_v, t, half);
         const uint32_t sub_row0 = (uint32_t)(row_begin + (int64_t)t * 64) + (uint32_t)(32 * half + 4 * h);
         uint32_t regs = 0;                                   // registers holding a candidate of some lane (uniform)
-#if MS_PF16_GROUPED
         // Round 6: sixteen ballots (~64 instructions, candidate or not) were half of a typical visit.  The lane's maximum over each GROUP of
         // four registers (rows 8 g + 4 h + 0..3: eight instructions), one ballot per group, and the four ballots of a group only where its
         // maximum passes: 8 + 12 + 16 instructions for the usual visit (one register of one group).
@@ -515,10 +429,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
             MS_PF16_GROUP(0, g0) MS_PF16_GROUP(1, g1) MS_PF16_GROUP(2, g2) MS_PF16_GROUP(3, g3)
 #undef MS_PF16_GROUP
         }
-#else
-#pragma unroll
-        for (int i = 0; i < 16; ++i) regs |= (__ballot(sc_v[i] > tau_s) != 0 ? 1u : 0u) << i;
-#endif
 #pragma unroll 1
         while (regs != 0u) {
             const int i = __builtin_ctz(regs);
@@ -560,12 +470,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
 #define PF2_ACC(V)
 #endif
     // ---- pipeline.  Stage t: the fragments of tile t are in `fr`; each is replaced by tile t + 1's right behind the matrix
-    //      instructions that used it; the chain runs into `out`; the scores of tile t - 1 (`pv`) are filtered in its shadow, the
-    //      rare path follows.  Two stages per loop iteration swap (pv, out): no register copies.
+    //      instructions that used it; the scores of tile t - 1 in `acc` are filtered first (the rare path follows), then the
+    //      chain of tile t overwrites them.
     f32x4 fr[16];
-    f32x16 accA0, accA1, accB0, accB1;         // (A, B) = (previous, current) tile; 0 / 1 = rows 0-31 / 32-63 of it
+    f32x16 acc0, acc1;                         // rows 0-31 / 32-63 of the tile
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { accA0[i] = -INFINITY; accA1[i] = -INFINITY; accB0[i] = -INFINITY; accB1[i] = -INFINITY; }
+    for (int i = 0; i < 16; ++i) { acc0[i] = -INFINITY; acc1[i] = -INFINITY; }
 
     auto frag_base = [&](int t) __attribute__((always_inline)) -> const f32x4 * {
         return reinterpret_cast<const f32x4 *>(smem + (size_t)(t % PF2_R) * 16384 + 16 * lane);
@@ -585,22 +495,12 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
                 "v_max3_f32 %0, %0, %10, %11\n\tv_max3_f32 %0, %0, %12, %13\n\tv_max3_f32 %0, %0, %14, %15\n\tv_max_f32 %0, %0, %16"               \
                 : "=&v"(M) : "v"(PV[0]), "v"(PV[1]), "v"(PV[2]), "v"(PV[3]), "v"(PV[4]), "v"(PV[5]), "v"(PV[6]), "v"(PV[7]), "v"(PV[8]), "v"(PV[9]), \
                   "v"(PV[10]), "v"(PV[11]), "v"(PV[12]), "v"(PV[13]), "v"(PV[14]), "v"(PV[15]))
-#ifdef MS_PF16_ABL_NOFILTER
-            asm volatile("" : "+v"(pv0), "+v"(pv1));
-            mx = -INFINITY; mx1 = -INFINITY;
-#else
             MS_PF16_MAX(mx, pv0);
             MS_PF16_MAX(mx1, pv1);
-#endif
 #undef MS_PF16_MAX
             // (each half tile is visited only if one of ITS scores passes: a visit costs ~900 cycles per half, candidate or not)
             const bool hit0 = __ballot(mx > tau_s) != 0, hit1 = __ballot(mx1 > tau_s) != 0;
-#ifdef MS_PF2_NOVISIT
-            asm volatile("" ::"v"(mx));
-            if (false) {
-#else
             if (__builtin_expect(hit0 || hit1 || neg_tau, 0)) {
-#endif
                 PF2_T0();
                 if (t > 0) {
                     if (hit0 || neg_tau) visit(pv0, t - 1, 0, false);
@@ -615,8 +515,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         }
     };
     // STEADY: 2 <= t and t + D < ntl -- every condition of the head and the tail of a stream is known (the generic form is the
-    // same code with the tests in)
-    auto stage = [&](auto steady_c, int t, f32x16 &pv0, f32x16 &pv1, f32x16 &out0, f32x16 &out1) __attribute__((always_inline)) {
+    // same code with the tests in).  (out0, out1) hold the scores of tile t - 1 on entry and those of tile t on exit.
+    auto stage = [&](auto steady_c, int t, f32x16 &out0, f32x16 &out1) __attribute__((always_inline)) {
         constexpr bool STEADY = decltype(steady_c)::value;
         // tile t is in registers (and the snapshot of the counters taken during the last chain): its slot is free
         PF2_T0();
@@ -624,10 +524,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         PF2_ACC(sp_lgkm)
         if (STEADY || t + 1 < ntl) wait_arrived(t + 1);                   // tile t + 1 has landed from every wave
         PF2_ACC(sp_sync)
-        // MS_PF16_SHADOW == 0: ONE pair of accumulators -- the scores of tile t - 1 are filtered here, before the chain of tile t
-        // overwrites them (the partner wave of the SIMD has the matrix pipe meanwhile); == 1: in the shadow of the chain, from a
-        // second pair (32 more registers: the 10- and 16-entry lists then spill with the query split hi / lo)
-        if constexpr (!MS_PF16_SHADOW) filter(t, pv0, pv1);
+        // ONE pair of accumulators: the scores of tile t - 1 are filtered here, before the chain of tile t overwrites them (the
+        // partner wave of the SIMD has the matrix pipe meanwhile; a second pair, filtered in the shadow of the chain, costs 32 more
+        // registers: the 10- and 16-entry lists then spill with the query split hi / lo)
+        filter(t, out0, out1);
 #pragma unroll
         for (int i = 0; i < 16; ++i) { out0[i] = 0.0f; out1[i] = 0.0f; }
         // The chain, k block by k block; behind each block's matrix instructions the two fragment reads of tile t + 1 that replace
@@ -635,67 +535,19 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         // 8 cycles next to a matrix instruction and 60-185 in a burst.
         const f32x4 *src = frag_base(t + 1);
         const bool issuing = STEADY || t + PF2_D < ntl;         // (uniform)
-#ifdef MS_PF16_ABL_NOMFMA
-#define MS_PF16_MFMA(ACC, F, Q) asm volatile("" : "+v"(ACC) : "v"(F), "v"(Q));
-#elif defined(MS_PF16_ABL_BF16)
-// (diagnostic build, WRONG results: the same bits through the bf16 form of the instruction -- does the narrower multiplier hold a higher clock?)
-#define MS_PF16_MFMA(ACC, F, Q) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, F), __builtin_bit_cast(bf16x8, Q), ACC, 0, 0, 0);
-#else
-#define MS_PF16_MFMA(ACC, F, Q) ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(F, Q, ACC, 0, 0, 0);
-#endif
 #define MS_PF2_BLOCK(B)                                                                                               \
         {                                                                                                             \
             const f16x8 f0 = __builtin_bit_cast(f16x8, fr[2 * (B)]), f1 = __builtin_bit_cast(f16x8, fr[2 * (B) + 1]);   \
-            MS_PF16_MFMA(out0, f0, qh[B])                                                                             \
-            MS_PF16_MFMA(out1, f1, qh[B])                                                                             \
+            out0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f0, qh[B], out0, 0, 0, 0);                                  \
+            out1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1, qh[B], out1, 0, 0, 0);                                  \
             if constexpr (NQP == 2) {                                                                                 \
                 out0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f0, ql[B], out0, 0, 0, 0);                              \
                 out1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1, ql[B], out1, 0, 0, 0);                              \
             }                                                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                        \
             fr[2 * (B)] = src[64 * (2 * (B))];                                                                        \
-            MS_PF16_SECOND_READ(B)                                                                                    \
+            fr[2 * (B) + 1] = src[64 * (2 * (B) + 1)];                                                                \
         }
-#if MS_PF16_ILV
-        // (MS_PF16_ILV: matrix instruction, the read that replaces ITS operand, matrix instruction, read -- each read issues in the 32-cycle
-        //  shadow of the instruction in front of it, and only "everything else" follows the second one)
-#undef MS_PF2_BLOCK
-#define MS_PF2_BLOCK(B)                                                                                               \
-        {                                                                                                             \
-            const f16x8 f0 = __builtin_bit_cast(f16x8, fr[2 * (B)]), f1 = __builtin_bit_cast(f16x8, fr[2 * (B) + 1]);   \
-            MS_PF16_MFMA(out0, f0, qh[B])                                                                             \
-            if constexpr (NQP == 2) out0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f0, ql[B], out0, 0, 0, 0);          \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            fr[2 * (B)] = src[64 * (2 * (B))];                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            MS_PF16_MFMA(out1, f1, qh[B])                                                                             \
-            if constexpr (NQP == 2) out1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(f1, ql[B], out1, 0, 0, 0);          \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            MS_PF16_SECOND_READ(B)                                                                                    \
-        }
-#endif
-#ifdef MS_PF16_ABL_1616
-        // (diagnostic build, WRONG results: the same operands through 32 v_mfma_f32_16x16x32_f16 on eight 4-register accumulators -- what would the
-        //  other matrix shape's instruction mix run at?)
-        typedef float f32x4_ __attribute__((ext_vector_type(4)));
-        f32x4_ oa[4], ob[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { oa[i] = f32x4_{0.0f, 0.0f, 0.0f, 0.0f}; ob[i] = f32x4_{0.0f, 0.0f, 0.0f, 0.0f}; }
-#undef MS_PF2_BLOCK
-#define MS_PF2_BLOCK(B)                                                                                               \
-        {                                                                                                             \
-            const f16x8 f0 = __builtin_bit_cast(f16x8, fr[2 * (B)]), f1 = __builtin_bit_cast(f16x8, fr[2 * (B) + 1]);   \
-            oa[(B) & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0, qh[B], oa[(B) & 3], 0, 0, 0);                    \
-            ob[(B) & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f1, qh[B], ob[(B) & 3], 0, 0, 0);                    \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            fr[2 * (B)] = src[64 * (2 * (B))];                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            oa[((B) + 2) & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f0, qh[((B) + 1) & 7], oa[((B) + 2) & 3], 0, 0, 0); \
-            ob[((B) + 2) & 3] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f1, qh[((B) + 1) & 7], ob[((B) + 2) & 3], 0, 0, 0); \
-            __builtin_amdgcn_sched_barrier(0);                                                                        \
-            MS_PF16_SECOND_READ(B)                                                                                    \
-        }
-#endif
         MS_PF2_BLOCK(0)
         __builtin_amdgcn_sched_barrier(0);
         MS_PF2_BLOCK(1)
@@ -723,15 +575,10 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         __builtin_amdgcn_sched_barrier(0);
         MS_PF2_BLOCK(7)
 #undef MS_PF2_BLOCK
-#ifdef MS_PF16_ABL_1616
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { out0[i] = oa[i >> 2][i & 3]; out1[i] = ob[i >> 2][i & 3]; }
-#endif
 #ifdef MS_STAMP
         asm volatile("s_nop 0" : "+v"(out0), "+v"(out1));
 #endif
         PF2_ACC(sp_chain)
-        if constexpr (MS_PF16_SHADOW) filter(t, pv0, pv1);
     };
 
 #ifdef MS_STAMP
@@ -755,20 +602,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
             for (int f = 0; f < 16; ++f) fr[f] = src[64 * f];
         }
         read_arrived(1);
-        // Shared bound, every MS_HIST_PERIOD tiles: the 16 bucket counters of this wave's 32 queries are fetched by LDS-DMA (sc1:
+        // Shared bound, every HIST_PERIOD tiles: the 16 bucket counters of this wave's 32 queries are fetched by LDS-DMA (sc1:
         // past this CU's L1) -- no destination register, nothing the compiler has to wait for; the counted vector-memory waits of
         // the stages cover them -- and read back one iteration later: the highest bucket edge with at least k rows at or above
         // it (counted by all waves so far) bounds the k-th best.  Waves w and w + 4 share staging area w & 3: wave w fetches in
         // phase 2 w of a period and reads in phase 2 w + 2, so the two are half a period (>= 8 tiles) apart, and no wave runs
         // more than max(W - 1, R - D) tiles ahead of another.
-        // (round 6, MS_PF2_HIST_AREAS = 8: every wave has a staging area of its own and the period may be 8 tiles -- the first look at the
-        //  shared bound comes at tile 2..8 instead of 2..16 and every 8 tiles from then on: C2's 61-tile streams see it 7 times, not 3-4)
-        constexpr int HP = MS_PF16_HIST_PERIOD;
-        static_assert(HP == 16 || (HP == 8 && (PF2_HIST_AREAS == 8 || NW == 4)), "a shared staging area needs half a period of 16 tiles between its two users");
-        const int fetch_phase = (HP == 16 ? 2 * wave : 2 * (wave & 3)), read_phase = (fetch_phase + 2) & (HP - 1);
-        const int hist_area = wave & (PF2_HIST_AREAS - 1);
+        const int fetch_phase = 2 * wave, read_phase = (2 * wave + 2) & (HIST_PERIOD - 1);
+        const int hist_area = wave & 3;
         auto hist_step = [&](int t) __attribute__((always_inline)) {
-            const int phase = t & (HP - 1);
+            const int phase = t & (HIST_PERIOD - 1);
             if (phase == fetch_phase) {
                 const uint64_t hb = (uint64_t)(uintptr_t)p.hist + (uint64_t)qtile * 2048u;
                 const uint32_t hb_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)hb);
@@ -781,7 +624,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
             if (phase == read_phase && t >= 2) {
                 PF2_T0();
                 // the two stages since then issued two tiles' pieces behind the counters' (near the end of a stream: fewer -- drain)
-                if (t - 1 + PF2_D < ntl) wait_own_hist(); else ms_pf2_vmcnt<0>();
+                if (t - 1 + PF2_D < ntl) wait_own(std::integral_constant<int, 2>{}); else ms_pf2_vmcnt<0>();
                 const ms_u32x4 *hp = reinterpret_cast<const ms_u32x4 *>(smem + PF2_OFF_HIST + hist_area * 2048 + r * 64);
                 const ms_u32x4 c0 = hp[0], c1 = hp[1], c2 = hp[2], c3 = hp[3];
                 const uint32_t c[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
@@ -801,54 +644,20 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
             }
         };
         int t = 0;
-#if !MS_PF16_SHADOW
-        // ONE stage per iteration (round 6: two per iteration doubled every copy of the rare path in the instruction cache; the register swap
-        // that needed pairs belongs to the shadow form): the body of a stream -- every stage issues (t + D < ntl) -- ...
+        // ONE stage per iteration (round 6: two per iteration doubled every copy of the rare path in the instruction cache): the body
+        // of a stream -- every stage issues (t + D < ntl) -- ...
         for (; t + PF2_D < ntl; ++t) {
             if ((t & 1) == 0) {
                 if (pace_on) pace(t);
                 if (hist_on) hist_step(t);
             }
-            stage(std::true_type{}, t, accA0, accA1, accA0, accA1);
+            stage(std::true_type{}, t, acc0, acc1);
         }
         // ... and its last D tiles, with the tests in
         for (; t < ntl; ++t) {
             if ((t & 1) == 0 && hist_on) hist_step(t);
-            stage(std::false_type{}, t, accA0, accA1, accA0, accA1);
+            stage(std::false_type{}, t, acc0, acc1);
         }
-#else
-        // the body of a stream: every stage issues (t + 1 + D < ntl), two tiles per iteration ...
-        for (; t + 1 + PF2_D < ntl; t += 2) {
-            if (pace_on) pace(t);
-            if (hist_on) hist_step(t);
-            if constexpr (MS_PF16_SHADOW) {
-                stage(std::true_type{}, t, accA0, accA1, accB0, accB1);             // accA = scores of tile t - 1 (or -inf), accB <- tile t
-                stage(std::true_type{}, t + 1, accB0, accB1, accA0, accA1);         // accB = tile t, accA <- tile t + 1
-            } else {
-                stage(std::true_type{}, t, accA0, accA1, accA0, accA1);
-                stage(std::true_type{}, t + 1, accA0, accA1, accA0, accA1);
-            }
-        }
-        // ... and its last D + 1 tiles, with the tests in
-        for (; t + 1 < ntl; t += 2) {
-            if (hist_on) hist_step(t);
-            if constexpr (MS_PF16_SHADOW) {
-                stage(std::false_type{}, t, accA0, accA1, accB0, accB1);
-                stage(std::false_type{}, t + 1, accB0, accB1, accA0, accA1);
-            } else {
-                stage(std::false_type{}, t, accA0, accA1, accA0, accA1);
-                stage(std::false_type{}, t + 1, accA0, accA1, accA0, accA1);
-            }
-        }
-        if (t < ntl) {
-            if constexpr (MS_PF16_SHADOW) {
-                stage(std::false_type{}, t, accA0, accA1, accB0, accB1);
-                accA0 = accB0; accA1 = accB1;
-            } else {
-                stage(std::false_type{}, t, accA0, accA1, accA0, accA1);
-            }
-        }
-#endif
 #ifdef MS_STAMP
         if (!SAMPLE && lane == 0 && p.stamps != nullptr && (size_t)bid * 64 + 64 <= 4 * 4 * 65536) {
             unsigned long long *o = p.stamps + ((size_t)bid * 8 + wave) * 8;
@@ -862,14 +671,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
 #endif
         if (pace_on && wave == 0 && lane == 0)        // this workgroup is through: nobody waits for it any more
             __hip_atomic_store(p.prog + (size_t)stream * 16 + qg, (p.prog_epoch << 24) | 0xFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // drain: the last tile's scores (accA), rows past row_end rejected
+        // drain: the last tile's scores, rows past row_end rejected
         if (SAMPLE) {
-            if (mask_on) { apply_mask(accA0, ntl - 1, 0); apply_mask(accA1, ntl - 1, 1); }
+            if (mask_on) { apply_mask(acc0, ntl - 1, 0); apply_mask(acc1, ntl - 1, 1); }
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { smax = (accA0[i] > smax) ? accA0[i] : smax; smax = (accA1[i] > smax) ? accA1[i] : smax; }
+            for (int i = 0; i < 16; ++i) { smax = (acc0[i] > smax) ? acc0[i] : smax; smax = (acc1[i] > smax) ? acc1[i] : smax; }
         } else {
-            visit(accA0, ntl - 1, 0, true);
-            visit(accA1, ntl - 1, 1, true);
+            visit(acc0, ntl - 1, 0, true);
+            visit(acc1, ntl - 1, 1, true);
             flush();
         }
     }
@@ -891,9 +700,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ms_scan_pf16_kernel(const Sca
         }
         return;
     }
-#ifdef MS_PF16_NOWRITE          // (diagnostic build: what do the list stores cost?)
-    if (p.k > 0) return;
-#endif
 #pragma unroll
     for (int j = 0; j < (SAMPLE ? 1 : KL); ++j) {
         const int rank = h * KL + j;

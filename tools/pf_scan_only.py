@@ -1,5 +1,6 @@
-"""The prefilter's scan launch alone (prepare once, then the scan in a loop under HIP events; no merge, no re-scoring): for diagnostic
-builds whose results are not meant to be right (MS_LIB_OVERRIDE=.../build/nowrite/...).
+"""The prefilter's scan launch alone (prepare once, then the scan in a loop under HIP events; no merge, no re-scoring), on the default
+build or one loaded with MS_LIB_OVERRIDE=.../build/<name>/... .  The diagnostic builds it was written for (-DMS_PF16_NOWRITE and the
+other ablations, whose results are not meant to be right) were removed from the sources: build them from commit 56b0d0e.
 usage: [MS_PF_FORMAT=f16x2|f16x1|bf16x3] python tools/pf_scan_only.py n,nq,k [...]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """Foldclass search benchmark: queries/sec of the exact 128-d cosine top-k scan on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (N > 1 without a launcher: starts its own ranks as children)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N > 1 without a launcher: starts its own ranks as children)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs, checks the
+last step's lists against a brute force (the recall the metric quotes) and prints the line, whose roofline is the scan launch's
+events of the timed region.  Every block below that takes runs of its own -- prefiltered, two_in_flight, the live traffic passes,
+cpu_baseline, the extras, and at N > 1 the exchange's own time and the weak-scaling reference -- runs only with `--full`.
 
 N = 1 (default): BASELINE.json configs[1] (C2) -- brute-force cosine top-10 over a 1M x 128 float32
 synthetic database, batch = 256 queries.  A step is one pass of the hot path over one query batch:
@@ -57,7 +62,7 @@ goes to bench_full.json beside this file and to stderr.  The blocks:
   embed         (N = 1) C3's embed half: 1000 TED-length domains -> embeds/s and fraction of the fp32 MFMA
                 peak, and the C5 query (AF-Q96PD2, 3 domains) latency;
   c3_end_to_end (N = 1) C3 as ONE timed unit: embed 1000 domains, then search their embeddings against the 500k-row database.
-`--no-extras` skips everything from hbm_regime down, `--no-cpu-baseline` the CPU legs.
+With `--full`, `--no-extras` skips everything from hbm_regime down, `--no-cpu-baseline` the CPU legs.
 """
 import argparse
 import json
@@ -170,9 +175,9 @@ def attach_committed_traffic(roof, pmc_name):
 
 def measure_traffic_live(kernels, log, timeout_s=150):
     """HBM bytes per launch of the top-level step's scan kernel, measured NOW: two `rocprofv3 --kernel-trace --pmc <counter>` CHILD passes
-    (FETCH_SIZE; WRITE_SIZE: counters that cannot share a pass) of this very script on the same workload (`--no-extras --no-cpu-baseline
-    --no-live-traffic --steps 5 --warmup 3`), corrected as MI355X_MICROARCH.md prescribes (KiB units; gfx950 reports half of a wide /
-    LDS-DMA read stream: reads = 2 x FETCH_SIZE x 1024).  The children are started as fresh processes (nothing is exec'd in this one) under
+    (FETCH_SIZE; WRITE_SIZE: counters that cannot share a pass) of this very script on the same workload (`--full --no-extras
+    --no-cpu-baseline --no-live-traffic --no-pipelined --steps 5 --warmup 3`: the fp32 and the prefiltered step), with the gfx950
+    corrections (KiB units; gfx950 reports half of a wide / LDS-DMA read stream: reads = 2 x FETCH_SIZE x 1024).  The children are started as fresh processes (nothing is exec'd in this one) under
     a hard time limit and killed as a group past it.  -> (bytes per launch, launches counted) or None (no rocprofv3, a pass failed or
     timed out: the caller keeps the figure of the committed profile and says so).  `kernels`: {key: kernel-name substring}; -> {key:
     (bytes per launch, launches counted)} for the kernels both passes saw."""
@@ -189,7 +194,7 @@ def measure_traffic_live(kernels, log, timeout_s=150):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="ms_pmc_")
         cmd = [rp, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "pmc", "--", os.path.realpath(sys.executable), os.path.abspath(__file__),
-               "--no-extras", "--no-cpu-baseline", "--no-live-traffic", "--no-pipelined", "--steps", "5", "--warmup", "3"]
+               "--full", "--no-extras", "--no-cpu-baseline", "--no-live-traffic", "--no-pipelined", "--steps", "5", "--warmup", "3"]
         env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         env["TMPDIR"] = tempfile.gettempdir()
         proc = subprocess.Popen(cmd, cwd=tempfile.gettempdir(), env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
@@ -1091,10 +1096,13 @@ def main():
     ap.add_argument("--shape", choices=("c2", "c4"), default=None,
                     help="N=1 only: c2 (default) = 1M rows x 256 queries; c4 = ONE rank's share of C4 (45,625,000 rows x 4096 queries) as the top-level "
                          "step -- the like-for-like first point of the weak-scaling curve that --gpus N>1 measures")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every block that takes runs of its own (prefiltered, two_in_flight, live traffic, cpu_baseline, the extras; "
+                         "at N > 1 the exchange's own time and the weak-scaling reference); the --no-* options below pick among them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip hbm_regime / c4_shard / embed")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic with rocprofv3 child passes (N = 1, default C2 shape, extras on: two passes of ~25 s); the "
+                    help="do not measure roofline.traffic with rocprofv3 child passes (--full, N = 1, default C2 shape, extras on: two passes of ~25 s); the "
                          "figure of the committed profile is used instead")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the `two_in_flight` block (N = 1: the same steps with two query batches in flight on two HIP streams)")
     ap.add_argument("--no-streamed", action="store_true", help="skip the `streamed` block (host memmap searched block by block over PCIe: writes up to 23.4 GB to /dev/shm)")
@@ -1179,7 +1187,7 @@ def main():
     lo, hi = sharded.shard_bounds(n_total, world, rank)
     log = (lambda m: print("[bench] " + m, file=sys.stderr, flush=True)) if rank == 0 else (lambda m: None)
 
-    use_pf = not args.no_prefilter
+    use_pf = args.full and not args.no_prefilter
     bench = SearchBench(torch, dist, ops, syn, sharded, dev, rank, world, n_total, lo, hi, nq, k, exchange=args.exercise_exchange)
     steps = args.steps
     elapsed, scan_ms, res = bench.run(steps, args.warmup)        # the fp32 scan: the reference's arithmetic, data-independent
@@ -1188,8 +1196,8 @@ def main():
         log("outputs of the last timed step: %s" % os.path.abspath(args.dump_outputs))
     checks = bench.check(res, sharded)
     # N > 1 (weak scaling): the same ranks' shard scans without the exchange -- the curve's one-rank reference from the same build
-    local_ref = bench.local_rate(max(2, min(steps, 10))) if world > 1 else None
-    if collective is not None:
+    local_ref = bench.local_rate(max(2, min(steps, 10))) if world > 1 and args.full else None
+    if collective is not None and args.full:
         collective["exchange_us"] = time_exchange(bench)
 
     def pf_block(b_fp32, res_fp32, steps_, warm_, prep_s=0.3, pmc=None):
@@ -1216,7 +1224,7 @@ def main():
     pf_main = pf_block(bench, res, max(20, min(steps, 200)), 10, pmc="r06_pf_c2_pmc.json" if c2 else None) if use_pf else None
 
     two = None
-    if world == 1 and nq > 64 and not args.no_pipelined:
+    if args.full and world == 1 and nq > 64 and not args.no_pipelined:
         # the same steps with two batches in flight (informative: see pipelined_rate)
         ms2, r2 = pipelined_rate(bench, max(20, min(steps, 200)))
         same = all(bool(torch.equal(r_[1], res[1]) and torch.equal(r_[0].view(torch.int32), res[0].view(torch.int32))) for r_ in r2)
@@ -1279,7 +1287,7 @@ def main():
         line = None
 
     extras_sd, extras_coords = None, None
-    if world == 1 and not args.no_extras and args.shape != "c4":
+    if args.full and world == 1 and not args.no_extras and args.shape != "c4":
         db_keep, q_keep = bench.db, bench.q_raw
         del bench.ws
         mk = lambda rows, nq_, **kw_: SearchBench(torch, dist, ops, syn, sharded, dev, 0, 1, rows, 0, rows, nq_, k, **kw_)
@@ -1396,7 +1404,7 @@ def main():
             line["streamed"] = streamed_bench(torch, ops, syn, dev, k, log)
         bench.db, bench.q_raw = db_keep, q_keep
 
-    if rank == 0 and world == 1 and c2 and not args.no_live_traffic and (not args.no_extras or os.environ.get("MS_BENCH_LIVE_TRAFFIC") == "1"):
+    if args.full and rank == 0 and world == 1 and c2 and not args.no_live_traffic and (not args.no_extras or os.environ.get("MS_BENCH_LIVE_TRAFFIC") == "1"):
         # roofline.traffic of the top-level kernel, measured in THIS run (the GPU is idle now: every timed region is over)
         # (the prefiltered step's image scan is in the same child runs: both kernels' counters from the same two passes)
         live = measure_traffic_live({"top": "ms_scan_loader_kernel<5, 0, false, false>", "pf": "ms_scan_pf16_kernel<10, 8, false, false,"}, log)
@@ -1411,7 +1419,7 @@ def main():
             roof_["traffic_source"] = roof_["traffic_from"]
             log("live traffic of %s: %.1f MB = %.3f x the algorithmic bytes" % (roof_["kernel"], live[key][0] / 1e6, live[key][0] / roof_["algorithmic_bytes_per_launch"]))
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             q_unit = bench.q_raw / bench.q_raw.norm(dim=1, keepdim=True)
             line["cpu_baseline"] = cpu_baseline(bench.db, q_unit, k, n_total, extras_sd, extras_coords)
         line["notes"] = {

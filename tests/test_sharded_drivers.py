@@ -392,7 +392,7 @@ def test_bench_gpus_2_self_launches_and_is_exact(tmp_path):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MS_BENCH_SAME_DEVICE="1", MS_BENCH_BACKEND="gloo")
-    r = _run_bench(["--gpus", "2", "--rows", "600000", "--nq", "96", "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], env, 400)
+    r = _run_bench(["--gpus", "2", "--rows", "600000", "--nq", "96", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"], env, 400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _bench_line(r.stdout)
     assert line["n_gpus"] == 2 and line["config"]["rows_per_gpu"] == 300000
@@ -412,8 +412,8 @@ def test_bench_gpus_4_self_launches_on_tiny_shards(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MS_BENCH_SAME_DEVICE="1", MS_BENCH_BACKEND="gloo")
     world = GPU_SHARING_RANKS
-    r = _run_bench(["--gpus", str(world), "--rows", str(100000 * world), "--nq", "96", "--steps", "2", "--warmup", "1", "--no-extras",
-                    "--no-cpu-baseline"], env, 400)
+    r = _run_bench(["--gpus", str(world), "--rows", str(100000 * world), "--nq", "96", "--steps", "2", "--warmup", "1", "--full",
+                    "--no-extras", "--no-cpu-baseline"], env, 400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _bench_line(r.stdout)
     assert line["n_gpus"] == world and line["config"]["rows_per_gpu"] == 100000
@@ -426,11 +426,11 @@ def test_bench_gpus_4_self_launches_on_tiny_shards(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_default_line_is_parseable_and_carries_roofline_and_cpu_baseline(tmp_path):
-    """`python bench.py` as the driver runs it at N = 1 (C2; extras skipped here for time): the last stdout line is under 4 KB and
+    """`python bench.py --full` at N = 1 (C2; extras skipped here for time): the last stdout line is under 4 KB and
     carries the contract's keys, `roofline` and `cpu_baseline`; the full document went to bench_full.json."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = _run_bench(["--steps", "20", "--warmup", "5", "--no-extras"], env, 600)
+    r = _run_bench(["--steps", "20", "--warmup", "5", "--full", "--no-extras"], env, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1            # ONE stdout line
     line = _bench_line(r.stdout)
@@ -446,11 +446,30 @@ def test_bench_default_line_is_parseable_and_carries_roofline_and_cpu_baseline(t
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """`python bench.py` without --full: the headline line (contract keys, the recall the metric quotes, the roofline of the timed
+    region's scan launches with the committed profile's traffic) and none of the blocks that take runs of their own."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], env, 300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert len([l for l in r.stdout.splitlines() if l.strip()]) == 1
+    line = _bench_line(r.stdout)
+    assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["config"]["workload"].startswith("C2:")
+    assert line["metric"].startswith("queries/sec, exact 128-d cosine top-10 (recall@10 vs brute force = ") and line["recall_at_k"] == 1.0
+    assert line["unit"] == "queries/s" and line["higher_is_better"] is True and line["value"] == pytest.approx(256e3 / line["ms_per_step"], rel=1e-4)
+    assert line["roofline"]["kernel_ms"] < line["ms_per_step"] and not line["roofline"]["traffic_from"].startswith("measured in this run")
+    for key in ("prefiltered", "cpu_baseline", "two_in_flight", "more", "weak_scaling_ref_q_per_s", "vs_ref"):
+        assert key not in line, key
+    for what in ("prefiltered:", "two batches in flight", "clustered:", "hbm_regime", "live traffic"):
+        assert "[bench] " + what not in r.stderr, what
+
+
+@pytest.mark.gpu
 def test_bench_shape_c4_is_the_one_rank_point_of_the_weak_scaling_curve(tmp_path):
     """`python bench.py --gpus 1 --shape c4` (rows per GPU cut down here): the top-level step is one rank's share of C4."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MS_BENCH_ROWS_PER_GPU"] = "2000000"
-    r = _run_bench(["--shape", "c4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env, 600)
+    r = _run_bench(["--shape", "c4", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], env, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _bench_line(r.stdout)
     assert line["config"]["workload"].startswith("C4 shape, ONE rank") and line["config"]["queries_per_step"] == 4096
@@ -491,7 +510,7 @@ def test_bench_measures_the_top_level_traffic_itself(tmp_path):
         pytest.skip("no rocprofv3 on this box")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MS_BENCH_LIVE_TRAFFIC"] = "1"
-    r = _run_bench(["--steps", "10", "--warmup", "3", "--no-extras", "--no-cpu-baseline"], env, 600)
+    r = _run_bench(["--steps", "10", "--warmup", "3", "--full", "--no-extras", "--no-cpu-baseline"], env, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = _bench_line(r.stdout)
     assert line["roofline"]["traffic_from"].startswith("measured in this run"), line["roofline"]

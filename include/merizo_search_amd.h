@@ -239,6 +239,41 @@ int ms_egnn_embed(const void *prepared, const float *pe, int pe_len, const float
                   const int32_t *offsets_host, int nb, float *out, void *workspace, size_t workspace_bytes,
                   ms_stream_t stream);
 
+/* ------------------------------------------------------------------ TM-align -------- */
+
+/* Batched TM-align (Zhang & Skolnick, NAR 2005), the check the reference runs as one subprocess per hit
+ * (utils.py:75-109) and per query-domain x target-domain pair of the multi-domain search (dbsearch_fulllength.py:55-92).
+ * The routine sequence and constants of the public TMalign.cpp (the version is unpinned), fp64
+ * geometry, one wave per pair.  Backward compatible additions: ms_version() stays 210. */
+#define MS_TMALIGN_MAX_LEN 2000   /* longest chain accepted (createdb's parser cap) */
+#define MS_TM_FAST 1              /* flags: TM-align -fast */
+/* out_i[3*p + 2], the status of pair p */
+#define MS_TM_OK 0
+#define MS_TM_ERR_SHORT 1         /* a chain of <= 5 residues: TM-align refuses it */
+#define MS_TM_ERR_LONG 2          /* a chain longer than max_len1 / max_len2 (or MS_TMALIGN_MAX_LEN) */
+#define MS_TM_ERR_INDEX 3         /* a structure index outside [0, nstruct) */
+
+/* Bytes of scratch for npairs pairs whose chain 1 has <= max_len1 and chain 2 <= max_len2 residues (0: bad argument).
+ * Pairs share slots of the workspace when there are many long ones (at most 2 GiB of slots are asked for). */
+size_t ms_tmalign_workspace_bytes(int max_len1, int max_len2, int npairs);
+int ms_tmalign_max_len(void); /* MS_TMALIGN_MAX_LEN */
+
+/* TM-align pair p: chain 1 = structure pairs[2p] (the query), chain 2 = structure pairs[2p+1].
+ *   xyz      fp64 [total][3], the CA coordinates of nstruct structures packed back to back (the values TM-align would
+ *            parse from the %8.3f PDB text: the caller rounds them to 3 decimals);
+ *   seq      uint8 [total], the one-letter residue codes (Seq_ID counts equal bytes);
+ *   offsets  int64 [nstruct + 1], structure s = rows [offsets[s], offsets[s+1]);
+ *   pairs    int32 [npairs][2]: worked on in the order given, one wave per pair -- give them longest first (L1 * L2);
+ *   flags    MS_TM_FAST or 0;
+ * Outputs: out_f fp64 [npairs][3] = TM-score normalised by chain 1, by chain 2, RMSD of the n_ali8 pairs;
+ *          out_i int32 [npairs][3] = n_ali8 ("Aligned length": aligned pairs within score_d8), identical residues among
+ *          them, status (MS_TM_*; values 0 unless MS_TM_OK);
+ *          out_invmap int32 [npairs][max_len2] or NULL: the final alignment, chain-2 residue j -> chain-1 residue or -1.
+ * All arrays are device memory; max_len1 / max_len2 bound every chain of the batch (longer ones get MS_TM_ERR_LONG). */
+int ms_tmalign_batch(const double *xyz, const uint8_t *seq, const int64_t *offsets, int nstruct, const int32_t *pairs, int npairs,
+                     int max_len1, int max_len2, int flags, void *workspace, size_t workspace_bytes, double *out_f, int32_t *out_i,
+                     int32_t *out_invmap, ms_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,10 @@ _sz = ctypes.c_size_t
 ABI_VERSION = 210
 # prefilter image formats (include/merizo_search_amd.h)
 PF_BF16X3, PF_F16X2, PF_F16X1 = 0, 1, 2
+# TM-align (include/merizo_search_amd.h): flags and per-pair status
+TMALIGN_MAX_LEN = 2000     # MS_TMALIGN_MAX_LEN
+TM_FAST = 1
+TM_OK, TM_ERR_SHORT, TM_ERR_LONG, TM_ERR_INDEX = 0, 1, 2, 3
 
 # name -> (restype, argtypes); exactly the symbols include/merizo_search_amd.h declares
 SIGNATURES = {
@@ -75,6 +79,9 @@ SIGNATURES = {
     "ms_egnn_prepare_weights": (_int, [_vp, _vp, _vp]),
     "ms_egnn_workspace_bytes": (_sz, [_int, _i64, _i64]),
     "ms_egnn_embed": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _sz, _vp]),
+    "ms_tmalign_workspace_bytes": (_sz, [_int, _int, _int]),
+    "ms_tmalign_max_len": (_int, []),
+    "ms_tmalign_batch": (_int, [_vp, _vp, _vp, _int, _vp, _int, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
 

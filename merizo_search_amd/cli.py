@@ -62,7 +62,10 @@ def _add_search_flags(p: argparse.ArgumentParser, default_format: str) -> None:
                    help="If --multi_domain_search is used, specifies the multi-domain search mode. Currently only "
                         "'exhaustive_tmalign' is supported.")
     p.add_argument("--skip_tmalign", action="store_true", default=False,
-                   help="Embedding-only search (automatic when no TM-align binary is found).")
+                   help="Embedding-only search (automatic when no TM-align binary is found and --tmalign_backend is auto).")
+    p.add_argument("--tmalign_backend", type=str, default="auto", choices=["auto", "hip"],
+                   help="'auto': the TM-align binary ($MERIZO_TMALIGN) if one is found, else an embedding-only search. "
+                        "'hip': TM-align every hit on the GPU in one batch (needs a cuda device). --skip_tmalign wins over both.")
     p.add_argument("--weights", type=str, default=None, help="Path to FINAL_foldclass_model.pt.")
 
 
@@ -130,7 +133,11 @@ def _embedding_only_format(fields, skip):
 
 def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
     from .foldclass import tmalign as tm
-    skip = args.skip_tmalign or tm.find_tmalign() is None
+    if args.tmalign_backend == "hip" and not str(args.device).startswith("cuda"):
+        logging.error("--tmalign_backend hip runs TM-align on the GPU: it needs a cuda device, got -d %s." % args.device)
+        sys.exit(1)
+    hip = args.tmalign_backend == "hip"
+    skip = args.skip_tmalign or (not hip and tm.find_tmalign() is None)
     search_output = args.output + "_search.tsv"
     all_output = args.output + "_search_insignificant.tsv"
     for path in (search_output, all_output):
@@ -138,7 +145,7 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
             logging.warning(f"Search output file '{path}' already exists. Results will be overwritten!")
     multi_output = args.output + "_search_multi_dom.tsv"
     if args.multi_domain_search:
-        if tm.find_tmalign() is None:
+        if not hip and tm.find_tmalign() is None:
             logging.error("--multi_domain_search aligns every query domain with every candidate target domain and needs a "
                           "TM-align binary (set $MERIZO_TMALIGN).")
             sys.exit(1)
@@ -148,7 +155,7 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         inputs=inputs, db_name=args.db_name, tmp=tmp, device=args.device, topk=args.topk, fastmode=args.fastmode,
         threads=args.threads, mincos=args.mincos, mintm=args.mintm, mincov=args.mincov, inputs_are_ca=inputs_are_ca,
         pdb_chain=pdb_chain, search_batchsize=args.search_batchsize, search_type=args.search_metric,
-        skip_tmalign=skip, weights_path=args.weights)
+        skip_tmalign=skip, weights_path=args.weights, tmalign_backend=args.tmalign_backend)
     if sharded.rank_world()[0] != 0:
         return                                            # every rank searched its shard; rank 0 reports
     fields = _embedding_only_format(fields, skip)
@@ -164,7 +171,8 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         from .foldclass.results import write_all_dom_search_results
         mda = multi_domain_search(queries=inputs, search_results=results, db_name=args.db_name, tmp_root=tmp, device=args.device,
                                   fastmode=args.fastmode, threads=args.threads, mintm=args.mintm,
-                                  inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain)
+                                  inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain,
+                                  tmalign_backend=args.tmalign_backend)
         write_all_dom_search_results(mda, multi_output, args.output_headers)
 
 

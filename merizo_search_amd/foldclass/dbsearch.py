@@ -22,7 +22,9 @@ What differs, deliberately (DESIGN.md "host drivers"):
     scans only its `sharded.shard_bounds` rows, one all-gather + merge gives every rank the global
     top-k, and rank 0 alone assembles hit records (sharded.py; replaces index_cpu_to_all_gpus,
     dbsearch.py:228-230);
-  * TM-align is optional (tmalign.py): with no binary the search is embedding-only;
+  * TM-align is optional (tmalign.py): with no binary the search is embedding-only; with tmalign_backend='hip' every
+    (query, hit) pair of a call that passes mincos is aligned on the GPU in ONE batch (ms_tmalign.hip), then the
+    reference's per-hit logic runs unchanged on those results;
   * reference defects are not reproduced: a single --pdb_chain with several inputs is applied
     to every input (dbsearch.py:523-524 builds a list of lists; :296 raises IndexError); a
     faiss-layout search with zero hits returns empty lists instead of crashing (:390); the
@@ -242,6 +244,39 @@ class _Blob:
         self._fd.close()
 
 
+def _aligner_device(network, device):
+    engine = getattr(network, "engine", None)
+    return getattr(engine, "device", None) or device or "cuda"
+
+
+def _hip_tm_outputs(query_dicts, hits, fastmode, device):
+    """TM-align the (query number, target coords, target seq) triples of `hits` in one GPU batch -> list of dicts
+    (extract_tmalign_values' shape) or None where TM-align refuses the pair."""
+    return tm.align_many([(query_dicts[q]["coords"], query_dicts[q]["seq"], c, s) for q, c, s in hits], fast=fastmode,
+                         device=device)
+
+
+def _pt_hip_outputs(query_dicts, target_dict, tops, topk, mincos, fastmode, device):
+    """`.pt` path: {rank: tm output} per query for every rank of its top-k that passes mincos, all queries in one batch."""
+    keys, hits = [], []
+    for q, (scores, indices) in enumerate(tops):
+        for rank in range(min(topk, scores.shape[0])):
+            if scores[rank] >= mincos:
+                _name, coords, seq = target_dict["index"][int(indices[rank])][:3]
+                keys.append((q, rank))
+                hits.append((q, coords, seq))
+    outs = _hip_tm_outputs(query_dicts, hits, fastmode, device)
+    per_query = [dict() for _ in tops]
+    for (q, rank), out in zip(keys, outs):
+        per_query[q][rank] = out
+    return per_query
+
+
+def _refused(query_dict, target_name) -> None:
+    logger.warning("TM-align refuses %s x %s (a structure of <= 5 residues): hit dropped"
+                   % (_query_name(query_dict), os.path.basename(str(target_name))))
+
+
 def _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode, target_name=None, named=False):
     if named:
         qfn = write_pdb(tmp, query_dict["coords"], query_dict["seq"], name=os.path.basename(query_dict["name"]))
@@ -255,10 +290,11 @@ def _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode, target_n
 # ------------------------------------------------------------------ `.pt` driver -------
 def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: float, mincos: float, mintm: float,
              fastmode: bool, device=None, inputs_are_ca: bool = False, pdb_chain: str = "A", skip_tmalign: bool = False,
-             score_corrections=None, _embedding=None, _topk=None):
+             score_corrections=None, _embedding=None, _topk=None, tmalign_backend: str = "auto", _tm_outputs=None):
     """One query against a `.pt` database -> (results, all_results), dicts keyed by the hit's
     position in the top-k (dbsearch.py:84-200).  `_embedding` / `_topk` let run_dbsearch pass one
-    row of a batched embedding / batched scan instead of recomputing per query."""
+    row of a batched embedding / batched scan instead of recomputing per query; `_tm_outputs` ({rank: output}) the
+    GPU aligner's results of a batch run_dbsearch made for all queries (tmalign_backend='hip')."""
     query_dict = query if inputs_are_ca else read_pdb(pdbfile=query, pdb_chain=pdb_chain)
     engine = network.engine
     if _topk is None:
@@ -272,6 +308,9 @@ def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: flo
         query_dict["embedding"] = _embedding
         scores, indices = _topk
 
+    if tmalign_backend == "hip" and not skip_tmalign and _tm_outputs is None:
+        _tm_outputs = _pt_hip_outputs([query_dict], target_dict, [(scores, indices)], topk, mincos, fastmode,
+                                      _aligner_device(network, device))[0]
     meta = None
     if target_dict["mdfn"] is not None and target_dict["mifn"] is not None:
         meta = _Blob(target_dict["mifn"], target_dict["mdfn"])
@@ -288,7 +327,13 @@ def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: flo
             continue
         if not (score >= mincos):
             continue
-        tm_output = _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode)
+        if _tm_outputs is not None:
+            tm_output = _tm_outputs[rank]
+            if tm_output is None:
+                _refused(query_dict, target_name)
+                continue
+        else:
+            tm_output = _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode)
         max_tm = max(tm_output["qtm"], tm_output["ttm"])
         if tm_output["len_ali"] >= len(target_seq) * mincov:       # coverage filter, `.pt` path only (:165)
             if meta is not None:
@@ -307,7 +352,7 @@ def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: flo
 def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, mincov: float, mincos: float,
                    mintm: float, fastmode: bool, device=None, inputs_are_ca: bool = False,
                    search_batchsize: int = 262144, search_type: str = "IP", pdb_chain: str = "A",
-                   skip_tmalign: bool = False, score_corrections=None):
+                   skip_tmalign: bool = False, score_corrections=None, tmalign_backend: str = "auto"):
     """All queries against a faiss-layout database -> (results, all_results): one dict per query,
     keyed by a dense counter of retained hits (dbsearch.py:203-472).  No mincov length mask on this
     path (acknowledged TODO at dbsearch.py:307-310)."""
@@ -384,6 +429,10 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
 
     if not skip_tmalign:
         logger.info("TM-align top hits...")
+    hip_outputs = None
+    if not skip_tmalign and tmalign_backend == "hip":               # every hit of the call in one GPU batch
+        hip_outputs = _hip_tm_outputs(query_dicts, [(int(query_indices[h]), hit_coords[h], hit_seqs[h]) for h in range(n_hits)],
+                                      fastmode, _aligner_device(network, device))
     counts = [0] * nq
     n_tm_exclude = 0
     for h in range(n_hits):
@@ -394,7 +443,13 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
             results[qi][counts[qi]] = _hit(qd, hit_ids[h], hit_scores[h], t_len, None, hit_indices[h], hit_metadata[h])
             counts[qi] += 1
             continue
-        tm_output = _tmalign_pair(tmp, qd, hit_coords[h], hit_seqs[h], fastmode, target_name=hit_ids[h], named=True)
+        if hip_outputs is not None:
+            tm_output = hip_outputs[h]
+            if tm_output is None:
+                _refused(qd, hit_ids[h])
+                continue
+        else:
+            tm_output = _tmalign_pair(tmp, qd, hit_coords[h], hit_seqs[h], fastmode, target_name=hit_ids[h], named=True)
         rec = _hit(qd, hit_ids[h], hit_scores[h], t_len, tm_output, hit_indices[h], hit_metadata[h])
         if max(tm_output["qtm"], tm_output["ttm"]) >= mintm:
             results[qi][counts[qi]] = rec
@@ -427,9 +482,12 @@ def _resident_shard(target_dict: dict, engine, dbmm, lo: int, hi: int, nq: int, 
 def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bool, threads: int, mincos: float,
                  mintm: float, mincov: float, inputs_are_ca: bool = False, search_batchsize: int = 262144,
                  search_type: str = "IP", pdb_chain: Optional[str] = None, skip_tmalign: bool = False,
-                 network=None, weights_path: Optional[str] = None):
+                 network=None, weights_path: Optional[str] = None, tmalign_backend: str = "auto"):
     """Set up the encoder, open the database, search every input (dbsearch.py:475-551).
-    Returns (search_results, all_search_results): one dict rank -> hit per input, twice."""
+    Returns (search_results, all_search_results): one dict rank -> hit per input, twice.
+    tmalign_backend: 'auto' = the TM-align binary if one is found, else an embedding-only search; 'hip' = the GPU
+    aligner (needs a cuda device).  skip_tmalign wins over both."""
+    tm.check_backend(tmalign_backend, device)
     if len(inputs) == 0:
         logger.error("No inputs were provided!")
         sys.exit(1)
@@ -437,7 +495,7 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
         os.mkdir(tmp)
     if network is None:
         network, device = network_setup(threads=threads, device=device, weights_path=weights_path)
-    if not skip_tmalign and tm.find_tmalign() is None:
+    if not skip_tmalign and tmalign_backend == "auto" and tm.find_tmalign() is None:
         logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
                        "TM-align columns are unavailable")
         skip_tmalign = True
@@ -450,7 +508,7 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
         return dbsearch_faiss(queries=inputs, target_dict=target_db, tmp=tmp, network=network, topk=topk,
                               mincov=mincov, mincos=mincos, mintm=mintm, fastmode=fastmode, device=device,
                               inputs_are_ca=inputs_are_ca, search_batchsize=search_batchsize, search_type=search_type,
-                              pdb_chain=pdb_chain, skip_tmalign=skip_tmalign)
+                              pdb_chain=pdb_chain, skip_tmalign=skip_tmalign, tmalign_backend=tmalign_backend)
 
     query_dicts = _load_queries(inputs, inputs_are_ca, _chain_list(pdb_chain, len(inputs)))
     emb = sharded.embed_distributed(network, [qd["coords"] for qd in query_dicts])   # ragged launches, data-parallel over ranks
@@ -460,10 +518,15 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
     search_results, all_search_results = [], []
     if sharded.rank_world()[0] != 0:
         return [dict() for _ in query_dicts], [dict() for _ in query_dicts]      # rank 0 assembles the hit records
+    tm_outputs = [None] * len(query_dicts)
+    if not skip_tmalign and tmalign_backend == "hip":               # every (query, hit) pair of the call in one GPU batch
+        tm_outputs = _pt_hip_outputs(query_dicts, target_db, list(zip(top_s, top_i)), topk, mincos, fastmode,
+                                     _aligner_device(network, device))
     for row, qd in enumerate(query_dicts):
         res, all_res = dbsearch(query=qd, target_dict=target_db, tmp=tmp, network=network, topk=topk, mincov=mincov,
                                 mincos=mincos, mintm=mintm, fastmode=fastmode, device=device, inputs_are_ca=True,
-                                skip_tmalign=skip_tmalign, _embedding=emb[row:row + 1], _topk=(top_s[row], top_i[row]))
+                                skip_tmalign=skip_tmalign, _embedding=emb[row:row + 1], _topk=(top_s[row], top_i[row]),
+                                tmalign_backend=tmalign_backend, _tm_outputs=tm_outputs[row])
         search_results.append(res)
         all_search_results.append(all_res)
     return search_results, all_search_results

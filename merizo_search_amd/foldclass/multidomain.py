@@ -11,7 +11,8 @@ inputs are the hit dictionaries the (GPU) per-domain search produced, the work i
   4. per (query chain, target chain) sub-matrix, enumerate the one-to-one assignments of query
      domains to target domains and classify them 0-3 (:95-180).
 Step 3 needs a TM-align executable ($MERIZO_TMALIGN): without one the reference cannot run this
-mode either, and `multi_domain_search` raises.  Steps 1, 2 and 4 are plain functions, tested
+mode either, and `multi_domain_search` raises -- unless tmalign_backend='hip', which aligns the pairs of ALL query
+chains in one GPU batch (ms_tmalign.hip) from the coordinates in memory, without files or processes.  Steps 1, 2 and 4 are plain functions, tested
 against outputs of the reference's own functions (tests/golden/multidomain.json).
 """
 from __future__ import annotations
@@ -29,7 +30,7 @@ import numpy as np
 
 from . import dbutil
 from .pdbio import read_pdb, write_pdb
-from .tmalign import find_tmalign, run_tmalign
+from .tmalign import align_many, check_backend, find_tmalign, run_tmalign
 
 logger = logging.getLogger(__name__)
 
@@ -196,16 +197,18 @@ class _TargetStore:
 
 def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, device=None, fastmode: bool = False,
                         threads: int = -1, mintm: float = 0.5, inputs_from_easy_search: bool = False,
-                        mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None):
+                        mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto"):
     """The reference's multi_domain_search (:183-574): same arguments, same result tuples (feed
     them to results.write_all_dom_search_results).  `queries`: PDB file names (search) or domain
-    dicts with 'coords', 'seq', 'name' (easy-search)."""
+    dicts with 'coords', 'seq', 'name' (easy-search).  tmalign_backend: 'auto' = the TM-align binary (required),
+    'hip' = the GPU aligner on `device`."""
     if mode != "exhaustive_tmalign":
         raise ValueError("Unrecognised multi-domain search mode: " + mode)
+    check_backend(tmalign_backend, device)
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
         return None
-    if find_tmalign() is None:
+    if tmalign_backend == "auto" and find_tmalign() is None:
         raise FileNotFoundError("multi-domain search aligns every query domain with every candidate target domain: "
                                 "it needs a TM-align binary (set $MERIZO_TMALIGN)")
     if not inputs_from_easy_search:
@@ -218,6 +221,11 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
     hits = group_hits(names, query_chains, search_results)
 
     store = _TargetStore(db_name)
+    if tmalign_backend == "hip":
+        try:
+            return _multi_domain_hip(hits, structures, store, fastmode, mintm, device)
+        finally:
+            store.close()
     results = []
     try:
         for qc, domains in hits.items():
@@ -253,4 +261,51 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
             logger.info("Finished multi-domain search for query chain %s." % qc)
     finally:
         store.close()
+    return results
+
+
+def _chain_entries(qc: str, domains: dict, store: "_TargetStore"):
+    """The database entries of every hit chain with at least as many domains as query chain qc has (:346-394), or
+    None (with the reference's log line) when there is nothing to align."""
+    nqd = len(domains)
+    if nqd < 2:
+        logger.info("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+        return None
+    rows = set()
+    for per_domain in domains.values():
+        for hit in per_domain:
+            chain_rows = sibling_rows(hit["hi"], hit["hc"], store.n, store.name)
+            if len(chain_rows) >= nqd:
+                rows.update(chain_rows)
+    if not rows:
+        logger.info("Query chain %s: every hit chain has fewer domains than the query; try a larger -k." % qc)
+        return None
+    return [store.entry(r) for r in sorted(rows)]
+
+
+def _multi_domain_hip(hits, structures, store, fastmode: bool, mintm: float, device) -> list:
+    """Step 3 on the GPU: every query-domain x target-domain pair of every query chain in ONE align_many batch, then the
+    per-chain matrices (max of the two TM-scores, below mintm -> 0, as tm_matrix) and steps 4 as on the binary path."""
+    plans = []
+    for qc, domains in hits.items():
+        entries = _chain_entries(qc, domains, store)
+        if entries is not None:
+            plans.append((qc, list(domains.keys()), entries))
+    items = [(structures[qd]["coords"], structures[qd]["seq"], e[1], e[2]) for _qc, qds, entries in plans for qd in qds
+             for e in entries]
+    logger.info("TM-align %d query-domain x target-domain pairs of %d query chains on the GPU" % (len(items), len(plans)))
+    outs = align_many(items, fast=fastmode, device=device or "cuda")
+    results, at = [], 0
+    for qc, qds, entries in plans:
+        n = len(qds) * len(entries)
+        scores = np.asarray([max(o["qtm"], o["ttm"]) if o is not None else 0.0 for o in outs[at:at + n]], dtype=np.float64)
+        at += n
+        scores = scores.reshape(len(qds), len(entries))
+        scores[scores < mintm] = 0.0
+        hit_chain = np.asarray([domid2chainid(e[0]) for e in entries])
+        info = [{"hd": e[0], "hc": hc, "hi": e[3], "hm": e[4]} for e, hc in zip(entries, hit_chain)]
+        for hc in np.unique(hit_chain):
+            cols = np.flatnonzero(hit_chain == hc)
+            results.extend(chain_mappings(scores[:, cols], qc, str(hc), qds, [info[c] for c in cols]))
+        logger.info("Finished multi-domain search for query chain %s." % qc)
     return results

@@ -1,10 +1,12 @@
-"""Optional TM-align verification hook (mirror of programs/Foldclass/utils.py:75-158).
+"""TM-align verification of hits (mirror of programs/Foldclass/utils.py:75-158).
 
-TM-align is a third-party CPU binary the reference shells out to for every hit; it is not
-shipped with the reference snapshot and is outside the accelerated path.  When a binary is
-available ($MERIZO_TMALIGN, or `tmalign` / `TMalign` on PATH, or next to this file) the
-drivers call it exactly like the reference; otherwise searches run embedding-only
-(skip_tmalign) and say so.
+Two backends:
+  * `auto` (the default): the third-party CPU binary the reference shells out to for every hit, when one is
+    available ($MERIZO_TMALIGN, or `tmalign` / `TMalign` on PATH, or next to this file) -- called exactly like the
+    reference; otherwise searches run embedding-only (skip_tmalign) and say so;
+  * `hip`: the batched GPU aligner (csrc/ms_tmalign.hip through ops.tmalign_batch): every pair of a call in one launch,
+    from the coordinates in memory, no files or processes.  `align_many` returns the dicts `extract_tmalign_values`
+    returns for the binary's output, its values rounded as the binary prints them.
 """
 from __future__ import annotations
 
@@ -13,7 +15,9 @@ import os
 import re
 import shutil
 import subprocess
-from typing import Optional
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
 
 logger = logging.getLogger(__name__)
 
@@ -67,3 +71,57 @@ def run_tmalign(structure1_path: str, structure2_path: str, options: Optional[st
             except OSError as exc:
                 logger.error(f"Error deleting structure files: {exc}")
     return extract_tmalign_values(proc.stdout)
+
+
+BACKENDS = ("auto", "hip")
+
+
+def check_backend(backend: str, device=None) -> None:
+    """`hip` needs a HIP device ('cuda' / 'cuda:N'); unknown names are refused."""
+    if backend not in BACKENDS:
+        raise ValueError("tmalign_backend must be one of %s, got %r" % (", ".join(BACKENDS), backend))
+    if backend == "hip" and device is not None and not str(device).startswith("cuda"):
+        raise ValueError("tmalign_backend 'hip' runs TM-align on the GPU: it needs a cuda device, got %r" % (device,))
+
+
+def pdb_values(coords) -> np.ndarray:
+    """The fp64 coordinates TM-align parses from the %8.3f PDB text the binary path writes: float("%.3f" % v)."""
+    c = np.asarray(coords, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    return np.asarray([float("%.3f" % v) for v in c.reshape(-1)], dtype=np.float64).reshape(-1, 3)
+
+
+def printed_values(qtm: float, ttm: float, rmsd: float, n_ali8: int, n_identical: int) -> dict:
+    """The dict extract_tmalign_values makes of the binary's output: TM-score %.5f, RMSD %.2f, Seq_ID %.3f."""
+    seq_id = n_identical / n_ali8 if n_ali8 > 0 else 0.0
+    return {"len_ali": int(n_ali8), "rmsd": float("%.2f" % rmsd), "seq_id": float("%.3f" % seq_id),
+            "qtm": float("%.5f" % qtm), "ttm": float("%.5f" % ttm)}
+
+
+def align_many(items: Sequence[Tuple], fast: bool = False, device="cuda") -> List[Optional[dict]]:
+    """TM-align every (coords1, seq1, coords2, seq2) of `items` on the GPU in one launch; chain 1 is the query.
+    Returns one extract_tmalign_values-shaped dict per item, or None where TM-align refuses the input (a chain of
+    <= 5 residues).  Structures that occur in several items (a query, a target domain) are uploaded once."""
+    if not items:
+        return []
+    from .. import ops
+    from .._lib import TM_OK
+
+    structs, seqs, index = [], [], {}
+
+    def slot(coords, seq):
+        key = (id(coords), seq)
+        if key not in index:
+            index[key] = len(structs)
+            structs.append(pdb_values(coords))
+            seqs.append(seq)
+        return index[key]
+
+    pairs = [(slot(c1, s1), slot(c2, s2)) for c1, s1, c2, s2 in items]
+    got = ops.tmalign_batch(structs, seqs, pairs, fast=fast, device=device)
+    out = []
+    for p in range(len(items)):
+        if got["status"][p] != TM_OK:
+            out.append(None)
+            continue
+        out.append(printed_values(got["qtm"][p], got["ttm"][p], got["rmsd"][p], got["n_ali8"][p], got["n_identical"][p]))
+    return out

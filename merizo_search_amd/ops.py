@@ -471,3 +471,94 @@ class EgnnEncoder:
                                     offsets.ctypes.data, nb, ptr(out), ptr(self._ws), self._ws.numel(), stream.cuda_stream),
                   "ms_egnn_embed")
         return out
+
+
+class _TmWorkspace:
+    """Scratch of ms_tmalign_batch on one device, grown on demand and kept across calls."""
+
+    def __init__(self):
+        self.buf = {}
+
+    def get(self, device, nbytes: int):
+        torch = _lib.require_gpu()
+        t = self.buf.get(device)
+        if t is None or t.numel() < nbytes:
+            t = self.buf[device] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return t
+
+
+_tm_ws = _TmWorkspace()
+
+
+def tmalign_batch(coords_list: Sequence[np.ndarray], seqs: Sequence[bytes], pairs, fast: bool = False, device="cuda",
+                  want_invmap: bool = False) -> dict:
+    """TM-align every pair (s1, s2) of `pairs` -- chain 1 = coords_list[s1] (the query), chain 2 = coords_list[s2] -- in ONE
+    launch of ms_tmalign_batch.  Coordinates are used as given, in fp64 (callers that stand in for the TM-align binary pass
+    the values of its %8.3f PDB text).  Returns numpy arrays indexed like `pairs`: qtm (TM-score normalised by chain 1),
+    ttm (by chain 2), rmsd, n_ali8, n_identical, status (_lib.TM_*), and invmap ([npairs, max chain-2 length], -1 = gap)
+    if asked.  A structure longer than _lib.TMALIGN_MAX_LEN raises; pairs with a chain of <= 5 residues get TM_ERR_SHORT."""
+    torch = _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise MerizoHipError("tmalign_batch runs on a HIP device only")
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ns, npairs = len(coords_list), pairs.shape[0]
+    out = {"qtm": np.zeros(npairs), "ttm": np.zeros(npairs), "rmsd": np.zeros(npairs), "n_ali8": np.zeros(npairs, np.int32),
+           "n_identical": np.zeros(npairs, np.int32), "status": np.zeros(npairs, np.int32)}
+    if npairs == 0:
+        if want_invmap:
+            out["invmap"] = np.zeros((0, 0), np.int32)
+        return out
+    if len(seqs) != ns:
+        raise MerizoHipError("tmalign_batch: one sequence per structure")
+    if pairs.min() < 0 or pairs.max() >= ns:
+        raise MerizoHipError("tmalign_batch: pair index outside the structure list")
+    lens = np.array([int(np.asarray(c).reshape(-1, 3).shape[0]) for c in coords_list], dtype=np.int64)
+    for c, s, n in zip(coords_list, seqs, lens):
+        if len(s) != n:
+            raise MerizoHipError("tmalign_batch: a sequence differs in length from its coordinates")
+    used = np.unique(pairs)
+    if lens[used].max() > _lib.TMALIGN_MAX_LEN:
+        raise MerizoHipError(f"tmalign_batch: a structure of {int(lens[used].max())} residues exceeds the aligner's limit of "
+                             f"{_lib.TMALIGN_MAX_LEN}")
+    offsets = np.zeros(ns + 1, np.int64)
+    offsets[1:] = np.cumsum(lens)
+    xyz = np.zeros((max(int(offsets[-1]), 1), 3), np.float64)
+    seq = np.zeros(max(int(offsets[-1]), 1), np.uint8)
+    for s in range(ns):
+        if lens[s]:
+            xyz[offsets[s]:offsets[s + 1]] = np.asarray(coords_list[s], dtype=np.float64).reshape(-1, 3)
+            b = seqs[s].encode() if isinstance(seqs[s], str) else bytes(seqs[s])
+            seq[offsets[s]:offsets[s + 1]] = np.frombuffer(b, dtype=np.uint8)
+    # one wave per pair, longest first (L1 * L2); the outputs are put back in the caller's order
+    work = lens[pairs[:, 0]] * lens[pairs[:, 1]]
+    order = np.argsort(-work, kind="stable")
+    sp = np.ascontiguousarray(pairs[order], dtype=np.int32)
+    max1 = max(int(lens[sp[:, 0]].max()), 1)
+    max2 = max(int(lens[sp[:, 1]].max()), 1)
+    need = int(lib.ms_tmalign_workspace_bytes(max1, max2, npairs))
+    if need == 0:
+        raise MerizoHipError("ms_tmalign_workspace_bytes rejected the batch")
+    with torch.cuda.device(dev):
+        d_xyz = torch.from_numpy(xyz).to(dev)
+        d_seq = torch.from_numpy(seq).to(dev)
+        d_off = torch.from_numpy(offsets).to(dev)
+        d_pairs = torch.from_numpy(sp).to(dev)
+        ws = _tm_ws.get(dev, need)
+        of = torch.empty((npairs, 3), dtype=torch.float64, device=dev)
+        oi = torch.empty((npairs, 3), dtype=torch.int32, device=dev)
+        inv = torch.full((npairs, max2), -1, dtype=torch.int32, device=dev) if want_invmap else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib.ms_tmalign_batch(ptr(d_xyz), ptr(d_seq), ptr(d_off), ns, ptr(d_pairs), npairs, max1, max2,
+                                   _lib.TM_FAST if fast else 0, ptr(ws), ws.numel(), ptr(of), ptr(oi), ptr(inv), stream),
+              "ms_tmalign_batch")
+        f, i = of.cpu().numpy(), oi.cpu().numpy()
+        inv_h = inv.cpu().numpy() if want_invmap else None
+    for name, col in (("qtm", f[:, 0]), ("ttm", f[:, 1]), ("rmsd", f[:, 2]), ("n_ali8", i[:, 0]), ("n_identical", i[:, 1]),
+                      ("status", i[:, 2])):
+        out[name][order] = col
+    if want_invmap:
+        out["invmap"] = np.empty_like(inv_h)
+        out["invmap"][order] = inv_h
+    return out

@@ -260,7 +260,8 @@ int ms_tmalign_max_len(void); /* MS_TMALIGN_MAX_LEN */
 
 /* TM-align pair p: chain 1 = structure pairs[2p] (the query), chain 2 = structure pairs[2p+1].
  *   xyz      fp64 [total][3], the CA coordinates of nstruct structures packed back to back (the values TM-align would
- *            parse from the %8.3f PDB text: the caller rounds them to 3 decimals);
+ *            parse from the %8.3f PDB text: the caller rounds them to 3 decimals).  Every coordinate must be finite: the
+ *            library does not check them, and NaN / inf give meaningless results;
  *   seq      uint8 [total], the one-letter residue codes (Seq_ID counts equal bytes);
  *   offsets  int64 [nstruct + 1], structure s = rows [offsets[s], offsets[s+1]);
  *   pairs    int32 [npairs][2]: worked on in the order given, one wave per pair -- give them longest first (L1 * L2);
@@ -268,7 +269,8 @@ int ms_tmalign_max_len(void); /* MS_TMALIGN_MAX_LEN */
  * Outputs: out_f fp64 [npairs][3] = TM-score normalised by chain 1, by chain 2, RMSD of the n_ali8 pairs;
  *          out_i int32 [npairs][3] = n_ali8 ("Aligned length": aligned pairs within score_d8), identical residues among
  *          them, status (MS_TM_*; values 0 unless MS_TM_OK);
- *          out_invmap int32 [npairs][max_len2] or NULL: the final alignment, chain-2 residue j -> chain-1 residue or -1.
+ *          out_invmap int32 [npairs][max_len2] or NULL: the final alignment, chain-2 residue j -> chain-1 residue or -1;
+ *          only entries j < the chain-2 length of pairs with status MS_TM_OK are written (fill it with -1 first).
  * All arrays are device memory; max_len1 / max_len2 bound every chain of the batch (longer ones get MS_TM_ERR_LONG). */
 int ms_tmalign_batch(const double *xyz, const uint8_t *seq, const int64_t *offsets, int nstruct, const int32_t *pairs, int npairs,
                      int max_len1, int max_len2, int flags, void *workspace, size_t workspace_bytes, double *out_f, int32_t *out_i,

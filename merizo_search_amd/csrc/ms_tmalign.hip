@@ -281,7 +281,7 @@ struct FragSel {
 
 // ---- scoring ----
 // TMalign.cpp score_fun8 over the aligned pairs [0, lali) rotated by (t,u): ordered list of pairs within d (relaxed by
-// 0.5 A while fewer than 3 survive) -> i_ali, score sum / Lnorm
+// 0.5 A while fewer than 3 survive and a pair outside the cut has a finite distance) -> i_ali, score sum / Lnorm
 __device__ int score_fun8(Ctx &c, int lali, const double t[3], const double u[3][3], double d, int *i_ali, double *score,
                           int score_sum_method, double Lnorm, double score_d8, double d0) {
     const double d02 = d0 * d0, score_d8_cut = score_d8 * score_d8;
@@ -298,19 +298,21 @@ __device__ int score_fun8(Ctx &c, int lali, const double t[3], const double u[3]
     for (;;) {
         n_cut = 0;
         p = 0.0;
+        bool out_finite = false;            // NaN / inf distances never enter the cut: relaxing for them would not end
         for (int base = 0; base < lali; base += 64) {
             const int k = base + c.lane;
             bool in = false;
             if (k < lali) {
                 const double di = c.dis[k];
                 in = di < d_tmp;
+                out_finite |= !in && isfinite(di);
                 p += (score_sum_method != 8 || di <= score_d8_cut) ? 1 / (1 + di / d02) : 0.0;
             }
             const unsigned long long m = __ballot(in);
             if (in) i_ali[n_cut + prefix_before(m, c.lane)] = k;
             n_cut += __popcll(m);
         }
-        if (n_cut < 3 && lali > 3) {
+        if (n_cut < 3 && lali > 3 && __any(out_finite)) {
             inc++;
             double dinc = d + inc * 0.5;
             d_tmp = dinc * dinc;
@@ -409,19 +411,26 @@ __device__ double detailed_search(Ctx &c, const int *y2x, double t[3], double u[
     return TMscore8_search(c, k, t, u, simplify_step, 8, c.d0_search, c.Lnorm, c.score_d8, c.d0);
 }
 
-// ordered list of the pairs [0, n_ali) with dis <= cut (relaxed by 0.5 while fewer than 3) -> c.ia; returns the count
+// ordered list of the pairs [0, n_ali) with dis <= cut (relaxed by 0.5 while fewer than 3 and a pair outside the cut has
+// a finite distance) -> c.ia; returns the count
 __device__ int select_within(Ctx &c, int n_ali, double cut) {
     int j;
     for (;;) {
         j = 0;
+        bool out_finite = false;
         for (int base = 0; base < n_ali; base += 64) {
             const int k = base + c.lane;
-            const bool in = k < n_ali && c.dis[k] <= cut;
+            bool in = false;
+            if (k < n_ali) {
+                const double di = c.dis[k];
+                in = di <= cut;
+                out_finite |= !in && isfinite(di);
+            }
             const unsigned long long m = __ballot(in);
             if (in) c.ia[j + prefix_before(m, c.lane)] = k;
             j += __popcll(m);
         }
-        if (j < 3 && n_ali > 3) cut += 0.5;
+        if (j < 3 && n_ali > 3 && __any(out_finite)) cut += 0.5;
         else break;
     }
     wave_sync();

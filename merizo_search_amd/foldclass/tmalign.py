@@ -100,9 +100,26 @@ def printed_values(qtm: float, ttm: float, rmsd: float, n_ali8: int, n_identical
 def align_many(items: Sequence[Tuple], fast: bool = False, device="cuda") -> List[Optional[dict]]:
     """TM-align every (coords1, seq1, coords2, seq2) of `items` on the GPU in one launch; chain 1 is the query.
     Returns one extract_tmalign_values-shaped dict per item, or None where TM-align refuses the input (a chain of
-    <= 5 residues).  Structures that occur in several items (a query, a target domain) are uploaded once."""
+    <= 5 residues) and where a chain has a NaN or infinite coordinate.  Structures that occur in several items (a query,
+    a target domain) are uploaded once."""
     if not items:
         return []
+    finite = {}
+
+    def is_finite(coords):
+        key = id(coords)
+        if key not in finite:
+            with np.errstate(over="ignore"):                  # pdb_values' fp32 cast turns |v| > 3.4e38 into inf
+                finite[key] = bool(np.isfinite(np.asarray(coords, dtype=np.float32)).all())
+        return finite[key]
+
+    keep = [p for p, (c1, _s1, c2, _s2) in enumerate(items) if is_finite(c1) and is_finite(c2)]
+    out: List[Optional[dict]] = [None] * len(items)
+    if len(keep) < len(items):
+        logger.warning("TM-align: %d of %d pairs have a chain with a non-finite coordinate; they are not aligned",
+                       len(items) - len(keep), len(items))
+    if not keep:
+        return out
     from .. import ops
     from .._lib import TM_OK
 
@@ -116,12 +133,9 @@ def align_many(items: Sequence[Tuple], fast: bool = False, device="cuda") -> Lis
             seqs.append(seq)
         return index[key]
 
-    pairs = [(slot(c1, s1), slot(c2, s2)) for c1, s1, c2, s2 in items]
+    pairs = [(slot(items[p][0], items[p][1]), slot(items[p][2], items[p][3])) for p in keep]
     got = ops.tmalign_batch(structs, seqs, pairs, fast=fast, device=device)
-    out = []
-    for p in range(len(items)):
-        if got["status"][p] != TM_OK:
-            out.append(None)
-            continue
-        out.append(printed_values(got["qtm"][p], got["ttm"][p], got["rmsd"][p], got["n_ali8"][p], got["n_identical"][p]))
+    for k, p in enumerate(keep):
+        if got["status"][k] == TM_OK:
+            out[p] = printed_values(got["qtm"][k], got["ttm"][k], got["rmsd"][k], got["n_ali8"][k], got["n_identical"][k])
     return out

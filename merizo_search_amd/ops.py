@@ -496,7 +496,11 @@ def tmalign_batch(coords_list: Sequence[np.ndarray], seqs: Sequence[bytes], pair
     launch of ms_tmalign_batch.  Coordinates are used as given, in fp64 (callers that stand in for the TM-align binary pass
     the values of its %8.3f PDB text).  Returns numpy arrays indexed like `pairs`: qtm (TM-score normalised by chain 1),
     ttm (by chain 2), rmsd, n_ali8, n_identical, status (_lib.TM_*), and invmap ([npairs, max chain-2 length], -1 = gap)
-    if asked.  A structure longer than _lib.TMALIGN_MAX_LEN raises; pairs with a chain of <= 5 residues get TM_ERR_SHORT."""
+    if asked.  A structure longer than _lib.TMALIGN_MAX_LEN or with a non-finite coordinate raises; pairs with a chain of
+    <= 5 residues get TM_ERR_SHORT."""
+    for s, c in enumerate(coords_list):                  # checked before the device: NaN / inf never reach the kernel
+        if not np.isfinite(np.asarray(c, dtype=np.float64)).all():
+            raise MerizoHipError(f"tmalign_batch: structure {s} has a non-finite coordinate")
     torch = _lib.require_gpu()
     lib = _lib.load()
     dev = torch.device(device)

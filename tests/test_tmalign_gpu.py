@@ -203,3 +203,199 @@ def test_multi_domain_search_runs_on_the_gpu_aligner_without_a_binary(tmp_path):
     run("easy-search", qpdb, str(tmp_path / "db"), str(tmp_path / "bin"), str(tmp_path / "tmp"), *args, binary=_stand_in(tmp_path))
     for suffix in ("_search.tsv", "_search_multi_dom.tsv"):
         assert open(str(tmp_path / "hip") + suffix, "rb").read() == open(str(tmp_path / "bin") + suffix, "rb").read(), suffix
+
+
+# ------------------------------------------------------------------ edges, long chains, slot reuse, C-level statuses ----
+def _restated(structs, pairs, fast):
+    """order=kernel results of every pair (None where TM-align refuses it), on at most 16 host threads (ctypes releases
+    the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    R.load()
+
+    def one(pair):
+        (_a, x, sx), (_b, y, sy) = structs[pair[0]], structs[pair[1]]
+        if min(len(x), len(y)) <= 5:
+            return None
+        return R.tm_align(x, y, sx, sy, fast=fast, order="kernel", quantize=False)
+    with ThreadPoolExecutor(max_workers=min(16, max(len(pairs), 1))) as ex:
+        return list(ex.map(one, pairs))
+
+
+def _assert_invariants(got, lens1, lens2):
+    """What holds for every result whatever the restatement says: ordered in-range alignments, counts, score ranges;
+    refused pairs: zero outputs and an all -1 row."""
+    for p, (xlen, ylen) in enumerate(zip(lens1, lens2)):
+        row = got["invmap"][p]
+        if got["status"][p] != 0:
+            assert got["qtm"][p] == 0 and got["ttm"][p] == 0 and got["rmsd"][p] == 0, p
+            assert got["n_ali8"][p] == 0 and got["n_identical"][p] == 0, p
+            assert (row == -1).all(), p
+            continue
+        assert (row[ylen:] == -1).all(), p
+        inv = row[:ylen]
+        ali = inv[inv >= 0]
+        assert (inv >= -1).all() and (ali < xlen).all() and (np.diff(ali) > 0).all(), p
+        assert 0 <= got["n_identical"][p] <= got["n_ali8"][p] <= len(ali), p
+        for key in ("qtm", "ttm"):
+            assert 0 <= got[key][p] <= 1 + 1e-12, (p, key, got[key][p])
+        assert got["rmsd"][p] >= 0, p
+
+
+def _assert_matches_restatement(label, structs, pairs, fast, got):
+    """Per pair: the same alignment, n_ali8 and n_identical as order=kernel, |dTM|, |dRMSD| <= 1e-9; prints how many are
+    bit-identical."""
+    lens = [len(s[1]) for s in structs]
+    _assert_invariants(got, [lens[i] for i, _j in pairs], [lens[j] for _i, j in pairs])
+    refs = _restated(structs, pairs, fast)
+    n_bits = n_ok = 0
+    for p, ((i, j), ref) in enumerate(zip(pairs, refs)):
+        what = "%s: %s x %s fast=%s" % (label, structs[i][0], structs[j][0], fast)
+        if ref is None:
+            assert got["status"][p] == 1, what
+            continue
+        assert got["status"][p] == 0, what
+        n_ok += 1
+        assert np.array_equal(got["invmap"][p, :lens[j]], ref["invmap"]), what
+        assert got["n_ali8"][p] == ref["n_ali8"] and got["n_identical"][p] == ref["n_identical"], what
+        for key in ("qtm", "ttm", "rmsd"):
+            assert abs(got[key][p] - ref[key]) <= 1e-9, (what, key, got[key][p], ref[key])
+        n_bits += all(np.float64(got[k][p]).tobytes() == np.float64(ref[k]).tobytes() for k in ("qtm", "ttm", "rmsd"))
+    print("\n%s (fast=%s): %d / %d aligned pairs bit-identical to order=kernel (%d pairs, %d refused)"
+          % (label, fast, n_bits, n_ok, len(pairs), len(pairs) - n_ok))
+
+
+@pytest.mark.parametrize("fast", [False, True])
+@pytest.mark.parametrize("which", ["boundary_set", "ties_set", "degenerate_set"])
+def test_kernel_matches_the_restatement_on_the_edge_sets(which, fast):
+    structs, pairs = getattr(tm_case, which)()
+    _assert_matches_restatement(which, structs, pairs, fast, _gpu_batch(structs, pairs, fast))
+
+
+@pytest.mark.parametrize("fast", [False, True])
+def test_kernel_matches_the_restatement_on_long_chains(fast):
+    structs, pairs = tm_case.long_set(fast)
+    _assert_matches_restatement("long_set", structs, pairs, fast, _gpu_batch(structs, pairs, fast))
+
+
+def _short_chains(n_structs=120, seed=9):
+    """Golden slices of 20-150 residues and noisy copies of them."""
+    rng = np.random.default_rng(seed)
+    structs = []
+    for k in range(n_structs // 2):
+        n = int(rng.integers(20, 151))
+        x, s = tm_case.golden_slice(n, int(rng.integers(0, 10 ** 6)))
+        structs += [("g%d_%d" % (k, n), x, s), ("g%d_%d_noisy" % (k, n), tm_case.noisy(x, 1.5, 900 + k), s)]
+    return structs
+
+
+def _slots(max1, max2, npairs):
+    from merizo_search_amd import _lib
+    lib = _lib.load()
+    one = int(lib.ms_tmalign_workspace_bytes(max1, max2, 1))
+    per = int(lib.ms_tmalign_workspace_bytes(max1, max2, 2)) - one
+    return (int(lib.ms_tmalign_workspace_bytes(max1, max2, npairs)) - one) // per + 1
+
+
+@pytest.mark.parametrize("fast", [False, True])
+def test_workgroups_that_run_several_pairs_match_the_restatement(fast):
+    structs = _short_chains()
+    rng = np.random.default_rng(11)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(0, len(structs), size=(2300, 2))]
+    lens = [len(s[1]) for s in structs]
+    assert _slots(max(lens[i] for i, _ in pairs), max(lens[j] for _, j in pairs), len(pairs)) < len(pairs)
+    _assert_matches_restatement("2300 short pairs", structs, pairs, fast, _gpu_batch(structs, pairs, fast))
+
+
+def _packed(structs):
+    import torch
+    lens = np.array([len(s[1]) for s in structs], np.int64)
+    offsets = np.zeros(len(structs) + 1, np.int64)
+    offsets[1:] = np.cumsum(lens)
+    xyz = np.concatenate([s[1] for s in structs]).astype(np.float64)
+    seq = np.frombuffer("".join(s[2] for s in structs).encode(), np.uint8).copy()
+    return [torch.from_numpy(a).to("cuda:0") for a in (xyz, seq, offsets)]
+
+
+def _raw_batch(structs, pairs, fast, max1, max2, ws):
+    """ms_tmalign_batch through ctypes, pairs in the order given (no host sort), on the caller's workspace tensor."""
+    import torch
+    from merizo_search_amd import _lib
+    lib = _lib.load()
+    d_xyz, d_seq, d_off = _packed(structs)
+    d_pairs = torch.tensor(pairs, dtype=torch.int32, device="cuda:0").reshape(-1, 2)
+    npairs = d_pairs.shape[0]
+    of = torch.full((npairs, 3), float("nan"), dtype=torch.float64, device="cuda:0")
+    oi = torch.full((npairs, 3), -7, dtype=torch.int32, device="cuda:0")
+    inv = torch.full((npairs, max2), -1, dtype=torch.int32, device="cuda:0")
+    rc = lib.ms_tmalign_batch(d_xyz.data_ptr(), d_seq.data_ptr(), d_off.data_ptr(), len(structs), d_pairs.data_ptr(), npairs,
+                              max1, max2, _lib.TM_FAST if fast else 0, ws.data_ptr(), ws.numel(), of.data_ptr(), oi.data_ptr(),
+                              inv.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.ms_last_error()
+    torch.cuda.synchronize()
+    f, i = of.cpu().numpy(), oi.cpu().numpy()
+    return {"qtm": f[:, 0], "ttm": f[:, 1], "rmsd": f[:, 2], "n_ali8": i[:, 0], "n_identical": i[:, 1], "status": i[:, 2],
+            "invmap": inv.cpu().numpy()}
+
+
+def _assert_same_bits(a, b, rows, what):
+    for key in ("qtm", "ttm", "rmsd", "n_ali8", "n_identical", "status"):
+        assert np.asarray(a[key])[rows].tobytes() == np.asarray(b[key])[rows].tobytes(), (what, key)
+    for r in rows:
+        assert np.array_equal(a["invmap"][r], b["invmap"][r][:a["invmap"].shape[1]]), (what, r)
+
+
+@pytest.mark.parametrize("fast", [False, True])
+def test_one_to_three_poisoned_slots_give_the_bits_of_a_plain_run(fast):
+    """Workspaces of exactly 1, 2 and 3 slots, filled with random bytes and then 0xFF, pairs short -> long -> short: each
+    slot (and its workgroup's LDS) takes pairs of growing, then shrinking extents over stale state of the pair before."""
+    import torch
+    from merizo_search_amd import _lib
+    structs = _short_chains(16, 21) + [("walk5", tm_case.walk(5, 5), "A" * 5)]
+    structs.sort(key=lambda t: len(t[1]))                                      # walk5 (refused) first, the longest last
+    k = len(structs) - 1
+    order = [1, 5, 9, 13, k - 1, k, 14, 10, 6, 2, k, 0, 3, 12, 4]            # short -> long -> short
+    pairs = [(order[m], order[m + 1]) for m in range(len(order) - 1)] + [(k - 1, k - 1), (2, 0), (k, 5)]
+    plain = _gpu_batch(structs, pairs, fast)
+    lens = [len(s[1]) for s in structs]
+    max1, max2 = max(lens[i] for i, _ in pairs), max(lens[j] for _, j in pairs)
+    lib = _lib.load()
+    base = int(lib.ms_tmalign_workspace_bytes(max1, max2, 1))
+    per = int(lib.ms_tmalign_workspace_bytes(max1, max2, 2)) - base
+    for slots in (1, 2, 3):
+        ws = torch.empty(base + (slots - 1) * per, dtype=torch.uint8, device="cuda:0")
+        for fill in ("random", 0xFF):
+            if fill == "random":
+                ws.copy_(torch.randint(0, 256, (ws.numel(),), dtype=torch.uint8, generator=torch.Generator().manual_seed(slots)))
+            else:
+                ws.fill_(fill)
+            got = _raw_batch(structs, pairs, fast, max1, max2, ws)
+            _assert_same_bits(got, plain, range(len(pairs)), (slots, fill))
+    _assert_matches_restatement("poisoned slots", structs, pairs, fast, plain)
+
+
+def test_long_and_index_statuses_leave_the_other_pairs_bits():
+    """MS_TM_ERR_LONG (a chain over the max_len1 / max_len2 passed in) and MS_TM_ERR_INDEX next to valid pairs: the refused
+    pairs get status, zero outputs and an untouched (-1) alignment row; the valid pairs keep the bits of a plain run."""
+    import torch
+    from merizo_search_amd import _lib
+    structs = _short_chains(12, 31)
+    lens = [len(s[1]) for s in structs]
+    short = sorted(range(len(structs)), key=lambda s: lens[s])
+    max1 = lens[short[6]]                              # chains 1 longer than this are refused
+    pairs = [(short[0], short[1]), (short[-1], short[2]), (short[3], short[-1]), (len(structs), short[0]),
+             (short[1], -1), (short[5], short[4]), (short[-2], short[-3]), (short[6], short[0])]
+    max2 = max(lens[j] for _i, j in pairs if 0 <= j < len(structs))
+    ws = torch.empty(int(_lib.load().ms_tmalign_workspace_bytes(max1, max2, len(pairs))), dtype=torch.uint8, device="cuda:0")
+    ws.fill_(0xFF)
+    got = _raw_batch(structs, pairs, False, max1, max2, ws)
+    ns = len(structs)
+    expect = [_lib.TM_ERR_INDEX if not (0 <= i < ns and 0 <= j < ns) else _lib.TM_ERR_LONG if lens[i] > max1 else 0
+              for i, j in pairs]
+    assert list(got["status"]) == expect and expect.count(_lib.TM_ERR_LONG) >= 2
+    valid = [p for p, e in enumerate(expect) if e == 0]
+    assert len(valid) >= 3
+    plain = _gpu_batch(structs, [pairs[p] for p in valid], False)
+    sub = {k: np.asarray(v)[valid] for k, v in got.items()}
+    _assert_same_bits(sub, plain, range(len(valid)), "valid pairs")
+    _assert_invariants(got, [lens[i] if 0 <= i < len(structs) else 0 for i, _ in pairs],
+                       [lens[j] if 0 <= j < len(structs) else 0 for _, j in pairs])

@@ -210,7 +210,7 @@ static void gather(ctx_t *c, const int *sel, int start, int n)
 }
 
 /* TMalign.cpp score_fun8: distances of the rotated pairs, the ordered list of pairs within d (relaxed by 0.5 A while
- * fewer than 3 survive), the score sum / Lnorm */
+ * fewer than 3 survive and a pair outside the cut has a finite distance), the score sum / Lnorm */
 static int score_fun8(ctx_t *c, int lali, const double t[3], const double u[3][3], double d, int *i_ali, double *score,
                       int score_sum_method, double Lnorm, double score_d8, double d0)
 {
@@ -221,13 +221,15 @@ static int score_fun8(ctx_t *c, int lali, const double t[3], const double u[3][3
         c->dis[i] = dist2(xx, c->y + 3 * c->ay[i]);
     }
     for (;;) {
+        int out_finite = 0;     /* NaN / inf distances never enter the cut: relaxing for them would not end */
         n_cut = 0;
         for (int i = 0; i < lali; i++) {
             double di = c->dis[i];
             if (di < d_tmp) i_ali[n_cut++] = i;
+            else out_finite |= isfinite(di) != 0;
             c->terms[i] = (score_sum_method != 8 || di <= score_d8_cut) ? 1 / (1 + di / d02) : 0.0;
         }
-        if (n_cut < 3 && lali > 3) {
+        if (n_cut < 3 && lali > 3 && out_finite) {
             inc++;
             double dinc = d + inc * 0.5;
             d_tmp = dinc * dinc;
@@ -321,10 +323,22 @@ static double detailed_search(ctx_t *c, const int *y2x, double t[3], double u[3]
     return TMscore8_search(c, k, t, u, simplify_step, 8, c->d0_search, c->Lnorm, c->score_d8, c->d0);
 }
 
+/* the ordered list of the pairs [0, n_ali) with dis <= cut -> c->i_ali; returns their number, *out_finite: whether a pair
+ * outside the cut has a finite distance (get_score_fast relaxes the cut by 0.5 while fewer than 3 are within and one is) */
+static int within(ctx_t *c, int n_ali, double cut, int *out_finite)
+{
+    int j = 0;
+    *out_finite = 0;
+    for (int k = 0; k < n_ali; k++)
+        if (c->dis[k] <= cut) c->i_ali[j++] = k;
+        else *out_finite |= isfinite(c->dis[k]) != 0;
+    return j;
+}
+
 /* TMalign.cpp get_score_fast: three superpositions of the pairs of y2x */
 static double get_score_fast(ctx_t *c, const int *y2x, double t[3], double u[3][3])
 {
-    int n_ali = pairs_of(c, y2x), j;
+    int n_ali = pairs_of(c, y2x), j, out_finite;
     double d002 = c->d0_search * c->d0_search, d02 = c->d0 * c->d0, xx[3], tmscore, tmscore1, tmscore2;
     gather(c, NULL, 0, n_ali);
     kabsch(c, c->r1, c->r2, n_ali, t, u);
@@ -336,10 +350,8 @@ static double get_score_fast(ctx_t *c, const int *y2x, double t[3], double u[3][
     tmscore = rsum(c->terms, n_ali, c->order);
     double d002t = d002;
     for (;;) {
-        j = 0;
-        for (int k = 0; k < n_ali; k++)
-            if (c->dis[k] <= d002t) c->i_ali[j++] = k;
-        if (j < 3 && n_ali > 3) d002t += 0.5;
+        j = within(c, n_ali, d002t, &out_finite);
+        if (j < 3 && n_ali > 3 && out_finite) d002t += 0.5;
         else break;
     }
     if (n_ali != j) {
@@ -353,10 +365,8 @@ static double get_score_fast(ctx_t *c, const int *y2x, double t[3], double u[3][
         tmscore1 = rsum(c->terms, n_ali, c->order);
         d002t = d002 + 1;
         for (;;) {
-            j = 0;
-            for (int k = 0; k < n_ali; k++)
-                if (c->dis[k] <= d002t) c->i_ali[j++] = k;
-            if (j < 3 && n_ali > 3) d002t += 0.5;
+            j = within(c, n_ali, d002t, &out_finite);
+            if (j < 3 && n_ali > 3 && out_finite) d002t += 0.5;
             else break;
         }
         gather(c, c->i_ali, 0, j);
@@ -637,6 +647,22 @@ static void get_initial_fgt(ctx_t *c, int *y2x, double t[3], double u[3][3])
 }
 
 /* ------------------------------------------------------------------ TMalign_main ---------------------------------- */
+/* Test hook: the superposition of the n point pairs r1 -> r2 (r2 ~ u r1 + t; u row-major [3][3]) that kabsch computes in
+ * order=kernel, for checking the solver against an independent SVD.  Returns 0, or -1 for n < 0. */
+int tm_kabsch(const double *r1, const double *r2, int n, double *t, double *u)
+{
+    if (n < 0) return -1;
+    ctx_t C;
+    memset(&C, 0, sizeof C);
+    C.order = 1;
+    C.terms = malloc(sizeof(double) * (n > 0 ? n : 1));
+    double uu[3][3];
+    kabsch(&C, r1, r2, n, t, uu);
+    memcpy(u, uu, sizeof uu);
+    free(C.terms);
+    return 0;
+}
+
 /* x: chain 1 (query) [xlen][3], y: chain 2 [ylen][3].  out_f: qtm (normalised by xlen), ttm (by ylen), rmsd;
  * out_i: n_ali8, n_identical; invmap_out [ylen] (NULL: not wanted): the final alignment y -> x (-1 = gap).
  * Returns 0, or -1 for a chain of <= 5 residues. */

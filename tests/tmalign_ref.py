@@ -33,6 +33,8 @@ def load():
     vp = ctypes.c_void_p
     lib.tm_align.restype = ctypes.c_int
     lib.tm_align.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+    lib.tm_kabsch.restype = ctypes.c_int
+    lib.tm_kabsch.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     _lib = lib
     return lib
 
@@ -63,3 +65,15 @@ def tm_align(x, y, seqx=None, seqy=None, fast=False, order="seq", quantize=True)
         raise ValueError("TM-align refuses structures of <= 5 residues (%d, %d)" % (len(x), len(y)))
     return {"qtm": float(out_f[0]), "ttm": float(out_f[1]), "rmsd": float(out_f[2]), "n_ali8": int(out_i[0]),
             "n_identical": int(out_i[1]), "invmap": inv[:len(y)].copy()}
+
+
+def kabsch(r1, r2):
+    """The restatement's superposition of the point pairs r1 -> r2 in order=kernel (the kernel's solver, op for op):
+    (t [3], u [3][3]) with r2 ~ r1 @ u.T + t."""
+    r1 = np.ascontiguousarray(r1, dtype=np.float64).reshape(-1, 3)
+    r2 = np.ascontiguousarray(r2, dtype=np.float64).reshape(-1, 3)
+    assert len(r1) == len(r2)
+    t, u = np.zeros(3), np.zeros((3, 3))
+    if load().tm_kabsch(r1.ctypes.data, r2.ctypes.data, len(r1), t.ctypes.data, u.ctypes.data) != 0:
+        raise ValueError("tm_kabsch refused n = %d" % len(r1))
+    return t, u

@@ -210,6 +210,26 @@ int ms_topk_merge(const float *scores, const int64_t *idx, int S, int nq, int k,
 int ms_topk_merge_strided(const float *scores, const int64_t *idx, int64_t score_stride_bytes, int64_t idx_stride_bytes,
                           int S, int nq, int k, float *out_scores, int64_t *out_idx, ms_stream_t stream);
 
+/* Exact removal of excluded rows from top-k lists: the step behind the scan when a database is searched against itself
+ * (every query finds its own row first, the sibling domains of its chain next; the reference has no such search -- its
+ * callers filter hit tables by hand).  Per query q, from a list of kin entries sorted as ms_ip_topk leaves it (score
+ * descending, row ascending, (-inf, -1) padding last):
+ *   - entries whose row lies in [lo[q], hi[q]) are dropped (global row numbers; lo[q] >= hi[q]: nothing is excluded);
+ *   - entries whose score is below min_score are dropped (-inf: no cut; NaN is refused);
+ *   - what remains keeps its order, the first kout entries are written, the tail is padded with (-inf, -1);
+ *   - out_count[q] = the number of real entries written.
+ * scores float32 [nq,kin], idx int64 [nq,kin], lo / hi int64 [nq], out_scores float32 [nq,kout], out_idx int64 [nq,kout],
+ * out_count int32 [nq]; the outputs may not overlap the inputs.  NULL pointers, nq < 1, kout < 1 and kin < kout: MS_ERR_ARG.
+ * One wave per query, the list read in 64-entry pieces (any kin), order preserved by a ballot compaction.
+ * EXACTNESS: a database with the rows [lo, hi) removed has its best kout rows among the best kout + (hi - lo) rows of the
+ * whole database (at most hi - lo of those are excluded, and removing rows does not reorder the others).  So if the input is
+ * the exact top-kin of the whole database and kin >= kout + (hi[q] - lo[q]) for every query, the output is the exact
+ * top-kout of the database without those rows -- scores and order included -- as long as min_score cuts nothing; with a
+ * cut it is that list's entries at or above min_score.  Backward compatible addition: ms_version() stays 210. */
+int ms_topk_drop_ranges(const float *scores, const int64_t *idx, int nq, int kin, const int64_t *lo, const int64_t *hi,
+                        float min_score, int kout, float *out_scores, int64_t *out_idx, int32_t *out_count,
+                        ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

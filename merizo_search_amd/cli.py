@@ -1,4 +1,4 @@
-"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments.
+"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments, and `db-search`.
 
 Mirror of merizo_search/merizo.py for the Foldclass path (search :126-226, easy_search :229-407,
 createdb :102-123).  `segment` (the Merizo IPA network) is out of scope: easy-search takes the
@@ -7,6 +7,10 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli search  <pdb...> <db_name> <output> <tmp> [-d cuda] [-k 10] ...
     python -m merizo_search_amd.cli createdb <input_dir> <out_db> [-d cuda] [--layout pt|faiss|both]
     python -m merizo_search_amd.cli easy-search <pdb...> <db_name> <output> <tmp> --chopping "71-189,190-290"
+    python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
+
+`db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
+against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
 
 Several GPUs of one node: start one process per GPU with torchrun,
 
@@ -30,7 +34,7 @@ from .foldclass import chopping as chop
 from .foldclass import sharded
 from .foldclass.dbsearch import run_dbsearch
 from .foldclass.makedb import run_createdb
-from .foldclass.results import (EASY_SEARCH_FIELDS, SEARCH_FIELDS, check_for_database, parse_output_format,
+from .foldclass.results import (EASY_SEARCH_FIELDS, SEARCH_FIELDS, check_for_database, embedding_only_format, parse_output_format,
                                 write_search_results, write_segment_results)
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s | %(levelname)s | %(message)s")
@@ -122,13 +126,7 @@ def _log_command(mode: str) -> None:
 
 
 def _embedding_only_format(fields, skip):
-    if not skip:
-        return fields
-    drop = {"ali_len", "seq_id", "q_tm", "t_tm", "max_tm", "rmsd"}
-    kept = [f for f in fields if f not in drop]
-    if len(kept) != len(fields):
-        logging.warning("TM-align columns dropped from the output (embedding-only search).")
-    return kept
+    return embedding_only_format(fields, skip)
 
 
 def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
@@ -251,6 +249,55 @@ def easy_search(argv) -> None:
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def db_search(argv) -> None:
+    p = argparse.ArgumentParser(prog="db-search", description="Search the entries of one Foldclass database against another "
+                                "database (or against itself) on the GPU: the stored embeddings are the queries.",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("query_db", type=str, help="Database prefix whose rows are the queries (either layout).")
+    p.add_argument("target_db", type=str, help="Database prefix to search (either layout; may be query_db itself).")
+    p.add_argument("output", type=str)
+    p.add_argument("tmp", type=str)
+    p.add_argument("-d", "--device", type=str, default="cuda", help="'cuda' / 'cuda:N' = the MI355X. 'cpu' is refused by this build.")
+    p.add_argument("-k", "--topk", type=int, default=1, help="Max number of domain matches to return per query domain.")
+    p.add_argument("-s", "--mincos", type=float, default=0.5, help="Minimum cosine similarity of reported hits.")
+    p.add_argument("-m", "--mintm", type=float, default=0.5, help="Minimum TM-align score of reported hits.")
+    p.add_argument("-c", "--mincov", type=float, default=0.7, help="Minimum coverage of database matches.")
+    p.add_argument("-f", "--fastmode", action="store_true", help="TM-align -fast.")
+    p.add_argument("--format", type=str, default=SEARCH_FIELDS, help="Comma-separated output columns.")
+    p.add_argument("--output_headers", action="store_true", default=False)
+    p.add_argument("--search_batchsize", type=int, default=262144, help="Target rows per block when the target is streamed.")
+    p.add_argument("--report_insignificant_hits", action="store_true", default=False)
+    p.add_argument("--metadata_json", action="store_true", default=False)
+    p.add_argument("--skip_tmalign", action="store_true", default=False,
+                   help="Embedding-only search (automatic when no TM-align binary is found and --tmalign_backend is auto).")
+    p.add_argument("--tmalign_backend", type=str, default="auto", choices=["auto", "hip"],
+                   help="'auto': the TM-align binary ($MERIZO_TMALIGN) if one is found, else an embedding-only search. "
+                        "'hip': TM-align every hit of a query batch on the GPU in one launch. --skip_tmalign wins over both.")
+    p.add_argument("--query_batchsize", type=int, default=4096, help="Queries per scan call.")
+    p.add_argument("--query_rows", type=str, default=None, metavar="LO:HI", help="Rows of query_db to search (default: all).")
+    p.add_argument("--exclude_self", action="store_true", default=False,
+                   help="query_db and target_db are the same database: never report a query as its own hit.")
+    p.add_argument("--exclude_same_chain", action="store_true", default=False,
+                   help="query_db and target_db are the same database: report no domain of the query's own chain "
+                        "(implies --exclude_self).")
+    args = p.parse_args(argv)
+    _join_process_group(args)
+    tmp = munge_tmp_with_uuid(args.tmp)
+    _log_command("db-search")
+    from .foldclass.dbsearch import run_dbsearch_db
+    fields = parse_output_format(args.format, SEARCH_FIELDS)
+    t0 = time.time()
+    n = run_dbsearch_db(query_db=args.query_db, db_name=args.target_db, output=args.output, tmp=tmp, device=args.device,
+                        topk=args.topk, fastmode=args.fastmode, mincos=args.mincos, mintm=args.mintm, mincov=args.mincov,
+                        search_batchsize=args.search_batchsize, skip_tmalign=args.skip_tmalign, tmalign_backend=args.tmalign_backend,
+                        query_batchsize=args.query_batchsize, query_rows=args.query_rows, exclude_self=args.exclude_self,
+                        exclude_same_chain=args.exclude_same_chain, format_list=fields,
+                        header=args.output_headers, metadata_json=args.metadata_json,
+                        report_insignificant_hits=args.report_insignificant_hits)
+    logging.info(f"Finished db-search of {n} queries in {time.time() - t0:.3f} seconds.")
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def createdb(argv) -> None:
     p = argparse.ArgumentParser(prog="createdb", description="Embed a directory of PDB files into a Foldclass database.",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -269,9 +316,9 @@ def createdb(argv) -> None:
 
 def main(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
-    modes = {"search": search, "easy-search": easy_search, "createdb": createdb}
+    modes = {"search": search, "easy-search": easy_search, "createdb": createdb, "db-search": db_search}
     if not argv or argv[0] not in modes:
-        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb} ...  "
+        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb,db-search} ...  "
               "(segment: out of scope, use the reference)", file=sys.stderr)
         sys.exit(2)
     modes[argv[0]](argv[1:])

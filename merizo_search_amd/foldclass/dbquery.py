@@ -1,0 +1,151 @@
+"""A Foldclass database as the QUERY side of a search (`db-search`, dbsearch.run_dbsearch_db).
+
+The reference searches PDB files only ("a few query domains per call", dbsearch.py:531-546): a user who holds embeddings in
+a database -- createdb output of a proteome, a TED shard -- has to re-parse and re-embed the structures to search with them.
+`QueryDB` reads, for a row range of either on-disk layout (dbutil.py), what a search needs of its queries:
+
+    embeddings(lo, hi)    float32 [hi-lo,128] as STORED: raw in the `.pt` layout (the searches normalise queries themselves:
+                          MS_MODE_COSINE_UNIT, MS_MODE_IP_NORMQ -- results bit-identical to `search` on the same structure),
+                          F.normalize'd in the faiss layout (searched as they are, MS_MODE_IP_PRENORM: a second normalisation
+                          would change bits)
+    records(lo, hi)       the query dicts of the drivers: name (normalised as multidomain._TargetStore.entry does), seq,
+                          coords (only when an aligner will read them)
+    exclusion_ranges(..)  per query row the database rows a self-search must not report: the row itself, or the contiguous
+                          run of rows of its chain (multidomain.domid2chainid; rows of one chain are adjacent, as
+                          multidomain.sibling_rows relies on)
+"""
+from __future__ import annotations
+
+import os
+from typing import List, Tuple
+
+import numpy as np
+
+from . import dbutil
+from .multidomain import _TargetStore, domid2chainid
+
+
+def same_database(prefix_a: str, prefix_b: str) -> bool:
+    """Do two database prefixes name the same files?"""
+    return os.path.realpath(prefix_a) == os.path.realpath(prefix_b)
+
+
+def parse_row_slice(text, n: int) -> Tuple[int, int]:
+    """'LO:HI' (either side may be empty) -> (lo, hi) with 0 <= lo < hi <= n; None: all rows.  ValueError otherwise."""
+    if text is None:
+        lo, hi = 0, n
+    else:
+        parts = str(text).split(":")
+        if len(parts) != 2:
+            raise ValueError("expected LO:HI, got %r" % (text,))
+        try:
+            lo = int(parts[0]) if parts[0].strip() else 0
+            hi = int(parts[1]) if parts[1].strip() else n
+        except ValueError:
+            raise ValueError("expected LO:HI with integer row numbers, got %r" % (text,))
+    if lo < 0 or hi > n:
+        raise ValueError("rows %d:%d lie outside the query database (%d rows)" % (lo, hi, n))
+    if lo >= hi:
+        raise ValueError("rows %d:%d select no query (the query database has %d rows)" % (lo, hi, n))
+    return lo, hi
+
+
+class QueryDB:
+    """Stored embeddings, names, sequences and coordinates of a database's rows, for either layout."""
+
+    def __init__(self, db_name: str, loaded=None):
+        """loaded: dbsearch.read_database's dict of this same `.pt` database, before it went to an engine -- its unpickled
+        index and its mapped tensor are used instead of reading both a second time (a database searched against itself)."""
+        self.prefix = db_name
+        shared = loaded is not None and not loaded.get("faiss") and "_engine" not in loaded
+        self.store = _TargetStore(db_name, index=loaded["index"] if shared else None)
+        self.faiss = self.store.faiss
+        self.n = self.store.n
+        if self.faiss:
+            info = dbutil.read_dbinfo(db_name + ".json")
+            folder = os.path.dirname(db_name + ".json")
+            if int(info["DB_SIZE"]) != self.n:
+                raise ValueError("%s.json: DB_SIZE %d, but the names file holds %d records" % (db_name, int(info["DB_SIZE"]), self.n))
+            self.matrix = dbutil.db_memmap(os.path.join(folder, info["dbfname_IP"]), (int(info["DB_SIZE"]), int(info["DB_DIM"])))
+        elif shared:
+            self.matrix = loaded["database"]            # the raw rows on the host (the engine gets its own, normalised copy)
+        else:
+            import torch
+
+            try:                # memory-mapped: a row slice reads its own pages only
+                raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True, mmap=True)
+            except (RuntimeError, TypeError, ValueError):
+                raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True)
+            self.matrix = raw
+        if not self.faiss and self.matrix.size(0) != self.n:
+            raise ValueError("%s.pt holds %d rows, its index %d entries" % (db_name, self.matrix.size(0), self.n))
+
+    @property
+    def normalized(self) -> bool:
+        """Are the stored rows L2-normalised already (the faiss layout)?"""
+        return self.faiss
+
+    def close(self) -> None:
+        self.store.close()
+
+    def embeddings(self, lo: int, hi: int) -> np.ndarray:
+        if self.faiss:
+            return np.ascontiguousarray(self.matrix[lo:hi], dtype=np.float32)
+        return np.ascontiguousarray(self.matrix[lo:hi].float().numpy())
+
+    def names(self, lo: int, hi: int) -> List[str]:
+        if self.faiss:
+            rec = np.frombuffer(self.store.names[lo * dbutil.NAME_RECORD: hi * dbutil.NAME_RECORD], dtype="S%d" % dbutil.NAME_RECORD)
+            return [r.decode().rstrip() for r in rec]
+        return [os.path.basename(self.store.index[r][0]).replace(".pdb", "") for r in range(lo, hi)]
+
+    def _blobs(self, pair, lo: int, hi: int, conv):
+        index, data = pair
+        offsets = np.frombuffer(index[lo * 16: hi * 16], dtype=np.int64).reshape(-1, 2)
+        return [dbutil.retrieve_bytes(s, e, mm=data, typeconv=conv) for s, e in offsets]
+
+    def seqs(self, lo: int, hi: int) -> List[str]:
+        if self.faiss:
+            return self._blobs(self.store.seq, lo, hi, dbutil.ascii_conv)
+        return [self.store.index[r][2] for r in range(lo, hi)]
+
+    def coords(self, lo: int, hi: int) -> List[np.ndarray]:
+        if self.faiss:
+            return self._blobs(self.store.coords, lo, hi, dbutil.coord_conv)
+        return [self.store.index[r][1] for r in range(lo, hi)]
+
+    def records(self, lo: int, hi: int, with_coords: bool = True) -> List[dict]:
+        """Query dicts {name, seq, coords} of rows [lo, hi), in row order (coords None unless asked for)."""
+        coords = self.coords(lo, hi) if with_coords else [None] * (hi - lo)
+        return [{"name": n, "seq": s, "coords": c} for n, s, c in zip(self.names(lo, hi), self.seqs(lo, hi), coords)]
+
+    def exclusion_ranges(self, lo: int, hi: int, same_chain: bool) -> Tuple[np.ndarray, np.ndarray]:
+        """(first, past-last) database row a self-search excludes for every query row of [lo, hi): the row itself, or with
+        same_chain the whole run of adjacent rows whose chain id equals the query's (it may reach beyond [lo, hi))."""
+        rows = np.arange(lo, hi, dtype=np.int64)
+        if not same_chain:
+            return rows, rows + 1
+        chains = [domid2chainid(n) for n in self.store_names(lo, hi)]
+        first, last = np.empty(hi - lo, np.int64), np.empty(hi - lo, np.int64)
+        a = 0
+        while a < hi - lo:
+            b = a + 1
+            while b < hi - lo and chains[b] == chains[a]:
+                b += 1
+            first[a:b], last[a:b] = lo + a, lo + b
+            a = b
+        r = lo - 1                                  # the first and the last run may continue outside the slice
+        while r >= 0 and domid2chainid(self.store.name(r)) == chains[0]:
+            r -= 1
+        first[first == first[0]] = r + 1
+        r = hi
+        while r < self.n and domid2chainid(self.store.name(r)) == chains[-1]:
+            r += 1
+        last[last == last[-1]] = r
+        return first, last
+
+    def store_names(self, lo: int, hi: int) -> List[str]:
+        """Names as stored (the `.pt` index keeps paths): what multidomain.domid2chainid is applied to."""
+        if self.faiss:
+            return self.names(lo, hi)
+        return [self.store.index[r][0] for r in range(lo, hi)]

@@ -9,6 +9,7 @@ Same function names, argument meaning, return shapes and on-disk layouts as the 
     dbsearch                                      dbsearch.py:84-200   `.pt` database
     dbsearch_faiss                                dbsearch.py:203-472  faiss-layout database
     run_dbsearch                                  dbsearch.py:475-551
+    run_dbsearch_db                               (no counterpart: a database as the query side, `db-search`)
 
 What differs, deliberately (DESIGN.md "host drivers"):
   * all queries of a call are embedded in ONE ragged GPU launch and searched in ONE batched
@@ -401,7 +402,19 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
     all_results = [dict() for _ in range(nq)]
     if rank != 0:
         return results, all_results                                       # rank 0 assembles the hit records
+    return _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
+                              _aligner_device(network, device))
 
+
+def _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
+                       aligner_device, tm_excluded_before: int = 0):
+    """Rank 0's half of dbsearch_faiss (dbsearch.py:312-472): the top-k lists D / I of all queries -> (results, all_results),
+    hit records retrieved from the mmaps of the layout (`path(key)`: the file a json key names), TM-align per hit.
+    tm_excluded_before: hits below mintm are keyed by ONE counter over all queries of a search (dbsearch.py:449-452); a
+    search made in several calls (run_dbsearch_db's query batches) passes how many the earlier calls counted."""
+    nq = len(query_dicts)
+    results = [dict() for _ in range(nq)]
+    all_results = [dict() for _ in range(nq)]
     keep = np.where((D >= mincos) & (I >= 0))                  # row-major: grouped by query, rank order
     hit_indices, hit_scores, query_indices = I[keep], D[keep], keep[0]
     n_hits = len(hit_indices)
@@ -432,9 +445,9 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
     hip_outputs = None
     if not skip_tmalign and tmalign_backend == "hip":               # every hit of the call in one GPU batch
         hip_outputs = _hip_tm_outputs(query_dicts, [(int(query_indices[h]), hit_coords[h], hit_seqs[h]) for h in range(n_hits)],
-                                      fastmode, _aligner_device(network, device))
+                                      fastmode, aligner_device)
     counts = [0] * nq
-    n_tm_exclude = 0
+    n_tm_exclude = int(tm_excluded_before)
     for h in range(n_hits):
         qi = int(query_indices[h])
         qd = query_dicts[qi]
@@ -457,8 +470,8 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
         else:
             all_results[qi][n_tm_exclude] = rec
             n_tm_exclude += 1
-    if n_tm_exclude > 0:
-        logger.info("Excluded " + str(n_tm_exclude) + " hits (across all query domains) by TM-score threshold(>=" + str(mintm) + ")")
+    if n_tm_exclude > tm_excluded_before:
+        logger.info("Excluded " + str(n_tm_exclude - int(tm_excluded_before)) + " hits (across all query domains) by TM-score threshold(>=" + str(mintm) + ")")
     return results, all_results
 
 
@@ -530,3 +543,246 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
         search_results.append(res)
         all_search_results.append(all_res)
     return search_results, all_search_results
+
+
+# ------------------------------------------------------------------ database x database -
+def engine_setup(device):
+    """The engine of a db-search.  No encoder and no weights: its queries are stored embeddings."""
+    from .engine import HipEngine, resolve_device
+    return HipEngine(resolve_device(device))
+
+
+def _refuse(message: str) -> None:
+    logger.error(message)
+    sys.exit(1)
+
+
+class _DeviceTimes:
+    """HIP-event spans of the scan calls and the drop kernel of a db-search (tools/dbsearch_bench.py); off unless asked for."""
+
+    def __init__(self, engine, sink):
+        self.sink = sink
+        self.torch = engine.torch if sink is not None and getattr(engine.device, "type", "cpu") == "cuda" else None
+        self.spans = {}
+
+    def mark(self):
+        if self.torch is None:
+            return None
+        ev = self.torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+
+    def add(self, name, start, end=None):
+        if self.torch is not None:
+            self.spans.setdefault(name, []).append((start, end or self.mark()))
+
+    def finish(self):
+        if self.torch is None:
+            return
+        self.torch.cuda.synchronize()
+        for name, spans in self.spans.items():
+            self.sink[name + "_ms"] = float(sum(a.elapsed_time(b) for a, b in spans))
+            self.sink[name + "_first_ms"] = float(spans[0][0].elapsed_time(spans[0][1]))
+            self.sink[name + "_calls"] = len(spans)
+
+
+def _append_tsv(results, path: str, part: str, fields, header: bool) -> None:
+    """One batch's rows behind what `path` holds already, written by results.write_search_results itself."""
+    from .results import write_search_results
+    write_search_results(results=results, output_file=part, format_list=fields, header=header)
+    with open(part, "rb") as src, open(path, "ab") as dst:
+        dst.write(src.read())
+    os.remove(part)
+
+
+def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="cuda", topk: int = 1, fastmode: bool = False,
+                    mincos: float = 0.5, mintm: float = 0.5, mincov: float = 0.7, search_batchsize: int = 262144,
+                    search_type: str = "IP", skip_tmalign: bool = False, tmalign_backend: str = "auto",
+                    query_batchsize: int = 4096, query_rows: Optional[str] = None, exclude_self: bool = False,
+                    exclude_same_chain: bool = False, format_list=None, header: bool = False, metadata_json: bool = False,
+                    report_insignificant_hits: bool = False, engine=None, timings: Optional[dict] = None) -> int:
+    """Search the rows of database `query_db` (all, or the slice query_rows = 'LO:HI') against database `db_name` and write
+    `<output>_search.tsv` (+ `_search_insignificant.tsv`), in query-row order: `search` with a database in the place of the
+    PDB files.  No structure is parsed or embedded -- the stored embeddings are the queries (dbquery.QueryDB), so the
+    search runs in the batches the kernels were built for: per `query_batchsize` queries ONE scan (resident target; the
+    streamed knn_exact over engine.device_blocks beyond the HBM budget), one exchange + merge under several ranks, one
+    ms_topk_drop_ranges, one record retrieval, one TM-align batch ('hip'), one append to the output.
+
+    exclude_self / exclude_same_chain (query and target the SAME database): the query's own row / every row of its chain
+    is taken out of its list EXACTLY: the scan fetches k' = k + the longest excluded run and the drop kernel removes
+    them (include/merizo_search_amd.h).  mincos is the kernel's min_score: only surviving hits are retrieved.
+    Everything else -- thresholds, hit records, columns -- is the code of dbsearch / dbsearch_faiss.  Returns the number of
+    queries searched.  `timings`: a dict that receives which path ran ('in_place': the queries were row ranges of the resident
+    matrix; 'streamed': the target went through engine.device_blocks) and HIP-event totals of the scan calls and the drop step."""
+    import time
+    from types import SimpleNamespace
+
+    from .dbquery import QueryDB, parse_row_slice, same_database
+    from .results import SEARCH_FIELDS, embedding_only_format
+
+    t_start = time.perf_counter()
+    if engine is None:
+        from .engine import resolve_device
+        device = resolve_device(device)                                   # ('cpu' is refused here, before anything else)
+    if tmalign_backend not in tm.BACKENDS:
+        _refuse("tmalign_backend must be one of %s, got %r" % (", ".join(tm.BACKENDS), tmalign_backend))
+    if topk < 1 or query_batchsize < 1 or search_batchsize < 1:
+        _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
+    exclude_self = exclude_self or exclude_same_chain
+    same = same_database(query_db, db_name)
+    if exclude_self and not same:
+        _refuse("--exclude_self / --exclude_same_chain remove the query's own rows from its hits: they need the query database "
+                "and the target database to be the same, got %s and %s." % (query_db, db_name))
+    for prefix in (query_db, db_name):
+        if not (os.path.exists(prefix + ".json") or (os.path.exists(prefix + ".pt") and os.path.exists(prefix + ".index"))):
+            _refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
+                    % (prefix, prefix, prefix))
+    target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
+    # (a `.pt` database searched against itself: ONE unpickled index and one mapped tensor serve both sides)
+    qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
+    try:
+        q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
+    except ValueError as exc:
+        _refuse("--query_rows: %s" % exc)
+    if target_db["faiss"]:
+        if search_type != "IP":
+            _refuse("Invalid/unsupported faiss search type: " + search_type + "\n\tOnly 'IP' is currently supported.")
+        dbinfo = read_dbinfo(target_db["database"])
+        db_dir = os.path.dirname(target_db["database"])
+        n_target = int(dbinfo["DB_SIZE"])
+
+        def path(key):
+            return os.path.join(db_dir, dbinfo[key])
+    else:
+        n_target = int(target_db["database"].shape[0])
+    ex_lo = ex_hi = np.zeros(q_hi - q_lo, np.int64)                       # lo >= hi: nothing excluded
+    if exclude_self:
+        ex_lo, ex_hi = qdb.exclusion_ranges(q_lo, q_hi, exclude_same_chain)
+    max_excluded = int((ex_hi - ex_lo).max())
+    kk = int(topk) + max_excluded
+    if kk > n_target and (exclude_self or not target_db["faiss"]):
+        _refuse("-k %d plus the %d rows excluded for a query exceed the %d rows of the target database."
+                % (topk, max_excluded, n_target))
+
+    rank, world = sharded.rank_world()
+    if not skip_tmalign and tmalign_backend == "auto" and tm.find_tmalign() is None:
+        logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
+                       "TM-align columns are unavailable")
+        skip_tmalign = True
+    fields = embedding_only_format(list(format_list) if format_list is not None else SEARCH_FIELDS.split(","), skip_tmalign)
+    if not os.path.exists(tmp):
+        os.makedirs(tmp, exist_ok=True)
+    search_output, all_output = output + "_search.tsv", output + "_search_insignificant.tsv"
+    written = (search_output, all_output) if report_insignificant_hits else (search_output,)      # the files this run writes
+    if rank == 0:
+        for out_path in written:
+            if os.path.exists(out_path):
+                logger.warning(f"Search output file '{out_path}' already exists. Results will be overwritten!")
+            open(out_path, "w").close()
+
+    engine = engine or engine_setup(device)
+    times = _DeviceTimes(engine, timings)
+    network = SimpleNamespace(engine=engine)
+    aligner_device = _aligner_device(network, device)
+    shard = None
+    if target_db["faiss"]:
+        dbmm = db_memmap(filename=path("dbfname_IP"), shape=(dbinfo["DB_SIZE"], dbinfo["DB_DIM"]))
+        lo, hi = sharded.shard_bounds(n_target, world, rank)
+        shard = _resident_shard(target_db, engine, dbmm, lo, hi, min(int(query_batchsize), q_hi - q_lo), kk)
+        if shard is None:
+            logger.info("database shard of %d rows exceeds the resident budget: streaming blocks of %d rows per query batch"
+                        % (hi - lo, int(search_batchsize)))
+    else:
+        _to_engine(target_db, engine)
+    # the same faiss-layout database on one rank: the resident rows ARE the queries (normalised, 16-byte aligned at 512 B per
+    # row), read in place by the scan.  (`.pt`: the resident rows were normalised in place, the raw queries come from the file.)
+    in_place = same and qdb.faiss and world == 1 and shard is not None
+    logger.info("db-search: %d queries of %s against %d rows of %s in batches of %d (k = %d%s)%s"
+                % (q_hi - q_lo, query_db, n_target, db_name, int(query_batchsize), int(topk),
+                   ", %d fetched: up to %d rows excluded per query" % (kk, max_excluded) if exclude_self else "",
+                   "; queries read in place from the resident rows" if in_place else ""))
+    if timings is not None:
+        timings["in_place"], timings["streamed"] = bool(in_place), bool(target_db["faiss"] and shard is None)
+    d_lo, d_hi = engine.to_device(ex_lo), engine.to_device(ex_hi)        # once for the run: a batch's ranges are a slice
+    md_all = {}
+    tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
+    t_loop = time.perf_counter()
+    for b0 in range(q_lo, q_hi, int(query_batchsize)):
+        b1 = min(q_hi, b0 + int(query_batchsize))
+        query_dicts = seqs = None
+        if rank == 0:
+            query_dicts = qdb.records(b0, b1, with_coords=not skip_tmalign)
+            seqs = [qd["seq"] for qd in query_dicts]
+        elif not target_db["faiss"]:
+            seqs = qdb.seqs(b0, b1)                                       # (every rank masks by query length)
+        q = shard[b0:b1] if in_place else engine.to_device(qdb.embeddings(b0, b1))
+        t0 = times.mark()
+        if not target_db["faiss"]:
+            top = search_query_against_db({"seq": seqs, "embedding": q}, target_db, mincov, kk, engine=engine)
+            Ds, Is = top["scores"], top["indices"]
+        else:
+            if shard is not None:
+                Ds, Is = knn_exact(q, [shard], kk, engine, log=_QUIET, row_offset=lo, to_host=False, raw_queries=not qdb.normalized,
+                                   row_norm_bound=target_db["_resident"].get("row_norm_bound"),
+                                   pf_image=target_db["_resident"].get("pf_image"))
+            else:
+                qn = q if qdb.normalized else engine.normalized(q, 1e-12)
+                Ds, Is = knn_exact(qn, db_iterator(dbmm[lo:hi], int(search_batchsize)), kk, engine, log=_QUIET, row_offset=lo,
+                                   to_host=False)
+            Ds, Is = sharded.exchange_and_merge(Ds, Is, engine)
+        t1 = times.mark()
+        times.add("scan", t0, t1)
+        Ds, Is, Cs = engine.topk_drop_ranges(Ds, Is, d_lo[b0 - q_lo: b1 - q_lo], d_hi[b0 - q_lo: b1 - q_lo], int(topk), float(mincos))
+        times.add("drop", t1)
+        if rank != 0:
+            continue
+        D, I, C = Ds.cpu().numpy(), Is.cpu().numpy(), Cs.cpu().numpy()
+        if target_db["faiss"]:
+            results, all_results = _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign,
+                                                      tmalign_backend, tmp, aligner_device, tm_excluded_before=tm_excluded)
+            tm_excluded += sum(len(per_query) for per_query in all_results)
+        else:
+            tops = [(D[r, : C[r]], I[r, : C[r]]) for r in range(b1 - b0)]
+            tm_outputs = [None] * (b1 - b0)
+            if not skip_tmalign and tmalign_backend == "hip":
+                tm_outputs = _pt_hip_outputs(query_dicts, target_db, tops, topk, mincos, fastmode, aligner_device)
+            results, all_results = [], []
+            for r, qd in enumerate(query_dicts):
+                res, all_res = dbsearch(query=qd, target_dict=target_db, tmp=tmp, network=network, topk=topk, mincov=mincov,
+                                        mincos=mincos, mintm=mintm, fastmode=fastmode, device=device, inputs_are_ca=True,
+                                        skip_tmalign=skip_tmalign, _topk=tops[r], tmalign_backend=tmalign_backend,
+                                        _tm_outputs=tm_outputs[r])
+                results.append(res)
+                all_results.append(all_res)
+        part = os.path.join(tmp, "db_search_batch.tsv")
+        _append_tsv(results, search_output, part, fields, header and b0 == q_lo)
+        if report_insignificant_hits:
+            _append_tsv(all_results, all_output, part, fields, header and b0 == q_lo)
+        if metadata_json:
+            for out_path, per_batch in zip(written, (results, all_results)):
+                md_all.setdefault(out_path, []).extend(hit["metadata"] for per_query in per_batch for hit in per_query.values()
+                                                       if hit["metadata"] != "{ }")
+        logger.info("db-search: queries %d..%d done" % (b0, b1 - 1))
+    times.finish()
+    if timings is not None:
+        timings["setup_s"], timings["loop_s"] = t_loop - t_start, time.perf_counter() - t_loop
+    qdb.close()
+    if rank == 0 and metadata_json:                                       # (results.write_search_results' file, for the whole run)
+        import ast
+        import json
+        for out_path in written:
+            with open(out_path + ".hit_metadata.json", "w") as handle:
+                json.dump([ast.literal_eval(m) for m in md_all.get(out_path, [])], handle)
+            logger.info("Metadata for hits written to " + out_path + ".hit_metadata.json")
+    return q_hi - q_lo
+
+
+class _Quiet:
+    """knn_exact's per-call log lines are per query batch here: kept at debug level."""
+
+    @staticmethod
+    def info(*args, **kw):
+        logger.debug(*args, **kw)
+
+
+_QUIET = _Quiet()

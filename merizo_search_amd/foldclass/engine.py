@@ -19,6 +19,8 @@ Engine interface (tensors are torch tensors on the engine's device):
                                                                (None when HBM has no room for it), built once per database
     topk_merge(scores [S,nq,k], idx [S,nq,k])               -> (scores [nq,k], idx [nq,k])
     merge_gathered(PackedExchange)                          -> (scores [nq,k], idx [nq,k])  multi-rank merge
+    topk_drop_ranges(scores, idx, lo, hi, kout, min_score)  -> (scores [nq,kout], idx [nq,kout], count int32 [nq]): the lists without
+                                                               the rows [lo[q], hi[q]) and without scores below min_score (db-search)
     upload_rows(matrix, lo, hi)                             -> rows [lo,hi) of a host matrix as ONE device tensor
     device_blocks(blocks)                                   -> iterator of device tensors (out-of-core streaming)
     resident_budget(nq, k)                                  -> bytes a resident matrix may occupy
@@ -229,6 +231,10 @@ class HipEngine:
     def merge_gathered(self, exchange):
         """Global top-k from the all-gathered per-shard blocks, read in place (ms_topk_merge_strided)."""
         return exchange.merge()
+
+    def topk_drop_ranges(self, scores, idx, lo, hi, kout: int, min_score: float = float("-inf")):
+        """Rows [lo[q], hi[q]) and scores below min_score taken out of sorted lists (ms_topk_drop_ranges)."""
+        return self._ops.topk_drop_ranges(scores, idx, lo, hi, kout, min_score)
 
     # -- database residency ----------------------------------------------------------
     STAGE_ROWS = 1 << 19          # 256 MiB pinned staging buffers

@@ -140,15 +140,19 @@ def group_hits(query_names: Sequence[str], query_chains: Sequence[str], search_r
 class _TargetStore:
     """Names, coordinates, sequences and metadata of database rows, for either on-disk layout."""
 
-    def __init__(self, db_name: str):
+    def __init__(self, db_name: str, index=None):
+        """index: the unpickled `<db>.index` of a `.pt` database when the caller holds it already."""
         self.maps = []
         self.meta = None
         if os.path.exists(db_name + ".pt"):
             import pickle
 
             self.faiss = False
-            with open(db_name + ".index", "rb") as handle:
-                self.index = pickle.load(handle)
+            if index is not None:
+                self.index = index
+            else:
+                with open(db_name + ".index", "rb") as handle:
+                    self.index = pickle.load(handle)
             self.n = len(self.index)
             mdfn = db_name + ".metadata"
             if os.path.exists(mdfn) and os.path.exists(mdfn + ".index"):

@@ -34,6 +34,16 @@ def parse_output_format(format_str: str, expected_str: str):
     return wanted
 
 
+def embedding_only_format(fields, skip_tmalign: bool):
+    """The output columns of a search that aligns nothing: the TM-align columns are dropped, with a warning."""
+    if not skip_tmalign:
+        return fields
+    kept = [f for f in fields if f not in _TM_FIELDS]
+    if len(kept) != len(fields):
+        logger.warning("TM-align columns dropped from the output (embedding-only search).")
+    return kept
+
+
 def check_for_database(db_name: str) -> None:
     """A faiss-layout DB is recognised by <db>.json; otherwise <db>.pt and <db>.index must exist
     (programs/utils.py:23-35)."""

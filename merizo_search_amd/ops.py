@@ -395,6 +395,75 @@ def topk_merge_packed(gathered, S: int, nq: int, k: int, idx_offset: int, out_s,
     return out_s, out_i
 
 
+def _i64_rows(x, nq: int, name: str, device):
+    """lo / hi of topk_drop_ranges: an int64 [nq] device tensor from a tensor or a host array."""
+    torch = _lib.require_gpu()
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64)))
+    t = t.to(device=device, dtype=torch.int64).contiguous()
+    if t.dim() != 1 or t.numel() != nq:
+        raise MerizoHipError(f"{name}: expected {nq} rows, got shape {tuple(t.shape)}")
+    return t
+
+
+def topk_drop_ranges(scores, idx, lo, hi, kout: int, min_score: float = float("-inf"), out=None):
+    """Drop from sorted top-k lists [nq,kin] the entries whose row lies in [lo[q], hi[q]) and those scoring below min_score;
+    the first kout of what remains, in order, (-inf, -1) behind them (ms_topk_drop_ranges).
+    -> (scores f32 [nq,kout], idx i64 [nq,kout], count i32 [nq]).  Exact top-kout of the database without those rows when
+    the input is the exact top-kin and kin >= kout + max(hi - lo).  Asynchronous; out: optional preallocated triple."""
+    torch = _lib.require_gpu()
+    if (not isinstance(scores, torch.Tensor) or not isinstance(idx, torch.Tensor) or scores.dim() != 2 or idx.shape != scores.shape
+            or scores.dtype != torch.float32 or idx.dtype != torch.int64 or not scores.is_cuda):
+        raise MerizoHipError("topk_drop_ranges: expected float32 / int64 CUDA tensors of one shape [nq,kin]")
+    scores, idx = scores.contiguous(), idx.contiguous()
+    nq, kin = scores.shape
+    kout = int(kout)
+    if nq < 1 or not 1 <= kout <= kin:
+        raise MerizoHipError(f"topk_drop_ranges: need nq >= 1 and 1 <= kout <= kin (nq={nq} kin={kin} kout={kout})")
+    lo, hi = _i64_rows(lo, nq, "lo", scores.device), _i64_rows(hi, nq, "hi", scores.device)
+    if out is None:
+        out_s = torch.empty((nq, kout), dtype=torch.float32, device=scores.device)
+        out_i = torch.empty((nq, kout), dtype=torch.int64, device=scores.device)
+        out_c = torch.empty((nq,), dtype=torch.int32, device=scores.device)
+    else:
+        out_s, out_i, out_c = out
+        if (tuple(out_s.shape) != (nq, kout) or tuple(out_i.shape) != (nq, kout) or out_c.numel() != nq or out_s.dtype != torch.float32
+                or out_i.dtype != torch.int64 or out_c.dtype != torch.int32
+                or not (out_s.is_contiguous() and out_i.is_contiguous() and out_c.is_contiguous())):
+            raise MerizoHipError("topk_drop_ranges: out must be contiguous (float32 [nq,kout], int64 [nq,kout], int32 [nq]) tensors")
+    with _on(scores, idx, lo, hi, out_s, out_i, out_c) as dev:
+        check(_lib.load().ms_topk_drop_ranges(ptr(scores), ptr(idx), nq, kin, ptr(lo), ptr(hi), float(min_score), int(kout),
+                                              ptr(out_s), ptr(out_i), ptr(out_c), dev.stream), "ms_topk_drop_ranges")
+    return out_s, out_i, out_c
+
+
+def topk_excluding(db, q, k: int, lo, hi, mode: int = MODE_IP_PRENORM, row_norm_bound=None, image=None,
+                   min_score: float = float("-inf"), row_offset: int = 0, lengths=None, qlen=None, mincov: float = 0.0,
+                   workspace=None, max_excluded: Optional[int] = None):
+    """Exact top-k of q against db WITHOUT the rows [lo[q], hi[q]) of each query (global row numbers, as the search
+    reports them: row_offset + row) -> (scores [nq,k], idx [nq,k], count [nq]).  The search runs with
+    k' = k + max(hi - lo) -- the prefiltered search when a row_norm_bound is given and prefilter_serves(n, nq, k', image),
+    ms_ip_topk otherwise -- and ms_topk_drop_ranges takes the excluded rows out again (exactness: the header).
+    lo / hi: int64 [nq], host arrays or tensors; max_excluded: max(hi - lo) when the caller knows it (a device tensor
+    costs a sync to find it).  min_score: also drop the entries scoring below it."""
+    torch = _lib.require_gpu()
+    nq = q.shape[0]
+    if max_excluded is None:
+        if isinstance(lo, torch.Tensor) or isinstance(hi, torch.Tensor):
+            span = torch.as_tensor(hi).to(torch.int64).cpu() - torch.as_tensor(lo).to(torch.int64).cpu()
+            max_excluded = int(span.max()) if nq else 0
+        else:
+            max_excluded = int((np.asarray(hi, dtype=np.int64) - np.asarray(lo, dtype=np.int64)).max()) if nq else 0
+    kk = int(k) + max(0, int(max_excluded))
+    n = db.shape[0]
+    if row_norm_bound is not None and prefilter_serves(n, nq, kk, image):
+        s, i = ip_topk_prefiltered(db, q, kk, float(row_norm_bound), mode=mode, row_offset=row_offset, image=image, lengths=lengths,
+                                   qlen=qlen, mincov=mincov, workspace=workspace if isinstance(workspace, PrefilterWorkspace) else None)
+    else:
+        s, i = ip_topk(db, q, kk, mode=mode, lengths=lengths, qlen=qlen, mincov=mincov, row_offset=row_offset,
+                       workspace=workspace if isinstance(workspace, TopKWorkspace) and not isinstance(workspace, PrefilterWorkspace) else None)
+    return topk_drop_ranges(s, i, lo, hi, int(k), min_score)
+
+
 class EgnnEncoder:
     """The Foldclass structure encoder on one GPU: prepared weights + positional table.
 

@@ -258,6 +258,12 @@ size_t ms_egnn_workspace_bytes(int nb, int64_t total_residues, int64_t sum_sq);
 int ms_egnn_embed(const void *prepared, const float *pe, int pe_len, const float *coords, const int32_t *offsets,
                   const int32_t *offsets_host, int nb, float *out, void *workspace, size_t workspace_bytes,
                   ms_stream_t stream);
+/* Diagnostics (tests; synchronises the device): the per-residue node features float32 [total,128] that the last ms_egnn_embed on
+ * this workspace left behind, copied to the host -- layer 0: the output of the first EGNN layer, layer 1: of the second (what the
+ * mean-pool reads).  nb, total (residues) and sum_sq (sum of N^2) must be those of that call: they fix where the blocks lie.
+ * MS_ERR_ARG on NULL pointers, a layer other than 0 / 1, or counts no batch can have (nb < 1, total < nb, sum_sq outside
+ * [total, total^2]).  Backward compatible addition: ms_version() stays 210. */
+int ms_debug_egnn_node_features(const void *workspace, int nb, int64_t total, int64_t sum_sq, int layer, float *host_out);
 
 /* ------------------------------------------------------------------ TM-align -------- */
 

@@ -80,6 +80,7 @@ SIGNATURES = {
     "ms_egnn_prepare_weights": (_int, [_vp, _vp, _vp]),
     "ms_egnn_workspace_bytes": (_sz, [_int, _i64, _i64]),
     "ms_egnn_embed": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _sz, _vp]),
+    "ms_debug_egnn_node_features": (_int, [_vp, _int, _i64, _i64, _int, _vp]),
     "ms_tmalign_workspace_bytes": (_sz, [_int, _int, _int]),
     "ms_tmalign_max_len": (_int, []),
     "ms_tmalign_batch": (_int, [_vp, _vp, _vp, _int, _vp, _int, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp]),

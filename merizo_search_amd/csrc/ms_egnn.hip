@@ -846,6 +846,19 @@ int ms_debug_egnn_stamps(unsigned long long *host, int words) {
 }
 #endif
 
+// Diagnostics for the tests (synchronises the device): the node features [total][128] the last ms_egnn_embed with this nb, total and
+// sum_sq left in its workspace -- layer 0 (the first EGNN layer's output) sits in the h1 block, layer 1 (what the pool reads) in h0.
+int ms_debug_egnn_node_features(const void *workspace, int nb, int64_t total, int64_t sum_sq, int layer, float *host_out) {
+    if (workspace == nullptr || host_out == nullptr || nb < 1 || total < nb || total >= 0x7FFFFFFF || sum_sq < total ||
+        sum_sq > total * total || (layer != 0 && layer != 1))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_egnn_node_features: NULL argument, layer not 0 / 1, or nb / total / sum_sq no batch can have");
+    const EgnnCarve cv = egnn_carve(nb, total, sum_sq / 32 + 2 * total + 1);
+    MS_HIP_CHECK(hipDeviceSynchronize());
+    MS_HIP_CHECK(hipMemcpy(host_out, (const char *)workspace + (layer == 0 ? cv.off_h1 : cv.off_h0), (size_t)total * DIM * sizeof(float),
+                           hipMemcpyDeviceToHost));
+    return MS_OK;
+}
+
 int ms_egnn_embed(const void *prepared, const float *pe, int pe_len, const float *coords, const int32_t *offsets,
                   const int32_t *offsets_host, int nb, float *out, void *workspace, size_t workspace_bytes,
                   ms_stream_t stream) {

@@ -490,6 +490,7 @@ class EgnnEncoder:
             torch.cuda.current_stream(self.device).synchronize()
         self.max_len = pe.shape[0]
         self._ws = None
+        self._last = None          # (nb, total, sum_sq) of the last embed: where its node features lie in the workspace
         self._stage = self._stage_dev = self._stage_free = None
 
     def embed(self, coords_list: Sequence[np.ndarray]):
@@ -531,7 +532,8 @@ class EgnnEncoder:
             self._stage_free = stream.record_event()
             offs_ptr = self._stage_dev.data_ptr()
             coords_ptr = offs_ptr + head
-            need = int(lib.ms_egnn_workspace_bytes(nb, total, int((lens * lens).sum())))
+            sum_sq = int((lens * lens).sum())
+            need = int(lib.ms_egnn_workspace_bytes(nb, total, sum_sq))
             if self._ws is None or self._ws.numel() < need:
                 self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             out = torch.empty((nb, DIM), dtype=torch.float32, device=self.device)
@@ -539,6 +541,19 @@ class EgnnEncoder:
             check(lib.ms_egnn_embed(ptr(self.prepared), ptr(self.pe), self.max_len, coords_ptr, offs_ptr,
                                     offsets.ctypes.data, nb, ptr(out), ptr(self._ws), self._ws.numel(), stream.cuda_stream),
                   "ms_egnn_embed")
+            self._last = (nb, total, sum_sq)
+        return out
+
+    def node_features(self, layer: int) -> np.ndarray:
+        """Diagnostics (tests): the per-residue features float32 [total,128] after EGNN layer ``layer`` (0 or 1) of the LAST
+        ``embed`` call, structures concatenated in batch order.  Valid only directly after that call: the next one reuses the
+        workspace.  Synchronises the device."""
+        if self._last is None:
+            raise MerizoHipError("node_features: no embed call on this encoder yet")
+        nb, total, sum_sq = self._last
+        out = np.empty((total, DIM), dtype=np.float32)
+        check(_lib.load().ms_debug_egnn_node_features(ptr(self._ws), nb, total, sum_sq, int(layer), out.ctypes.data),
+              "ms_debug_egnn_node_features")
         return out
 
 

@@ -15,6 +15,9 @@
  * its workspace, a launch aborted half way) does not answer: the exact pass queued behind it finds the re-scoring's verdict missing
  * and TRAPS (round 6; ms_debug_prefilter_poison is the test's way in).
  *
+ * Environment: the search path has a handful of diagnostic and tuning switches (MS_LOADER_WAVE, MS_PREPASS_TILES, ...), each read once
+ * per process; DESIGN.md, "Switches of the search path", is the one table of their names, defaults and meanings.
+ *
  * Paths below are relative to /root/reference/merizo_search/programs/Foldclass/.
  */
 #ifndef MERIZO_SEARCH_AMD_H

@@ -76,8 +76,7 @@ __device__ __forceinline__ unsigned long long ms_order_key(uint2 e) {
 //   4. every survivor counts the survivors that beat it: that is its place in the answer.
 // Returns the answer (k entries in LDS, best first, empty slots (-inf, MS_IDX_NONE) last), or nullptr when the shape does
 // not fit -- fewer than k lists, no k-th head (empty lists), more than 256 survivors (ties) -- and the caller falls back
-// to the head-advance merge.  Every thread of the workgroup must call it; scratch: MS_BLOCK_MERGE_SCRATCH bytes of LDS.
-constexpr int MS_BLOCK_MERGE_SCRATCH = 8192;
+// to the head-advance merge.  Every thread of the workgroup must call it; scratch: MS_BLOCK_MERGE_SCRATCH bytes of LDS (ms_plan.h).
 __device__ __forceinline__ const uint2 *ms_block_merge(const uint2 *ent, char *scratch, int P, int k, int tid) {
     unsigned long long *hk = reinterpret_cast<unsigned long long *>(scratch);      // [256] head keys (0 past P)
     unsigned long long *cand = hk + 256;                                           // [4 k <= 256] threshold candidates

@@ -3,74 +3,48 @@
 // ms_scan_kl10.hip, ms_scan_kl32.hip, ms_scan_kl32ub.hip.  ms_search.hip holds everything else.
 #pragma once
 #include "ms_common.h"
+#include "ms_plan.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
 
 // ------------------------------------------------------------------ scan kernel --------
-// The decomposition of one scan launch: query tiles x row streams.  Computed on the host for an ordinary search (make_plan) and ON
-// THE DEVICE for the exact pass behind a prefiltered search, whose batch -- the queries whose proof failed -- is only known there
-// (the last workgroup of ms_rescore_kernel writes a ScanDevPlan, the gated scan and merge read it).
-struct ScanDevPlan {
-    int nq, nq_pad, n_qtiles, qwb, n_qgroups, n_sgroups, n_streams, rows_per_stream, P, grid;
-    int pad_[6];
-};
-__host__ __device__ inline void ms_plan_core(int64_t n, int nq, int cus, ScanDevPlan *d) {
-    d->nq = nq;
-    d->n_qtiles = (nq + 31) / 32;
-    d->qwb = d->n_qtiles >= 3 ? 4 : (d->n_qtiles == 2 ? 2 : 1);
-    d->n_qgroups = (d->n_qtiles + d->qwb - 1) / d->qwb;
-    d->nq_pad = d->n_qgroups * d->qwb * 32;
-    const int64_t tiles = (n + 31) / 32;
-    // one wave per (query tile, stream): one wave on each of the 4 * cus SIMDs
-    int64_t want = ((int64_t)4 * cus) / ((int64_t)d->n_qgroups * d->qwb);
-    if (want < 1) want = 1;
-    if (want > tiles) want = tiles > 0 ? tiles : 1;
-    const int64_t tiles_per_stream = (tiles + want - 1) / want;
-    d->rows_per_stream = (int)((tiles_per_stream > 0 ? tiles_per_stream : 1) * 32);
-    d->n_streams = (int)((n + d->rows_per_stream - 1) / d->rows_per_stream);
-    if (d->n_streams < 1) d->n_streams = 1;
-    const int spb = 4 / d->qwb;
-    d->n_sgroups = (d->n_streams + spb - 1) / spb;
-    d->P = d->qwb == 4 ? d->n_streams : d->n_sgroups;
-    d->grid = ((d->n_sgroups + 7) / 8) * 8 * d->n_qgroups;
-}
-
+// (ScanDevPlan, the decomposition of one scan launch, and ms_plan_core: ms_plan.h)
 struct ScanParams {
-    const float *db;        // [n,128]
-    int64_t n;
-    const float *qn;        // prepared queries [nq_pad,128], or the caller's [nq,128] array (inner-product mode, 16-byte aligned)
-    int nq;                 // real queries
-    int nq_pad;
-    int k;                  // ranks wanted this pass (<= 2*KL <= 64)
-    const float *inv_norm;  // [n] or NULL
-    const float *lengths;   // [n] or NULL
-    const float *qlen;      // [nq] or NULL
-    float mincov;
-    float qnorm_eps;        // > 0: qn is the caller's RAW query array; every wave L2-normalises its query tile itself (x / max(|x|, eps),
-                            //      the arithmetic of ms_normalize_rows_kernel) -- the kernels for 1-2 query tiles only
-    float qraw_eps = 0.0f;  // > 0 (fp16-image scans of the prefilter only, round 6): qn is the caller's RAW query array and every wave normalises its
-                            //      query tile in its set-up, APPROXIMATELY (q * (1 / max(|q|, eps)): a few ulp from F.normalize, far inside the scan's
-                            //      error bound; the sample pass and the scan run the same sequence) -- the exact normalisation the answer needs is
-                            //      done by the re-scoring launch, one query per workgroup (ms_rescore_body): no query-preparation launch at all
-    int debug_flags = 0;    // diagnostics (MS_PF_DEBUG, fp16-image scan): 1 = every threshold +inf (the rare path is compiled in and never taken: WRONG results)
-    int unit_rows;          // MS_MODE_COSINE_UNIT: the rows are L2-normalised already (no inv_norm array); lengths / qlen mask as usual
-    const float *ub_s;      // [nq_pad] exclusive upper bound of this pass (total order), or NULL
-    const uint32_t *ub_i;
-    const float *lb_s;      // [nq_pad] inclusive lower bound on the k-th best score (from the sample pass), or NULL
-    uint32_t *hist;         // [nq_pad][16] candidates counted per score bucket during the full pass (loader-wave form), or NULL
-    const float *hstep;     // [nq_pad] bucket width of a query (bucket j starts at lb + j * step); 0 = no histogram for it
-    int max_tiles;          // > 0: sample pass, every stream stops after this many tiles
+    const float *db = nullptr;        // [n,128]
+    int64_t n = 0;
+    const float *qn = nullptr;        // prepared queries [nq_pad,128], or the caller's [nq,128] array (inner-product mode, 16-byte aligned)
+    int nq = 0;                       // real queries
+    int nq_pad = 0;
+    int k = 0;                        // ranks wanted this pass (<= 2*KL <= 64)
+    const float *inv_norm = nullptr;  // [n] or NULL
+    const float *lengths = nullptr;   // [n] or NULL
+    const float *qlen = nullptr;      // [nq] or NULL
+    float mincov = 0.0f;
+    float qnorm_eps = 0.0f;           // > 0: qn is the caller's RAW query array; every wave L2-normalises its query tile itself (x / max(|x|, eps),
+                                      //      the arithmetic of ms_normalize_rows_kernel) -- the kernels for 1-2 query tiles only
+    float qraw_eps = 0.0f;            // > 0 (fp16-image scans of the prefilter only, round 6): qn is the caller's RAW query array and every wave normalises its
+                                      //      query tile in its set-up, APPROXIMATELY (q * (1 / max(|q|, eps)): a few ulp from F.normalize, far inside the scan's
+                                      //      error bound; the sample pass and the scan run the same sequence) -- the exact normalisation the answer needs is
+                                      //      done by the re-scoring launch, one query per workgroup (ms_rescore_body): no query-preparation launch at all
+    int debug_flags = 0;              // diagnostics (MS_PF_DEBUG, fp16-image scan): 1 = every threshold +inf (the rare path is compiled in and never taken: WRONG results)
+    int unit_rows = 0;                // MS_MODE_COSINE_UNIT: the rows are L2-normalised already (no inv_norm array); lengths / qlen mask as usual
+    const float *ub_s = nullptr;      // [nq_pad] exclusive upper bound of this pass (total order), or NULL
+    const uint32_t *ub_i = nullptr;
+    const float *lb_s = nullptr;      // [nq_pad] inclusive lower bound on the k-th best score (from the sample pass), or NULL
+    uint32_t *hist = nullptr;         // [nq_pad][16] candidates counted per score bucket during the full pass (loader-wave form), or NULL
+    const float *hstep = nullptr;     // [nq_pad] bucket width of a query (bucket j starts at lb + j * step); 0 = no histogram for it
+    int max_tiles = 0;                // > 0: sample pass, every stream stops after this many tiles
     // A handful of queries (1-2 query tiles, ms_ip_topk only): the LAST workgroup of a query group to finish merges the lists
     // inside the scan launch -- final results straight into fin_s / fin_i, no merge launch (NULL: off)
-    float *fin_s;
-    int64_t *fin_i;
-    int64_t fin_row_offset;
-    int fin_stride;
-    const int *fin_qmap = nullptr;   // ... of query q of the batch into output row fin_qmap[q] (the exact pass behind a prefiltered search of a handful of queries)
-    int prefilter = 0;      // loader-wave form only: score with three bf16 matrix instructions on the split operands (approximate scores;
-                            // the caller re-scores the survivors exactly: ms_ip_topk_prefiltered)
+    float *fin_s = nullptr;
+    int64_t *fin_i = nullptr;
+    int64_t fin_row_offset = 0;
+    int fin_stride = 0;
+    const int *fin_qmap = nullptr;    // ... of query q of the batch into output row fin_qmap[q] (the exact pass behind a prefiltered search of a handful of queries)
+    int prefilter = 0;                // loader-wave form only: score with three bf16 matrix instructions on the split operands (approximate scores;
+                                      // the caller re-scores the survivors exactly: ms_ip_topk_prefiltered)
     const ScanDevPlan *dev_plan = nullptr;   // ms_scan_kernel only: nq, the streams and the grid come from device memory (exact pass
                                              // over the flagged queries of a prefiltered search); workgroups past its grid return at once
     const void *pf_image = nullptr;   // prefilter, ms_scan_pf.h / ms_scan_pf16.h: the image of db (ms_pf_build_image), or NULL (split in registers)
@@ -82,18 +56,18 @@ struct ScanParams {
     int qpw = 1;                      // ... and the waves per workgroup of that kernel, one query tile each, in fours (1: 4 waves, 2: 8)
     const uint32_t *gate = nullptr;   // NULL, or: the launch does nothing unless *gate == gate_epoch (the exact pipeline behind a
     uint32_t gate_epoch = 0;          // prefiltered search runs only when the prefilter could not prove its answer)
-    uint32_t *ticket;       // [n_qgroups] arrival counters in library-owned memory, zero between launches (the last arriver resets its counter)
-    float *part_s;          // [nq_pad][k][P]  rank-major per query, P partial lists
-    uint32_t *part_i;
-    int rows_per_stream;    // multiple of 32
-    int n_streams;          // row streams (one wave each per query tile)
-    int n_qtiles;           // 32-query tiles
-    int qwb;                // query tiles per workgroup: 4, 2 or 1 (the other 4/qwb waves take other streams)
-    int n_qgroups;
-    int n_sgroups;          // stream groups = workgroups per query group
-    int P;                  // partial lists per query written by this launch
+    uint32_t *ticket = nullptr;       // [n_qgroups] arrival counters in library-owned memory, zero between launches (the last arriver resets its counter)
+    float *part_s = nullptr;          // [nq_pad][k][P]  rank-major per query, P partial lists
+    uint32_t *part_i = nullptr;
+    int rows_per_stream = 0;          // multiple of 32
+    int n_streams = 0;                // row streams (one wave each per query tile)
+    int n_qtiles = 0;                 // 32-query tiles
+    int qwb = 0;                      // query tiles per workgroup: 4, 2 or 1 (the other 4/qwb waves take other streams)
+    int n_qgroups = 0;
+    int n_sgroups = 0;                // stream groups = workgroups per query group
+    int P = 0;                        // partial lists per query written by this launch
 #ifdef MS_STAMP
-    unsigned long long *stamps;   // diagnostic builds only: per compute wave {cycles, 100 MHz ticks, tiles, 0}
+    unsigned long long *stamps = nullptr;   // diagnostic builds only: per compute wave {cycles, 100 MHz ticks, tiles, 0}
 #endif
 };
 
@@ -1786,32 +1760,13 @@ template <int KL, bool AUX>
 __global__ __launch_bounds__(256, 1) void ms_scan_sample_kernel(const ScanParams p) { ms_scan_body<KL, AUX, false, true>(p); }
 
 // ------------------------------------------------------------------ launch plan + launch templates
-struct ScanPlan {
-    int n_qtiles, qwb, n_qgroups, nq_pad, nq_real;
-    int k_pass;            // ranks per pass (<= 64)
-    int kl;                // list entries per lane: smallest of {5,10,32} with 2*kl >= k_pass
-    int rows_per_stream, n_streams, n_sgroups, P;
-    int grid;
-    int prepass_tiles;     // tiles per stream scanned by the sample pass (0 = no sample pass)
-    int qpw;               // split-image prefilter scan (ms_scan_pf.h): query tiles per wave (0: any other kernel)
-    int list_sm;           // the scan of this plan writes stream-major lists (the image scans; the loader-wave kernel when P <= 256 and the block merge takes them)
-    size_t lds_bytes;
-    // workspace carve (byte offsets)
-    size_t off_qn, off_inv, off_part_s, off_part_i, off_ub_s, off_ub_i, off_lb_s, off_lb_i, off_scr_s, off_scr_i, off_hist, off_hstep, off_prog, total;
-};
-
-inline int loader_wave_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_LOADER_WAVE"); v = e ? atoi(e) : 1; }
-    return v;
-}
-
+// (ScanPlan, the host's plan of a launch and of its workspace: ms_plan.h)
 template <int KL, bool AUX, bool UB>
 int launch_scan_variant(const ScanPlan &pl, const ScanParams &sp, hipStream_t st) {
     if (!UB && sp.max_tiles > 0) {      // sample pass
         MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_sample_kernel<KL, AUX>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
-        hipLaunchKernelGGL((ms_scan_sample_kernel<KL, AUX>), dim3(pl.grid), dim3(256), pl.lds_bytes, st, sp);
+        hipLaunchKernelGGL((ms_scan_sample_kernel<KL, AUX>), dim3(pl.d.grid), dim3(256), pl.lds_bytes, st, sp);
         MS_LAUNCH_CHECK("ms_scan_sample_kernel");
         return MS_OK;
     }
@@ -1822,17 +1777,17 @@ int launch_scan_variant(const ScanPlan &pl, const ScanParams &sp, hipStream_t st
             if (sp.qwb == 4 && sp.prefilter) {          // the prefilter's scan (ms_ip_topk_prefiltered)
                 MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_loader_kernel<KL, 0, false, true>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDR_LDS));
-                hipLaunchKernelGGL((ms_scan_loader_kernel<KL, 0, false, true>), dim3(pl.grid), dim3(320), LDR_LDS, st, sp);
+                hipLaunchKernelGGL((ms_scan_loader_kernel<KL, 0, false, true>), dim3(pl.d.grid), dim3(320), LDR_LDS, st, sp);
                 MS_LAUNCH_CHECK("ms_scan_loader_kernel (prefilter)");
                 return MS_OK;
             }
         }
-        if (sp.qwb == 4 && loader_wave_setting()) {     // MFMA-bound batches
+        if (sp.qwb == 4 && ms_settings().loader_wave) {     // MFMA-bound batches
 #define MS_LAUNCH_LOADER(AUXM)                                                                                           \
             constexpr int lds_ = KL >= APPEND_MIN_KL ? LDR_LDS_APPEND : LDR_LDS;       /* (the candidate buffers of the append-and-flush rare path) */ \
             MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_loader_kernel<KL, AUXM, false>),     \
                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_));                         \
-            hipLaunchKernelGGL((ms_scan_loader_kernel<KL, AUXM, false>), dim3(pl.grid), dim3(320), lds_, st, sp);
+            hipLaunchKernelGGL((ms_scan_loader_kernel<KL, AUXM, false>), dim3(pl.d.grid), dim3(320), lds_, st, sp);
             if constexpr (!AUX) { MS_LAUNCH_LOADER(0) }
             else if (sp.unit_rows) { MS_LAUNCH_LOADER(2) }
             else { MS_LAUNCH_LOADER(1) }
@@ -1843,7 +1798,7 @@ int launch_scan_variant(const ScanPlan &pl, const ScanParams &sp, hipStream_t st
     }
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_kernel<KL, AUX, UB>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
-    hipLaunchKernelGGL((ms_scan_kernel<KL, AUX, UB>), dim3(pl.grid), dim3(256), pl.lds_bytes, st, sp);
+    hipLaunchKernelGGL((ms_scan_kernel<KL, AUX, UB>), dim3(pl.d.grid), dim3(256), pl.lds_bytes, st, sp);
     MS_LAUNCH_CHECK("ms_scan_kernel");
     return MS_OK;
 }
@@ -1855,14 +1810,14 @@ int launch_sample_loader_variant(const ScanPlan &pl, const ScanParams &sp, hipSt
         if (sp.prefilter) {
             MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_loader_kernel<5, 0, true, true>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDR_LDS));
-            hipLaunchKernelGGL((ms_scan_loader_kernel<5, 0, true, true>), dim3(pl.grid), dim3(320), LDR_LDS, st, sp);
+            hipLaunchKernelGGL((ms_scan_loader_kernel<5, 0, true, true>), dim3(pl.d.grid), dim3(320), LDR_LDS, st, sp);
             MS_LAUNCH_CHECK("ms_scan_loader_kernel (prefilter sample)");
             return MS_OK;
         }
     }
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_loader_kernel<5, AUXM, true>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDR_LDS));
-    hipLaunchKernelGGL((ms_scan_loader_kernel<5, AUXM, true>), dim3(pl.grid), dim3(320), LDR_LDS, st, sp);
+    hipLaunchKernelGGL((ms_scan_loader_kernel<5, AUXM, true>), dim3(pl.d.grid), dim3(320), LDR_LDS, st, sp);
     MS_LAUNCH_CHECK("ms_scan_loader_kernel (sample)");
     return MS_OK;
 }

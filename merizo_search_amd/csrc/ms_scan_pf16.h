@@ -727,7 +727,7 @@ template <int KL, int NW, bool MASK, int NQP>
 int launch_scan_pf16(const ScanPlan &pl, const ScanParams &sp, hipStream_t st) {
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_pf16_kernel<KL, NW, false, MASK, NQP>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF2_LDS));
-    hipLaunchKernelGGL((ms_scan_pf16_kernel<KL, NW, false, MASK, NQP>), dim3(pl.grid), dim3(64 * NW), PF2_LDS, st, sp);
+    hipLaunchKernelGGL((ms_scan_pf16_kernel<KL, NW, false, MASK, NQP>), dim3(pl.d.grid), dim3(64 * NW), PF2_LDS, st, sp);
     MS_LAUNCH_CHECK("ms_scan_pf16_kernel");
     return MS_OK;
 }

@@ -9,7 +9,7 @@ template <int NW, bool MASK, int NQP>
 static int launch_sample_pf16(const ScanPlan &pl, const ScanParams &sp, hipStream_t st) {
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_pf16_kernel<5, NW, true, MASK, NQP>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF2_LDS));
-    hipLaunchKernelGGL((ms_scan_pf16_kernel<5, NW, true, MASK, NQP>), dim3(pl.grid), dim3(64 * NW), PF2_LDS, st, sp);
+    hipLaunchKernelGGL((ms_scan_pf16_kernel<5, NW, true, MASK, NQP>), dim3(pl.d.grid), dim3(64 * NW), PF2_LDS, st, sp);
     MS_LAUNCH_CHECK("ms_scan_pf16_kernel (sample)");
     return MS_OK;
 }

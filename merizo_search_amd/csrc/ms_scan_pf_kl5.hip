@@ -10,7 +10,7 @@ template <int NW, bool MASK>
 static int launch_sample_pf2(const ScanPlan &pl, const ScanParams &sp, hipStream_t st) {
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_scan_pf2_kernel<5, NW, true, MASK>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF2_LDS));
-    hipLaunchKernelGGL((ms_scan_pf2_kernel<5, NW, true, MASK>), dim3(pl.grid), dim3(64 * NW), PF2_LDS, st, sp);
+    hipLaunchKernelGGL((ms_scan_pf2_kernel<5, NW, true, MASK>), dim3(pl.d.grid), dim3(64 * NW), PF2_LDS, st, sp);
     MS_LAUNCH_CHECK("ms_scan_pf2_kernel (sample)");
     return MS_OK;
 }

@@ -717,8 +717,8 @@ __global__ __launch_bounds__(64) void ms_kway_merge_any_kernel(const float *scor
 }
 
 // ------------------------------------------------------------------ host side ----------
+// (the switches, the launch plan, the workspace carve and the rules shared below: ms_plan.h)
 namespace {
-
 
 // CU count of HIP's current device (the device the caller's tensors live on: the Python front end
 // makes it current for every call), cached per device ordinal.
@@ -733,36 +733,6 @@ int cu_count_cached() {
         cus[dev] = c;
     }
     return cus[dev];
-}
-
-
-int head_merge_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_HEAD_MERGE"); v = e ? atoi(e) : 1; }
-    return v;
-}
-
-int block_merge_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_BLOCK_MERGE"); v = e ? atoi(e) : 1; }      // diagnostics: 0 = the head-advance merge
-    return v;
-}
-
-int64_t pf_few_min_rows(int nq) {   // <= 64 queries take the fp16-image scan from this many rows: 1..32 queries (one query tile, HBM-bound) / 33..64 (two tiles)
-    static int64_t v1 = -1, v2 = -1;
-    if (v1 < 0) { const char *e = getenv("MS_PF_FEW_MIN_ROWS"); v1 = e ? atoll(e) : (int64_t)MS_PF_FEW_MIN_ROWS; }
-    if (v2 < 0) { const char *e = getenv("MS_PF_FEW2_MIN_ROWS"); v2 = e ? atoll(e) : (int64_t)MS_PF_FEW2_MIN_ROWS; }
-    return nq > 32 ? (v2 < v1 ? v2 : v1) : v1;
-}
-
-constexpr double PF_SAMPLE_COEF_DEFAULT = 1.2;   // the constant of the sample-size rule for the image scans with more than 64 queries (MS_PF_SAMPLE_COEF
-                                                 // overrides): twice the sample of the fp32 rule's 0.3 -- a visit of the rare path costs these kernels ~900 cycles per
-                                                 // half tile and a sample tile next to nothing (the sample launch is mostly fixed cost): C2 0.145 -> 0.137 ms per
-                                                 // call, every other shape within 1 % (profiles/r05_pf_sample_coef_sweep.log); few-query plans keep 0.3
-int sample_min_queries_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_SAMPLE_MIN_NQ"); v = e ? atoi(e) : 8; }
-    return v;
 }
 
 // Histogram counters of the shared bound (ScanHist) must be zero when a scan starts.  ms_sample_bound_kernel zeroes them
@@ -836,131 +806,6 @@ uint32_t sync_take_tickets(const char *mem, uint32_t count) {
         if (g_sync[i].mem == mem) { const uint32_t base = g_sync[i].pf_tickets; g_sync[i].pf_tickets = base + count; return base; }
     return 0u;
 }
-int inkernel_norm_setting() {      // MS_MODE_IP_NORMQ: up to this many queries are normalised by the scan's own waves (one batch of row loads)
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_INKERNEL_NORM_MAX_NQ"); v = e ? atoi(e) : 4; }
-    return v;
-}
-int fused_merge_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_FUSED_MERGE_MAX_NQ"); v = e ? atoi(e) : 2; }      // diagnostics: 0 = always a merge launch
-    return v;
-}
-
-int hist_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_SHARED_BOUND"); v = e ? atoi(e) : 1; }      // diagnostics: 0 = no shared bound
-    return v;
-}
-
-double sample_coef_setting() {      // diagnostics: the constant of the sample-size rule when the shared bound is on
-    static double v = -1.0;
-    if (v < 0.0) { const char *e = getenv("MS_SAMPLE_COEF"); v = e ? atof(e) : 0.05; }
-    return v;
-}
-
-int prepass_tiles_setting() {
-    static int v = -2;
-    if (v == -2) {
-        const char *e = getenv("MS_PREPASS_TILES");     // diagnostics: force a sample size (0 = no sample pass)
-        v = e ? atoi(e) : -1;
-        if (v < -1) v = -1;
-    }
-    return v;
-}
-
-// list entries per lane and pass: 5 for k <= 10, 10 for k <= 20, 16 for k <= 32, else 32 (k <= 64)
-int pick_kl(int k_pass) {
-    const int opts[4] = {5, 10, 16, 32};
-    for (int i = 0; i < 4; ++i)
-        if (2 * opts[i] >= k_pass) return opts[i];
-    return 32;
-}
-
-// qpw > 0: the plan of the split-image prefilter scan (ms_scan_pf.h): 4 waves x qpw query tiles per workgroup, one workgroup per CU
-// tile_rows: rows per tile of that kernel's image (32: split-bf16, 64: fp16); streams are whole tiles
-ScanPlan make_plan(int64_t n, int nq, int k, int cus, int qpw = 0, int tile_rows = 32) {
-    ScanPlan pl;
-    pl.nq_real = nq;
-    pl.qpw = qpw;
-    pl.k_pass = k < 64 ? k : 64;
-    pl.kl = pick_kl(pl.k_pass);
-    int64_t tiles_per_stream;
-    if (qpw == 0) {
-        ScanDevPlan d;
-        ms_plan_core(n, nq, cus, &d);      // (the same arithmetic the device runs for the exact pass behind a prefiltered search)
-        pl.n_qtiles = d.n_qtiles; pl.qwb = d.qwb; pl.n_qgroups = d.n_qgroups; pl.nq_pad = d.nq_pad; pl.rows_per_stream = d.rows_per_stream;
-        pl.n_streams = d.n_streams; pl.n_sgroups = d.n_sgroups; pl.P = d.P; pl.grid = d.grid;
-        tiles_per_stream = d.rows_per_stream / 32;
-    } else {
-        pl.n_qtiles = (nq + 31) / 32;
-        pl.qwb = 4;                        // (one list per (stream, query), as in the loader-wave form)
-        const int group_tiles = 4 * qpw;   // query tiles per workgroup
-        pl.n_qgroups = (pl.n_qtiles + group_tiles - 1) / group_tiles;
-        pl.nq_pad = pl.n_qgroups * group_tiles * 32;
-        const int64_t big_tiles = (n + tile_rows - 1) / tile_rows;
-        int64_t want = (int64_t)cus / pl.n_qgroups;
-        if (want < 1) want = 1;
-        if (want > big_tiles) want = big_tiles > 0 ? big_tiles : 1;
-        const int64_t big_per_stream = (big_tiles + want - 1) / want;
-        tiles_per_stream = big_per_stream * (tile_rows / 32);           // (in 32-row units: the sample-size rule below)
-        pl.rows_per_stream = (int)((big_per_stream > 0 ? big_per_stream : 1) * tile_rows);
-        pl.n_streams = (int)((n + pl.rows_per_stream - 1) / pl.rows_per_stream);
-        if (pl.n_streams < 1) pl.n_streams = 1;
-        pl.n_sgroups = pl.n_streams;
-        pl.P = pl.n_streams;
-        pl.grid = ((pl.n_sgroups + 7) / 8) * 8 * pl.n_qgroups;
-    }
-    pl.lds_bytes = 4 * 32768 + 4 * 1024;        // tile slots, cosine side data, in-launch bound
-    // stream-major lists: the image scans always; the loader-wave kernel (>= 3 query tiles, one pass) when the workgroup-per-query merge
-    // reads them (<= 256 lists whose [k][P] staging fits the LDS) -- MS_LIST_SM=0: rank-major as in rounds 1-4
-    {
-        static const int sm_setting = [] { const char *e = getenv("MS_LIST_SM"); return e ? atoi(e) : 1; }();
-        const size_t block_lds = (size_t)MS_BLOCK_MERGE_SCRATCH + (((size_t)pl.k_pass * pl.P + 3) & ~(size_t)3) * sizeof(uint2);
-        pl.list_sm = (qpw > 0 || (sm_setting && pl.qwb == 4 && loader_wave_setting() && k <= 64 && pl.P <= 256 && block_lds <= 156 * 1024)) ? 1 : 0;
-    }
-    // sample pass: the k-th best score of the first few tiles of every stream bounds the answer
-    // from below and prunes almost every insertion of the full pass; worth it for long streams
-    // Size of the sample: T0 tiles per stream cost T0 tile times; the insertion steps they save in the
-    // full pass fall as 1/T0 (candidates per tile = 1024 k / (streams * 32 * T0) while the sample's bound is
-    // tighter than a stream's own list).  Minimum at T0 = sqrt(c * tiles_per_stream * k / streams), c from
-    // the measured cost of a tile (2.2 us) and of a candidate (0.27 us): 3 tiles at 31 tiles per stream,
-    // 9 at 244, 17 at 977 for k = 10 and 128 streams (sweeps at 125k-16M rows x 256 queries agree).
-    // (... without the shared bound.  With it -- the loader-wave form of the fp32 scan -- the threshold follows the scan and
-    //  the sample only has to start it: the optimum moves to ~0.4 of that, 3-4 tiles at C2 instead of 9 (0.518 against 0.526 ms per
-    //  step) and 9 instead of 22 at k = 64 (0.665 against 0.719); profiles/r04_sample_size_sweep.log.  Below k = 5 the sample's best and
-    //  k-th best scores are too close for the histogram to have buckets: the old rule)
-    pl.prepass_tiles = prepass_tiles_setting();
-    if (pl.prepass_tiles < 0) {
-        static const double pf_coef = [] { const char *e = getenv("MS_PF_SAMPLE_COEF"); return e ? atof(e) : PF_SAMPLE_COEF_DEFAULT; }();
-        const double c = (qpw == 0 && pl.qwb == 4 && pl.k_pass >= 5 && loader_wave_setting() && hist_setting()) ? sample_coef_setting() : (qpw > 0 && nq > 64 ? pf_coef : 0.3);      // (the split-image
-                                     // scan only appends between flushes: its thresholds move with the shared bound alone, and it wants the larger sample)
-        const double t0 = sqrt(c * (double)tiles_per_stream * ((double)pl.k_pass / 10.0) * (128.0 / (double)pl.n_streams));
-        pl.prepass_tiles = t0 < 1.0 ? 1 : (t0 > 32.0 ? 32 : (int)(t0 + 0.5));
-    }
-    if (tiles_per_stream < 8 * (int64_t)pl.prepass_tiles) pl.prepass_tiles = (int)(tiles_per_stream / 8);
-    // short streams / few queries: few insertions anyway -- except in the image scans of the prefilter, whose lists only take candidates at
-    // a flush and whose thresholds come from the sample and the shared bound alone: without a sample every tile visits the rare path
-    // until the first flush (one query over 1M rows: 158 us against 62 with a sample)
-    if (tiles_per_stream < 12 || k > 64 || (qpw == 0 && nq < sample_min_queries_setting())) pl.prepass_tiles = 0;
-    if (qpw > 0 && tile_rows == 64) pl.prepass_tiles = (pl.prepass_tiles + 1) / 2;                     // (counted in the kernel's own tiles)
-    size_t off = 0;
-    pl.off_qn = off;      off += ms_align_up((size_t)pl.nq_pad * MS_DIM * sizeof(float), 256);
-    pl.off_inv = off;     off += ms_align_up((size_t)(n > 0 ? n : 1) * sizeof(float), 256);
-    pl.off_part_s = off;  off += ms_align_up((size_t)pl.P * pl.nq_pad * pl.k_pass * sizeof(float), 256);
-    pl.off_part_i = off;  off += ms_align_up((size_t)pl.P * pl.nq_pad * pl.k_pass * sizeof(uint32_t), 256);
-    pl.off_ub_s = off;    off += ms_align_up((size_t)pl.nq_pad * sizeof(float), 256);
-    pl.off_ub_i = off;    off += ms_align_up((size_t)pl.nq_pad * sizeof(uint32_t), 256);
-    pl.off_lb_s = off;    off += ms_align_up((size_t)pl.nq_pad * sizeof(float), 256);
-    pl.off_lb_i = off;    off += ms_align_up((size_t)pl.nq_pad * sizeof(uint32_t), 256);
-    pl.off_scr_s = off;   off += ms_align_up((size_t)pl.nq_pad * pl.k_pass * sizeof(float), 256);
-    pl.off_scr_i = off;   off += ms_align_up((size_t)pl.nq_pad * pl.k_pass * sizeof(int64_t), 256);
-    pl.off_hist = off;    off += ms_align_up((size_t)pl.nq_pad * 16 * sizeof(uint32_t), 256);
-    pl.off_hstep = off;   off += ms_align_up((size_t)pl.nq_pad * sizeof(float), 256);
-    pl.off_prog = off;    off += qpw > 0 ? ms_align_up((size_t)pl.n_streams * 64, 256) : 0;      // progress words of the image scan's workgroups
-    pl.total = off;
-    return pl;
-}
 
 int check_search_args(const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm,
                       const float *lengths, const float *qlen) {
@@ -980,54 +825,68 @@ int check_search_args(const float *db, int64_t n, const float *q, int nq, int k,
     return MS_OK;
 }
 
+// The opening of the four fp32 entry points: argument check, the plan of the call, workspace check.  out_scores / out_idx are
+// looked at where the stage writes results (ms_ip_topk, ms_ip_topk_finish -- which takes no rows or queries and checks its own few)
+enum Stage { WHOLE, PREPARE, SCAN, FINISH };
+int open_search(Stage stage, const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm, const float *lengths,
+                const float *qlen, const float *out_scores, const int64_t *out_idx, const void *workspace, size_t workspace_bytes, ScanPlan *pl) {
+    static const char *const names[] = {"ms_ip_topk", "ms_ip_topk_prepare", "ms_ip_topk_scan", "ms_ip_topk_finish"};
+    const char *who = names[stage];
+    if (stage == FINISH) {
+        if (k < 1 || k > 64 || nq < 1 || out_scores == nullptr || out_idx == nullptr) MS_FAIL(MS_ERR_ARG, "%s: bad arguments", who);
+    } else {
+        const int rc = check_search_args(db, n, q, nq, k, mode, inv_norm, lengths, qlen);
+        if (rc) return rc;
+        if (stage == WHOLE && (out_scores == nullptr || out_idx == nullptr)) MS_FAIL(MS_ERR_ARG, "%s: NULL outputs", who);
+        if (stage != WHOLE && k > 64) MS_FAIL(MS_ERR_ARG, "%s: k <= 64 only (use ms_ip_topk)", who);
+    }
+    *pl = make_plan(ms_settings(), cu_count_cached(), n, nq, k);
+    if (workspace == nullptr || workspace_bytes < pl->total) MS_FAIL(MS_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, pl->total);
+    return MS_OK;
+}
+
 int launch_scan(const ScanPlan &pl, const ScanParams &sp, hipStream_t st) {
-    if (sp.prefilter && sp.pf_image != nullptr && sp.pf_format != MS_PF_BF16X3) {      // the prefilter's scan over the fp16 image
-        if (pick_kl(sp.k) == 5) return ms_launch_scan_pf16_kl5(pl, sp, st);
-        if (pick_kl(sp.k) == 10) return ms_launch_scan_pf16_kl10(pl, sp, st);
-        if (pick_kl(sp.k) == 16) return ms_launch_scan_pf16_kl16(pl, sp, st);
-        return ms_launch_scan_pf16_kl32(pl, sp, st);
-    }
-    if (sp.prefilter && sp.pf_image != nullptr) {                  // the prefilter's scan over the split-bf16 image
-        if (pick_kl(sp.k) == 5) return ms_launch_scan_pf2_kl5(pl, sp, st);
-        if (pick_kl(sp.k) == 10) return ms_launch_scan_pf2_kl10(pl, sp, st);
-        if (pick_kl(sp.k) == 16) return ms_launch_scan_pf2_kl16(pl, sp, st);
-        return ms_launch_scan_pf2_kl32(pl, sp, st);
-    }
-    if (sp.ub_s != nullptr) return ms_launch_scan_kl32ub(pl, sp, st);
-    if (pick_kl(sp.k) == 5) return ms_launch_scan_kl5(pl, sp, st);
-    if (pick_kl(sp.k) == 10) return ms_launch_scan_kl10(pl, sp, st);
-    if (pick_kl(sp.k) == 16) return ms_launch_scan_kl16(pl, sp, st);
-    return ms_launch_scan_kl32(pl, sp, st);
+    typedef int (*Launch)(const ScanPlan &, const ScanParams &, hipStream_t);
+    // one row per kernel family -- the fp32 scan, the prefilter's scan over the split-bf16 image, the one over the fp16 image --
+    // one column per list length (MS_KL)
+    static const Launch table[3][4] = {
+        {ms_launch_scan_kl5, ms_launch_scan_kl10, ms_launch_scan_kl16, ms_launch_scan_kl32},
+        {ms_launch_scan_pf2_kl5, ms_launch_scan_pf2_kl10, ms_launch_scan_pf2_kl16, ms_launch_scan_pf2_kl32},
+        {ms_launch_scan_pf16_kl5, ms_launch_scan_pf16_kl10, ms_launch_scan_pf16_kl16, ms_launch_scan_pf16_kl32}};
+    const bool image = sp.prefilter && sp.pf_image != nullptr;
+    if (!image && sp.ub_s != nullptr) return ms_launch_scan_kl32ub(pl, sp, st);
+    return table[!image ? 0 : (is_f16_image(sp.pf_image, sp.pf_format) ? 2 : 1)][pick_kl_index(sp.k)](pl, sp, st);
 }
 
 // dp / qmap: the merge behind the exact pass over a prefiltered search's flagged queries -- the list count comes from the device
-// plan (pl.P is then its upper bound), query q of the compacted batch is output row qmap[q]
+// plan (pl.d.P is then its upper bound), query q of the compacted batch is output row qmap[q]
 int launch_merge(const ScanPlan &pl, const ScanParams &sp, int nq, int kp, int64_t row_offset, float *out_s,
                  int64_t *out_i, int out_stride, int col0, float *ub_s, uint32_t *ub_i, hipStream_t st,
                  const ScanDevPlan *dp = nullptr, const int *qmap = nullptr, int sparse = 0, size_t sm_stride = 0) {
     const uint32_t *gate = sp.gate;
     const uint32_t gate_epoch = sp.gate_epoch;
-    if (pl.P > MERGE_MAX_P) MS_FAIL(MS_ERR_RANGE, "internal: %d partial lists exceed the merge limit", pl.P);
-    const size_t head_lds = (size_t)kp * pl.P * sizeof(uint2);
-    const size_t block_lds = (size_t)MS_BLOCK_MERGE_SCRATCH + (((size_t)kp * pl.P + 3) & ~(size_t)3) * sizeof(uint2);
-    if (block_lds <= 156 * 1024 && pl.P <= 256 && (block_merge_setting() || dp != nullptr || sm_stride != 0)) {     // the usual case: a workgroup per query
+    const int P = pl.d.P;
+    if (P > MERGE_MAX_P) MS_FAIL(MS_ERR_RANGE, "internal: %d partial lists exceed the merge limit", P);
+    const size_t head_lds = (size_t)kp * P * sizeof(uint2);
+    if (block_merge_takes(kp, P) && (ms_settings().block_merge || dp != nullptr || sm_stride != 0)) {     // the usual case: a workgroup per query
+        const size_t block_lds = block_merge_lds(kp, P);
         if (block_lds > 48 * 1024)
             MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_block_merge_kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)block_lds));
-        hipLaunchKernelGGL(ms_block_merge_kernel, dim3(nq), dim3(256), block_lds, st, sp.part_s, sp.part_i, pl.P, kp, row_offset, out_s,
+        hipLaunchKernelGGL(ms_block_merge_kernel, dim3(nq), dim3(256), block_lds, st, sp.part_s, sp.part_i, P, kp, row_offset, out_s,
                            out_i, out_stride, col0, ub_s, ub_i, gate, gate_epoch, dp, qmap, (ub_s == nullptr) ? sparse : 0, sm_stride);
         MS_LAUNCH_CHECK("ms_block_merge_kernel");
         return MS_OK;
     }
-    if (dp != nullptr) MS_FAIL(MS_ERR_RANGE, "internal: the exact pass behind the prefilter needs the block merge (P = %d, k = %d)", pl.P, kp);
-    if (sm_stride != 0) MS_FAIL(MS_ERR_RANGE, "internal: stream-major lists need the block merge (P = %d, k = %d)", pl.P, kp);
-    if (head_lds <= 128 * 1024 && head_merge_setting()) {       // k * P entries fit in LDS: one wave per query, k arg-max rounds
-        const int per = (pl.P + 63) / 64;
+    if (dp != nullptr) MS_FAIL(MS_ERR_RANGE, "internal: the exact pass behind the prefilter needs the block merge (P = %d, k = %d)", P, kp);
+    if (sm_stride != 0) MS_FAIL(MS_ERR_RANGE, "internal: stream-major lists need the block merge (P = %d, k = %d)", P, kp);
+    if (head_lds <= 128 * 1024 && ms_settings().head_merge) {       // k * P entries fit in LDS: one wave per query, k arg-max rounds
+        const int per = (P + 63) / 64;
 #define MS_HEAD_MERGE(PER)                                                                                             \
     if (head_lds > 48 * 1024)                                                                                          \
         MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_head_merge_kernel<PER>),                    \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)head_lds));                  \
-    hipLaunchKernelGGL(ms_head_merge_kernel<PER>, dim3(nq), dim3(64), head_lds, st, sp.part_s, sp.part_i, pl.P, kp,    \
+    hipLaunchKernelGGL(ms_head_merge_kernel<PER>, dim3(nq), dim3(64), head_lds, st, sp.part_s, sp.part_i, P, kp,       \
                        row_offset, out_s, out_i, out_stride, col0, ub_s, ub_i, gate, gate_epoch)
         if (per <= 1) { MS_HEAD_MERGE(1); }
         else if (per <= 2) { MS_HEAD_MERGE(2); }
@@ -1039,14 +898,12 @@ int launch_merge(const ScanPlan &pl, const ScanParams &sp, int nq, int kp, int64
         return MS_OK;
     }
     const size_t lds = ((size_t)kp * kp + kp) * sizeof(uint2);
-    hipLaunchKernelGGL(ms_partial_merge_kernel, dim3(nq), dim3(256), lds, st, sp.part_s, sp.part_i, pl.P, kp, row_offset,
+    hipLaunchKernelGGL(ms_partial_merge_kernel, dim3(nq), dim3(256), lds, st, sp.part_s, sp.part_i, P, kp, row_offset,
                        out_s, out_i, out_stride, col0, ub_s, ub_i, gate, gate_epoch);
     MS_LAUNCH_CHECK("ms_partial_merge_kernel");
     return MS_OK;
 }
 
-// ScanParams of the full pass from the workspace layout (queries prepared, inverse norms in the
-// workspace when the caller gave none)
 #ifdef MS_STAMP
 constexpr size_t MS_STAMP_WORDS = 4 * 4 * 65536;
 unsigned long long *ms_stamp_buffer() {
@@ -1069,84 +926,98 @@ extern "C" int ms_debug_stamps(unsigned long long *host, int words) {
 // own query tile (ScanParams::qnorm_eps); larger batches get the prepared copy (ms_prepare_queries_kernel, eps 1e-12).
 bool queries_used_in_place(const float *q, int mode, const ScanPlan &pl) {
     if (mode == MS_MODE_IP_PRENORM) return ((uintptr_t)q & 15) == 0;
-    if (mode == MS_MODE_IP_NORMQ) return pl.qwb < 4 && pl.nq_real <= inkernel_norm_setting() && ((uintptr_t)q & 7) == 0;
+    if (mode == MS_MODE_IP_NORMQ) return pl.d.qwb < 4 && pl.d.nq <= ms_settings().inkernel_norm_max_nq && ((uintptr_t)q & 7) == 0;
     return false;
 }
 
-void fill_scan_params(const ScanPlan &pl, const float *db, int64_t n, const float *q, int nq, const float *inv_norm, const float *lengths,
-                      const float *qlen, float mincov, char *ws, int mode, ScanParams *sp) {
-    const float *inv = inv_norm;
-    if (mode == MS_MODE_COSINE_RAW && inv == nullptr && n > 0) inv = reinterpret_cast<const float *>(ws + pl.off_inv);
-    sp->db = db; sp->n = n; sp->nq = nq; sp->nq_pad = pl.nq_pad;
-    sp->qn = queries_used_in_place(q, mode, pl) ? q : reinterpret_cast<const float *>(ws + pl.off_qn);
-    sp->qnorm_eps = (mode == MS_MODE_IP_NORMQ && queries_used_in_place(q, mode, pl)) ? 1e-12f : 0.0f;
-    sp->k = pl.k_pass;
-    sp->inv_norm = inv; sp->lengths = lengths; sp->qlen = qlen; sp->mincov = mincov;
-    sp->unit_rows = mode == MS_MODE_COSINE_UNIT ? 1 : 0;
-    sp->ub_s = nullptr; sp->ub_i = nullptr; sp->lb_s = nullptr; sp->max_tiles = 0;
-    sp->hist = nullptr; sp->hstep = nullptr;
-    sp->fin_s = nullptr; sp->fin_i = nullptr; sp->fin_row_offset = 0; sp->fin_stride = 0; sp->ticket = nullptr; sp->fin_qmap = nullptr;
-    sp->prefilter = 0; sp->gate = nullptr; sp->gate_epoch = 0; sp->pf_image = nullptr; sp->pf_format = 0; sp->qpw = pl.qpw;
-    sp->list_sm = pl.list_sm; sp->prog = nullptr; sp->prog_epoch = 0;
-    sp->part_s = reinterpret_cast<float *>(ws + pl.off_part_s);
-    sp->part_i = reinterpret_cast<uint32_t *>(ws + pl.off_part_i);
-    sp->rows_per_stream = pl.rows_per_stream; sp->n_streams = pl.n_streams; sp->n_qtiles = pl.n_qtiles;
-    sp->qwb = pl.qwb; sp->n_qgroups = pl.n_qgroups; sp->n_sgroups = pl.n_sgroups; sp->P = pl.P;
+// ScanParams of the full pass from the workspace layout (queries prepared, inverse norms in the
+// workspace when the caller gave none); everything not named here keeps its default: off
+ScanParams fill_scan_params(const ScanPlan &pl, const float *db, int64_t n, const float *q, int nq, const float *inv_norm, const float *lengths,
+                            const float *qlen, float mincov, char *ws, int mode) {
+    ScanParams sp{};
+    const ScanDevPlan &d = pl.d;
+    const bool in_place = queries_used_in_place(q, mode, pl);
+    sp.db = db; sp.n = n; sp.nq = nq; sp.nq_pad = d.nq_pad;
+    sp.qn = in_place ? q : pl.qn(ws);
+    sp.qnorm_eps = (mode == MS_MODE_IP_NORMQ && in_place) ? 1e-12f : 0.0f;
+    sp.k = pl.k_pass;
+    sp.inv_norm = (mode == MS_MODE_COSINE_RAW && inv_norm == nullptr && n > 0) ? pl.inv(ws) : inv_norm;
+    sp.lengths = lengths; sp.qlen = qlen; sp.mincov = mincov;
+    sp.unit_rows = mode == MS_MODE_COSINE_UNIT ? 1 : 0;
+    sp.qpw = pl.qpw; sp.list_sm = pl.list_sm;
+    sp.part_s = pl.part_s(ws); sp.part_i = pl.part_i(ws);
+    sp.rows_per_stream = d.rows_per_stream; sp.n_streams = d.n_streams; sp.n_qtiles = d.n_qtiles;
+    sp.qwb = d.qwb; sp.n_qgroups = d.n_qgroups; sp.n_sgroups = d.n_sgroups; sp.P = d.P;
 #ifdef MS_STAMP
-    sp->stamps = ms_stamp_buffer();
+    sp.stamps = ms_stamp_buffer();
 #endif
+    return sp;
+}
+
+// What a sample pass left in the workspace for the scan behind it: the lower bound of every query and, with `hist`, the
+// shared bound's histogram (counters zeroed by ms_sample_bound_kernel, and the bucket width it chose)
+void attach_prepass_results(const ScanPlan &pl, char *ws, ScanParams *sp, bool hist) {
+    sp->lb_s = pl.lb_s(ws);
+    if (hist) { sp->hist = pl.hist(ws); sp->hstep = pl.hstep(ws); }
+}
+
+// The counters must start at zero for EVERY scan (a second scan after one prepare would otherwise count rows twice): a staged scan
+// that does not directly follow its prepare zeroes them itself
+int zero_hist_unless_clean(const ScanPlan &pl, const ScanParams &sp, const void *workspace, int64_t n, int nq, int k, hipStream_t st) {
+    if (sp.hist != nullptr && !hist_take_clean(workspace, n, nq, k))
+        MS_HIP_CHECK(hipMemsetAsync(sp.hist, 0, (size_t)pl.d.nq_pad * 16 * sizeof(uint32_t), st));
+    return MS_OK;
 }
 
 // Sample pass: scan the first prepass_tiles tiles of every stream, merge, and leave the k-th
-// best score per query in the workspace (off_ub_s doubles as the buffer) as the lower bound
-// of the full pass.  Outputs of the merge go to scratch inside the partial-list area's tail.
+// best score per query in the workspace as the lower bound of the full pass (attach_prepass_results).
 int run_prepass(const ScanPlan &pl, ScanParams *sp, int nq, char *ws, hipStream_t st) {
     if (pl.prepass_tiles <= 0) return MS_OK;
+    const MsSettings &set = ms_settings();
+    const int P = pl.d.P, qwb = pl.d.qwb;
     ScanParams s0 = *sp;
     s0.max_tiles = pl.prepass_tiles;
     s0.lb_s = nullptr;
-    int rc = (s0.prefilter && s0.pf_image != nullptr) ? (s0.pf_format != MS_PF_BF16X3 ? ms_launch_sample_pf16(pl, s0, st) : ms_launch_sample_pf2(pl, s0, st))
-             : ((pl.qwb == 4 && loader_wave_setting()) ? ms_launch_sample_loader(pl, s0, st) : launch_scan(pl, s0, st));
+    int rc = (s0.prefilter && s0.pf_image != nullptr) ? (is_f16_image(s0.pf_image, s0.pf_format) ? ms_launch_sample_pf16(pl, s0, st) : ms_launch_sample_pf2(pl, s0, st))
+             : ((qwb == 4 && set.loader_wave) ? ms_launch_sample_loader(pl, s0, st) : launch_scan(pl, s0, st));
     if (rc) return rc;
-    float *lb = reinterpret_cast<float *>(ws + pl.off_lb_s);
     // the sample kernel leaves at most 2 entries per (query, stream) and merges the 4 / qwb streams of a workgroup: only the
     // first `ranks` entries of a list can be valid.  Their k-th largest value is the bound: no rows, no sorted list needed.
-    int ranks = (2 * (4 / pl.qwb) < s0.k) ? 2 * (4 / pl.qwb) : s0.k;
+    int ranks = (2 * (4 / qwb) < s0.k) ? 2 * (4 / qwb) : s0.k;
     // (few query tiles: a workgroup's list holds the maxima of 4 / qwb streams; the best two or so per list bound nearly as
     //  well as all eight, and the selection below reads a quarter of the values: 12 -> 5 us)
     {
-        const int enough = (s0.k + pl.P - 1) / pl.P;                 // ranks * P >= k values are needed for a bound at all
-        const int cap = 512 / pl.P > enough ? 512 / pl.P : enough;
+        const int enough = (s0.k + P - 1) / P;                 // ranks * P >= k values are needed for a bound at all
+        const int cap = 512 / P > enough ? 512 / P : enough;
         if (ranks > cap) ranks = cap > 1 ? cap : 1;
     }
-    {   // diagnostics / tuning: MS_BOUND_RANKS caps how many entries per sample list the bound selection reads (fewer = a cheaper, weaker bound)
-        static const int cap_env = [] { const char *e = getenv("MS_BOUND_RANKS"); return e ? atoi(e) : 0; }();
-        if (cap_env > 0 && cap_env < ranks && (int64_t)cap_env * pl.P >= 4 * (int64_t)s0.k) ranks = cap_env;
-    }
-    const int vpl = (ranks * pl.P + 63) / 64;
-    const size_t sm_stride = s0.list_sm ? (size_t)pl.nq_pad * s0.k : 0;       // (the image scans, and the loader-wave kernel where its merge allows, write stream-major lists)
-    if (vpl > 32 && sm_stride != 0) MS_FAIL(MS_ERR_RANGE, "internal: %d sample lists of the image scan exceed the bound selection", pl.P);
-    if (vpl <= 32) {
-        const bool hist_on = pl.qwb == 4 && loader_wave_setting() && hist_setting();
-        uint32_t *hist = hist_on ? reinterpret_cast<uint32_t *>(ws + pl.off_hist) : nullptr;
-        float *hstep = reinterpret_cast<float *>(ws + pl.off_hstep);
-#define MS_BOUND(V) hipLaunchKernelGGL(ms_sample_bound_kernel<V>, dim3(nq), dim3(64), 0, st, s0.part_s, pl.P, s0.k, ranks, lb, hist, hstep, s0.gate, s0.gate_epoch, sm_stride)
-        if (vpl <= 4) { MS_BOUND(4); }
-        else if (vpl <= 8) { MS_BOUND(8); }
-        else if (vpl <= 16) { MS_BOUND(16); }
-        else { MS_BOUND(32); }
-#undef MS_BOUND
-        MS_LAUNCH_CHECK("ms_sample_bound_kernel");
-        if (hist_on) { sp->hist = hist; sp->hstep = hstep; }
-    } else {
-        float *scratch_s = reinterpret_cast<float *>(ws + pl.off_scr_s);
-        int64_t *scratch_i = reinterpret_cast<int64_t *>(ws + pl.off_scr_i);
-        uint32_t *lb_i = reinterpret_cast<uint32_t *>(ws + pl.off_lb_i);
-        rc = launch_merge(pl, s0, nq, s0.k, 0, scratch_s, scratch_i, s0.k, 0, lb, lb_i, st);
+    // diagnostics / tuning: MS_BOUND_RANKS caps how many entries per sample list the bound selection reads (fewer = a cheaper, weaker bound)
+    if (set.bound_ranks > 0 && set.bound_ranks < ranks && (int64_t)set.bound_ranks * P >= 4 * (int64_t)s0.k) ranks = set.bound_ranks;
+    const int vpl = (ranks * P + 63) / 64;
+    const size_t sm_stride = s0.list_sm ? (size_t)pl.d.nq_pad * s0.k : 0;       // (the image scans, and the loader-wave kernel where its merge allows, write stream-major lists)
+    if (vpl > 32 && sm_stride != 0) MS_FAIL(MS_ERR_RANGE, "internal: %d sample lists of the image scan exceed the bound selection", P);
+    if (vpl > 32) {      // too many values for one wave's selection: a merge, its outputs to scratch (no histogram: nothing zeroes its counters)
+        rc = launch_merge(pl, s0, nq, s0.k, 0, pl.scr_s(ws), pl.scr_i(ws), s0.k, 0, pl.lb_s(ws), pl.lb_i(ws), st);
         if (rc) return rc;
+        attach_prepass_results(pl, ws, sp, false);
+        return MS_OK;
     }
-    sp->lb_s = lb;
+    uint32_t *hist = pl.hist_on ? pl.hist(ws) : nullptr;
+#define MS_BOUND(V) hipLaunchKernelGGL(ms_sample_bound_kernel<V>, dim3(nq), dim3(64), 0, st, s0.part_s, P, s0.k, ranks, pl.lb_s(ws), hist, pl.hstep(ws), s0.gate, s0.gate_epoch, sm_stride)
+    if (vpl <= 4) { MS_BOUND(4); }
+    else if (vpl <= 8) { MS_BOUND(8); }
+    else if (vpl <= 16) { MS_BOUND(16); }
+    else { MS_BOUND(32); }
+#undef MS_BOUND
+    MS_LAUNCH_CHECK("ms_sample_bound_kernel");
+    attach_prepass_results(pl, ws, sp, pl.hist_on);
     return MS_OK;
+}
+
+// 4 rows per 256-thread workgroup, grid-stride beyond 65536 workgroups: the row-norm kernels
+dim3 row_grid(int64_t n) {
+    const int64_t blocks = (n + 3) / 4;
+    return dim3((unsigned)(blocks < 65536 ? blocks : 65536));
 }
 
 // Prepare queries (+ inverse norms if absent) and fill ScanParams for the first pass.
@@ -1154,19 +1025,15 @@ int prepare_scan(const ScanPlan &pl, const float *db, int64_t n, const float *q,
                  const float *inv_norm, const float *lengths, const float *qlen, float mincov, char *ws,
                  hipStream_t st, ScanParams *sp) {
     if (!queries_used_in_place(q, mode, pl)) {
-        float *qn = reinterpret_cast<float *>(ws + pl.off_qn);
-        hipLaunchKernelGGL(ms_prepare_queries_kernel, dim3((pl.nq_pad + 3) / 4), dim3(256), 0, st, q, nq, pl.nq_pad,
-                           mode != MS_MODE_IP_PRENORM ? 1 : 0, mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f, qn);
+        hipLaunchKernelGGL(ms_prepare_queries_kernel, dim3((pl.d.nq_pad + 3) / 4), dim3(256), 0, st, q, nq, pl.d.nq_pad,
+                           mode != MS_MODE_IP_PRENORM ? 1 : 0, mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f, pl.qn(ws));
         MS_LAUNCH_CHECK("ms_prepare_queries_kernel");
     }
     if (mode == MS_MODE_COSINE_RAW && inv_norm == nullptr && n > 0) {
-        float *inv_ws = reinterpret_cast<float *>(ws + pl.off_inv);
-        const int64_t blocks = (n + 3) / 4;
-        hipLaunchKernelGGL(ms_row_inv_norms_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st,
-                           db, n, 1e-8f, inv_ws);
+        hipLaunchKernelGGL(ms_row_inv_norms_kernel, row_grid(n), dim3(256), 0, st, db, n, 1e-8f, pl.inv(ws));
         MS_LAUNCH_CHECK("ms_row_inv_norms_kernel");
     }
-    fill_scan_params(pl, db, n, q, nq, inv_norm, lengths, qlen, mincov, ws, mode, sp);
+    *sp = fill_scan_params(pl, db, n, q, nq, inv_norm, lengths, qlen, mincov, ws, mode);
     return MS_OK;
 }
 
@@ -1194,19 +1061,17 @@ int ms_device_pci_bus_id(char *buf, int len) {
 }
 
 void ms_small_batch_thresholds(int *fused_merge_max_nq, int *inkernel_norm_max_nq) {
-    if (fused_merge_max_nq != nullptr) *fused_merge_max_nq = fused_merge_setting();
-    if (inkernel_norm_max_nq != nullptr) *inkernel_norm_max_nq = inkernel_norm_setting();
+    if (fused_merge_max_nq != nullptr) *fused_merge_max_nq = ms_settings().fused_merge_max_nq;
+    if (inkernel_norm_max_nq != nullptr) *inkernel_norm_max_nq = ms_settings().inkernel_norm_max_nq;
 }
 int ms_prefilter_max_k(void) { return MS_PREFILTER_MAX_K; }
-int64_t ms_pf_few_min_rows(int nq) { return pf_few_min_rows(nq); }
+int64_t ms_pf_few_min_rows(int nq) { return pf_few_min_rows(ms_settings(), nq); }
 
 int ms_l2_normalize_rows(float *x, int64_t n, int d, float eps, ms_stream_t stream) {
     if (d != MS_DIM) MS_FAIL(MS_ERR_ARG, "ms_l2_normalize_rows: d must be %d (got %d)", MS_DIM, d);
     if (n < 0 || (n > 0 && x == nullptr)) MS_FAIL(MS_ERR_ARG, "ms_l2_normalize_rows: bad arguments");
     if (n == 0) return MS_OK;
-    const int64_t blocks = (n + 3) / 4;
-    hipLaunchKernelGGL(ms_normalize_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
-                       (hipStream_t)stream, x, x, n, eps);
+    hipLaunchKernelGGL(ms_normalize_rows_kernel, row_grid(n), dim3(256), 0, (hipStream_t)stream, x, x, n, eps);
     MS_LAUNCH_CHECK("ms_normalize_rows_kernel");
     return MS_OK;
 }
@@ -1215,9 +1080,7 @@ int ms_l2_normalize_rows_to(const float *x, float *y, int64_t n, int d, float ep
     if (d != MS_DIM) MS_FAIL(MS_ERR_ARG, "ms_l2_normalize_rows_to: d must be %d (got %d)", MS_DIM, d);
     if (n < 0 || (n > 0 && (x == nullptr || y == nullptr))) MS_FAIL(MS_ERR_ARG, "ms_l2_normalize_rows_to: bad arguments");
     if (n == 0) return MS_OK;
-    const int64_t blocks = (n + 3) / 4;
-    hipLaunchKernelGGL(ms_normalize_rows_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
-                       (hipStream_t)stream, x, y, n, eps);
+    hipLaunchKernelGGL(ms_normalize_rows_kernel, row_grid(n), dim3(256), 0, (hipStream_t)stream, x, y, n, eps);
     MS_LAUNCH_CHECK("ms_normalize_rows_kernel");
     return MS_OK;
 }
@@ -1226,27 +1089,22 @@ int ms_row_inv_norms(const float *x, int64_t n, int d, float eps, float *inv_nor
     if (d != MS_DIM) MS_FAIL(MS_ERR_ARG, "ms_row_inv_norms: d must be %d (got %d)", MS_DIM, d);
     if (n < 0 || (n > 0 && (x == nullptr || inv_norm == nullptr))) MS_FAIL(MS_ERR_ARG, "ms_row_inv_norms: bad arguments");
     if (n == 0) return MS_OK;
-    const int64_t blocks = (n + 3) / 4;
-    hipLaunchKernelGGL(ms_row_inv_norms_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0,
-                       (hipStream_t)stream, x, n, eps, inv_norm);
+    hipLaunchKernelGGL(ms_row_inv_norms_kernel, row_grid(n), dim3(256), 0, (hipStream_t)stream, x, n, eps, inv_norm);
     MS_LAUNCH_CHECK("ms_row_inv_norms_kernel");
     return MS_OK;
 }
 
 size_t ms_ip_topk_workspace_bytes(int64_t n, int nq, int k) {
     if (n < 0 || nq < 1 || k < 1) return 0;
-    return make_plan(n, nq, k, cu_count_cached()).total;
+    return make_plan(ms_settings(), cu_count_cached(), n, nq, k).total;
 }
 
 int ms_ip_topk_prepare(const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm,
                        const float *lengths, const float *qlen, float mincov, void *workspace, size_t workspace_bytes,
                        ms_stream_t stream) {
-    int rc = check_search_args(db, n, q, nq, k, mode, inv_norm, lengths, qlen);
+    ScanPlan pl;
+    int rc = open_search(PREPARE, db, n, q, nq, k, mode, inv_norm, lengths, qlen, nullptr, nullptr, workspace, workspace_bytes, &pl);
     if (rc) return rc;
-    if (k > 64) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_prepare: k <= 64 only (use ms_ip_topk)");
-    const ScanPlan pl = make_plan(n, nq, k, cu_count_cached());
-    if (workspace == nullptr || workspace_bytes < pl.total)
-        MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk_prepare: workspace %zu < %zu bytes", workspace_bytes, pl.total);
     ScanParams sp;
     rc = prepare_scan(pl, db, n, q, nq, mode, inv_norm, lengths, qlen, mincov, (char *)workspace, (hipStream_t)stream, &sp);
     if (rc) return rc;
@@ -1258,74 +1116,54 @@ int ms_ip_topk_prepare(const float *db, int64_t n, const float *q, int nq, int k
 int ms_ip_topk_scan(const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm,
                     const float *lengths, const float *qlen, float mincov, void *workspace, size_t workspace_bytes,
                     ms_stream_t stream) {
-    int rc = check_search_args(db, n, q, nq, k, mode, inv_norm, lengths, qlen);
+    ScanPlan pl;
+    int rc = open_search(SCAN, db, n, q, nq, k, mode, inv_norm, lengths, qlen, nullptr, nullptr, workspace, workspace_bytes, &pl);
     if (rc) return rc;
-    if (k > 64) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_scan: k <= 64 only (use ms_ip_topk)");
-    const ScanPlan pl = make_plan(n, nq, k, cu_count_cached());
-    if (workspace == nullptr || workspace_bytes < pl.total)
-        MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk_scan: workspace %zu < %zu bytes", workspace_bytes, pl.total);
     char *ws = (char *)workspace;
-    ScanParams sp;
-    // same parameters as ms_ip_topk_prepare left in the workspace (queries, inverse norms, lower bound)
-    fill_scan_params(pl, db, n, q, nq, inv_norm, lengths, qlen, mincov, ws, mode, &sp);
-    if (pl.prepass_tiles > 0) {
-        sp.lb_s = reinterpret_cast<const float *>(ws + pl.off_lb_s);
-        if (pl.qwb == 4 && loader_wave_setting() && hist_setting()) {      // as run_prepass left them
-            sp.hist = reinterpret_cast<uint32_t *>(ws + pl.off_hist);
-            sp.hstep = reinterpret_cast<const float *>(ws + pl.off_hstep);
-            // the counters must start at zero for EVERY scan (a second scan after one prepare would otherwise count rows twice)
-            if (!hist_take_clean(workspace, n, nq, k))
-                MS_HIP_CHECK(hipMemsetAsync(sp.hist, 0, (size_t)pl.nq_pad * 16 * sizeof(uint32_t), (hipStream_t)stream));
-        }
-    }
+    // same parameters as ms_ip_topk_prepare left in the workspace (queries, inverse norms, lower bound, histogram)
+    ScanParams sp = fill_scan_params(pl, db, n, q, nq, inv_norm, lengths, qlen, mincov, ws, mode);
+    if (pl.prepass_tiles > 0) attach_prepass_results(pl, ws, &sp, pl.hist_on);
+    rc = zero_hist_unless_clean(pl, sp, workspace, n, nq, k, (hipStream_t)stream);
+    if (rc) return rc;
     return launch_scan(pl, sp, (hipStream_t)stream);
 }
 
 int ms_ip_topk_finish(int64_t n, int64_t row_offset, int nq, int k, float *out_scores, int64_t *out_idx,
                       void *workspace, size_t workspace_bytes, ms_stream_t stream) {
-    if (k < 1 || k > 64 || nq < 1 || out_scores == nullptr || out_idx == nullptr)
-        MS_FAIL(MS_ERR_ARG, "ms_ip_topk_finish: bad arguments");
-    const ScanPlan pl = make_plan(n, nq, k, cu_count_cached());
-    if (workspace == nullptr || workspace_bytes < pl.total)
-        MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk_finish: workspace %zu < %zu bytes", workspace_bytes, pl.total);
-    char *ws = (char *)workspace;
-    ScanParams sp;
-    sp.part_s = reinterpret_cast<float *>(ws + pl.off_part_s);
-    sp.part_i = reinterpret_cast<uint32_t *>(ws + pl.off_part_i);
+    ScanPlan pl;
+    const int rc = open_search(FINISH, nullptr, n, nullptr, nq, k, 0, nullptr, nullptr, nullptr, out_scores, out_idx, workspace, workspace_bytes, &pl);
+    if (rc) return rc;
+    ScanParams sp{};
+    sp.part_s = pl.part_s(workspace);
+    sp.part_i = pl.part_i(workspace);
     return launch_merge(pl, sp, nq, pl.k_pass, row_offset, out_scores, out_idx, k, 0, nullptr, nullptr, (hipStream_t)stream, nullptr, nullptr, 0,
-                        pl.list_sm ? (size_t)pl.nq_pad * pl.k_pass : 0);
+                        pl.list_sm ? (size_t)pl.d.nq_pad * pl.k_pass : 0);
 }
 
 int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
                const float *inv_norm, const float *lengths, const float *qlen, float mincov, float *out_scores,
                int64_t *out_idx, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
-    int rc = check_search_args(db, n, q, nq, k, mode, inv_norm, lengths, qlen);
+    ScanPlan pl;
+    int rc = open_search(WHOLE, db, n, q, nq, k, mode, inv_norm, lengths, qlen, out_scores, out_idx, workspace, workspace_bytes, &pl);
     if (rc) return rc;
-    if (out_scores == nullptr || out_idx == nullptr) MS_FAIL(MS_ERR_ARG, "ms_ip_topk: NULL outputs");
-    const ScanPlan pl = make_plan(n, nq, k, cu_count_cached());
-    if (workspace == nullptr || workspace_bytes < pl.total)
-        MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk: workspace %zu < %zu bytes", workspace_bytes, pl.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     ScanParams sp;
     rc = prepare_scan(pl, db, n, q, nq, mode, inv_norm, lengths, qlen, mincov, ws, st, &sp);
     if (rc) return rc;
-    float *ub_s = reinterpret_cast<float *>(ws + pl.off_ub_s);
-    uint32_t *ub_i = reinterpret_cast<uint32_t *>(ws + pl.off_ub_i);
     rc = run_prepass(pl, &sp, nq, ws, st);
     if (rc) return rc;
     hist_invalidate(workspace);     // (a staged ms_ip_topk_scan on this workspace must not take the counters for clean afterwards)
-    // ceil(k / 64) passes; pass p returns ranks [64p, 64p + kp) using the last entry of pass
-    // p-1 as an exclusive upper bound in the total order.
     // a handful of queries, one pass: the scan launch merges its own lists (ms_scan_body, last workgroup of a query group)
-    char *blk = (k <= 64 && pl.qwb < 4 && nq <= fused_merge_setting() && pl.P <= 256 && (size_t)pl.k_pass * pl.P <= 4224)
+    char *blk = (k <= 64 && pl.d.qwb < 4 && nq <= ms_settings().fused_merge_max_nq && merge_fits_scan_launch(pl.k_pass, pl.d.P))
                     ? sync_block_for(ws) : nullptr;
     if (blk != nullptr) {
-        uint32_t *ticket = reinterpret_cast<uint32_t *>(blk);
-        sp.fin_s = out_scores; sp.fin_i = out_idx; sp.fin_row_offset = row_offset; sp.fin_stride = k; sp.ticket = ticket;
-        sp.k = pl.k_pass;
+        sp.fin_s = out_scores; sp.fin_i = out_idx; sp.fin_row_offset = row_offset; sp.fin_stride = k;
+        sp.ticket = reinterpret_cast<uint32_t *>(blk);
         return launch_scan(pl, sp, st);
     }
+    // ceil(k / 64) passes; pass p returns ranks [64p, 64p + kp) using the last entry of pass
+    // p-1 as an exclusive upper bound in the total order.
     for (int col0 = 0; col0 < k; col0 += 64) {
         const int kp = (k - col0) < 64 ? (k - col0) : 64;
         sp.k = kp;
@@ -1333,11 +1171,11 @@ int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, i
         rc = launch_scan(pl, sp, st);
         if (rc) return rc;
         const bool more = col0 + 64 < k;
-        rc = launch_merge(pl, sp, nq, kp, row_offset, out_scores, out_idx, k, col0, more ? ub_s : nullptr,
-                          more ? ub_i : nullptr, st, nullptr, nullptr, 0, sp.list_sm ? (size_t)pl.nq_pad * kp : 0);
+        rc = launch_merge(pl, sp, nq, kp, row_offset, out_scores, out_idx, k, col0, more ? pl.ub_s(ws) : nullptr,
+                          more ? pl.ub_i(ws) : nullptr, st, nullptr, nullptr, 0, sp.list_sm ? (size_t)pl.d.nq_pad * kp : 0);
         if (rc) return rc;
-        sp.ub_s = ub_s;
-        sp.ub_i = ub_i;
+        sp.ub_s = pl.ub_s(ws);
+        sp.ub_i = pl.ub_i(ws);
     }
     return MS_OK;
 }
@@ -1346,89 +1184,21 @@ int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, i
 // stages: 1 = queries + sample pass + bound, 2 = the scan launch, 4 = merge + exact re-scoring + the exact pass over the queries
 // whose proof failed
 namespace {
-// candidates kept per query: twice k for short lists, at least 8-16 spare entries for long ones (the proof needs the rows within the
-// error bound of the k-th best to fit; more spare entries = fewer queries for the exact pass on clustered data)
-int pf_list_len(int k) { return k <= 5 ? 10 : (k <= 10 ? 20 : (k <= 24 ? 32 : (k <= MS_PREFILTER_MAX_K ? 64 : 0))); }
-int pace_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_PF_PACE"); v = e ? atoi(e) : 1; }      // diagnostics: 0 = the query groups of a row stream run free
-    return v;
-}
-int pf_rawq_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_PF_RAWQ"); v = e ? atoi(e) : 1; }      // diagnostics: 0 = always the prepared (normalised) copy of the queries
-    return v;
-}
-int prefilter_setting() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("MS_PREFILTER"); v = e ? atoi(e) : 1; }      // diagnostics: 0 = always the fp32 scan
-    return v;
-}
 uint32_t next_epoch() {                                // never 0: the gate word starts at zero
     static std::atomic<uint32_t> e{1};
     uint32_t v = e.fetch_add(1);
     if (v == 0) v = e.fetch_add(1);
     return v;
 }
-// Workspace of a prefiltered search: [the larger of the prefilter scan's and the exact scan's plans | candidate lists (approximate
-// scores, rows) | per-query flags | the compacted batch of the exact pass: queries, bounds, lengths, map | its device plan]
-struct PfLayout {
-    ScanPlan pf, exact;
-    size_t off_as, off_ai, off_flag, off_qn_c, off_lb_c, off_qlen_c, off_qmap, off_dp, off_xs, off_xi, total;
-    int kp, exact_grid_max, exact_P_max;
-    bool ok;
-};
 bool pf_format_ok(int f) { return f == MS_PF_BF16X3 || f == MS_PF_F16X2 || f == MS_PF_F16X1; }
 float pf_err_coef(bool image, int format) {
-    if (!image || format == MS_PF_BF16X3) return MS_PF_ERR;
+    if (!is_f16_image(image, format)) return MS_PF_ERR;
     return format == MS_PF_F16X2 ? MS_PF_ERR_F16X2 : MS_PF_ERR_F16X1;
 }
-PfLayout pf_layout(int64_t n, int nq, int k, int mode, bool image, int format = MS_PF_BF16X3) {
-    PfLayout L;
-    const int cus = cu_count_cached();
-    L.kp = pf_list_len(k);
-    L.exact = make_plan(n, nq, k, cus);
-    const bool ip = mode == MS_MODE_IP_PRENORM || mode == MS_MODE_IP_NORMQ;
-    // without an image the rows are split in registers (round 3's kernel: inner-product modes only, the loader-wave form)
-    // (one or two query tiles -- the reference's own CLI regime -- are HBM-bound: over the fp16 image the scan reads half the bytes of
-    //  the fp32 rows; worth the fixed cost of the pipeline around it from a few million rows: pf_few_min_rows)
-    const bool few_ok = image && format != MS_PF_BF16X3 && n >= pf_few_min_rows(nq);
-    L.ok = prefilter_setting() && L.kp > 0 && n >= 65536 && (L.exact.qwb == 4 || few_ok) &&
-           (image ? (ip || mode == MS_MODE_COSINE_UNIT) : (ip && loader_wave_setting() != 0));
-    L.exact_grid_max = L.exact.grid; L.exact_P_max = L.exact.P;
-    if (!L.ok) { L.total = L.exact.total; L.off_as = L.off_ai = L.off_flag = L.off_qn_c = L.off_lb_c = L.off_qlen_c = L.off_qmap = L.off_dp = L.off_xs = L.off_xi = 0; return L; }
-    // two query tiles per wave (8 per workgroup) from 5 query tiles, while the lists leave room for it
-    const int qpw = image ? ((L.exact.n_qtiles >= 5 && L.kp <= 32) ? 2 : 1) : 0;
-    L.pf = make_plan(n, nq, L.kp, cus, qpw, (image && format != MS_PF_BF16X3) ? 64 : 32);
-    // the exact pass runs over 1 .. nq queries, decomposed on the device: the launch grid and the merge's LDS cover every case
-    size_t lists_max = 0;        // (its partial lists: nq_pad * P entries per rank, whichever decomposition the device picks)
-    for (int qt = 1; qt <= L.exact.n_qtiles; ++qt) {
-        ScanDevPlan d;
-        ms_plan_core(n, qt * 32 < nq ? qt * 32 : nq, cus, &d);
-        if (d.grid > L.exact_grid_max) L.exact_grid_max = d.grid;
-        if (d.P > L.exact_P_max) L.exact_P_max = d.P;
-        if ((size_t)d.nq_pad * d.P > lists_max) lists_max = (size_t)d.nq_pad * d.P;
-    }
-    if (L.exact_P_max > 256 || L.pf.P > 256 || nq >= (1 << 20)) {       // the merges behind the image scan and the exact pass stage <= 256 lists per query (a device with more than 256 CUs): ms_ip_topk
-        L.ok = false;
-        L.total = L.exact.total; L.off_as = L.off_ai = L.off_flag = L.off_qn_c = L.off_lb_c = L.off_qlen_c = L.off_qmap = L.off_dp = L.off_xs = L.off_xi = 0;
-        return L;
-    }
-    size_t off = L.pf.total > L.exact.total ? L.pf.total : L.exact.total;
-    const int nq_pad = L.pf.nq_pad > L.exact.nq_pad ? L.pf.nq_pad : L.exact.nq_pad;
-    L.off_as = off;     off += ms_align_up((size_t)nq_pad * L.kp * sizeof(float), 256);
-    L.off_ai = off;     off += ms_align_up((size_t)nq_pad * L.kp * sizeof(int64_t), 256);
-    L.off_flag = off;   off += ms_align_up((size_t)nq_pad * sizeof(uint32_t), 256);
-    L.off_qn_c = off;   off += ms_align_up((size_t)nq_pad * MS_DIM * sizeof(float), 256);
-    L.off_lb_c = off;   off += ms_align_up((size_t)nq_pad * sizeof(float), 256);
-    L.off_qlen_c = off; off += ms_align_up((size_t)nq_pad * sizeof(float), 256);
-    L.off_qmap = off;   off += ms_align_up((size_t)nq_pad * sizeof(int), 256);
-    L.off_dp = off;     off += 256;
-    L.off_xs = off;     off += ms_align_up(lists_max * L.exact.k_pass * sizeof(float), 256);
-    L.off_xi = off;     off += ms_align_up(lists_max * L.exact.k_pass * sizeof(uint32_t), 256);
-    L.total = off;
-    return L;
-}
+// A staged scan or finish (no stage 1 in the call) attaches the histogram wherever the shared bound is on.  That is NOT
+// ScanPlan::hist_on, which stage 1 goes by: the two differ over an image with MS_LOADER_WAVE=0 (diagnostics), as they always have.
+bool pf_staged_hist(const MsSettings &set) { return set.shared_bound != 0; }
+
 int pf_run(int stages, const float *db, const void *image, int format, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
            const float *lengths, const float *qlen, float mincov, float row_norm_bound, float *out_scores, int64_t *out_idx,
            void *workspace, size_t workspace_bytes, hipStream_t st) {
@@ -1436,7 +1206,8 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
     if (rc) return rc;
     if (mode == MS_MODE_COSINE_RAW) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_prefiltered: MS_MODE_COSINE_RAW is not served (normalise the rows once: MS_MODE_COSINE_UNIT)");
     if (image != nullptr && !pf_format_ok(format)) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_prefiltered: unknown pf_format %d", format);
-    const PfLayout L = pf_layout(n, nq, k, mode, image != nullptr, format);
+    const MsSettings &set = ms_settings();
+    const PfLayout L = pf_layout(set, cu_count_cached(), n, nq, k, mode, image != nullptr, format);
     if (workspace == nullptr || workspace_bytes < L.total)
         MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk_prefiltered: workspace %zu < %zu bytes", workspace_bytes, L.total);
     char *blk = L.ok && row_norm_bound > 0.0f && row_norm_bound < INFINITY ? sync_block_for(workspace) : nullptr;
@@ -1448,47 +1219,35 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
     }
     char *ws = (char *)workspace;
     const ScanPlan &pl = L.pf;
-    ScanParams sp;
+    const bool f16 = is_f16_image(image, format);
     // Raw queries over the fp16 image (MS_MODE_IP_NORMQ, MS_MODE_COSINE_UNIT; round 6): no query-preparation launch -- the sample pass and the
     // scan read the caller's array and normalise approximately in their set-up, the re-scoring launch normalises exactly (MS_PF_RAWQ=0: the
     // prepared copy as before)
-    const float rawq_eps = (image != nullptr && format != MS_PF_BF16X3 && (mode == MS_MODE_IP_NORMQ || mode == MS_MODE_COSINE_UNIT) &&
-                            ((uintptr_t)q & 15) == 0 && pf_rawq_setting()) ? (mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f) : 0.0f;
+    const float rawq_eps = (f16 && (mode == MS_MODE_IP_NORMQ || mode == MS_MODE_COSINE_UNIT) && ((uintptr_t)q & 15) == 0 && set.pf_rawq)
+                               ? (mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f) : 0.0f;
+    ScanParams sp;
+    if ((stages & 1) && rawq_eps == 0.0f) rc = prepare_scan(pl, db, n, q, nq, mode, nullptr, lengths, qlen, mincov, ws, st, &sp);
+    else sp = fill_scan_params(pl, db, n, q, nq, nullptr, lengths, qlen, mincov, ws, mode);
+    if (rc) return rc;
+    if (rawq_eps > 0.0f) { sp.qn = q; sp.qnorm_eps = 0.0f; sp.qraw_eps = rawq_eps; }
+    sp.prefilter = 1; sp.pf_image = image; sp.pf_format = format;
     if (stages & 1) {
-        if (rawq_eps > 0.0f) fill_scan_params(pl, db, n, q, nq, nullptr, lengths, qlen, mincov, ws, mode, &sp);
-        else rc = prepare_scan(pl, db, n, q, nq, mode, nullptr, lengths, qlen, mincov, ws, st, &sp);
-        if (rc) return rc;
-        if (rawq_eps > 0.0f) { sp.qn = q; sp.qnorm_eps = 0.0f; sp.qraw_eps = rawq_eps; }
-        sp.prefilter = 1; sp.pf_image = image; sp.pf_format = format;
         rc = run_prepass(pl, &sp, nq, ws, st);
         if (rc) return rc;
         if (sp.hist != nullptr) hist_mark_clean(workspace, n, nq, L.kp);
+        if ((stages & 2) && sp.hist != nullptr) (void)hist_take_clean(workspace, n, nq, L.kp);
     } else {
-        fill_scan_params(pl, db, n, q, nq, nullptr, lengths, qlen, mincov, ws, mode, &sp);
-        if (rawq_eps > 0.0f) { sp.qn = q; sp.qnorm_eps = 0.0f; sp.qraw_eps = rawq_eps; }
-        sp.prefilter = 1; sp.pf_image = image; sp.pf_format = format;
-        if (pl.prepass_tiles > 0) {
-            sp.lb_s = reinterpret_cast<const float *>(ws + pl.off_lb_s);
-            if (hist_setting()) {
-                sp.hist = reinterpret_cast<uint32_t *>(ws + pl.off_hist);
-                sp.hstep = reinterpret_cast<const float *>(ws + pl.off_hstep);
-                if ((stages & 2) && !hist_take_clean(workspace, n, nq, L.kp))
-                    MS_HIP_CHECK(hipMemsetAsync(sp.hist, 0, (size_t)pl.nq_pad * 16 * sizeof(uint32_t), st));
-            }
-        }
+        if (pl.prepass_tiles > 0) attach_prepass_results(pl, ws, &sp, pf_staged_hist(set));
+        if (stages & 2) rc = zero_hist_unless_clean(pl, sp, workspace, n, nq, L.kp, st);
+        if (rc) return rc;
     }
-    if ((stages & 1) && (stages & 2) && sp.hist != nullptr) (void)hist_take_clean(workspace, n, nq, L.kp);
-    sp.k = pl.k_pass;
-    {
-        static const int dbg = [] { const char *e = getenv("MS_PF_DEBUG"); return e ? atoi(e) : 0; }();
-        sp.debug_flags = dbg;
-    }
+    sp.debug_flags = set.pf_debug;
     if (stages & 2) {
-        if (image != nullptr && format != MS_PF_BF16X3 && pl.n_qgroups >= 2 && pl.n_qgroups <= 16 && pace_setting()) {
+        if (f16 && pl.d.n_qgroups >= 2 && pl.d.n_qgroups <= 16 && set.pf_pace) {
             // several query groups walk every row stream: they pace each other through progress words (ms_scan_pf16.h) so that a tile
             // one of them fetched is still in the XCD's L2 when the others want it
             static std::atomic<uint32_t> pace_epoch{1};
-            sp.prog = reinterpret_cast<uint32_t *>(ws + pl.off_prog);
+            sp.prog = pl.prog(ws);
             sp.prog_epoch = pace_epoch.fetch_add(1) & 0xFFu;
         }
         rc = launch_scan(pl, sp, st);
@@ -1496,48 +1255,39 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
     }
     if (stages & 4) {
         if (out_scores == nullptr || out_idx == nullptr) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_prefiltered: NULL outputs");
-        float *as = reinterpret_cast<float *>(ws + L.off_as);
-        int64_t *ai = reinterpret_cast<int64_t *>(ws + L.off_ai);
         uint32_t *gate = reinterpret_cast<uint32_t *>(blk + 256);
         const uint32_t epoch = next_epoch();
         const ScanPlan &px = L.exact;
-        uint32_t *flag = reinterpret_cast<uint32_t *>(ws + L.off_flag);
-        float *qn_c = reinterpret_cast<float *>(ws + L.off_qn_c), *lb_c = reinterpret_cast<float *>(ws + L.off_lb_c);
-        float *qlen_c = reinterpret_cast<float *>(ws + L.off_qlen_c);
-        int *qmap = reinterpret_cast<int *>(ws + L.off_qmap);
-        ScanDevPlan *dp = reinterpret_cast<ScanDevPlan *>(ws + L.off_dp);
         PfCompact cp;
-        cp.qn_c = qn_c; cp.lb_c = lb_c; cp.qlen_c = qlen_c; cp.qmap = qmap; cp.dp = dp; cp.gate = gate; cp.epoch = epoch; cp.n = n;
+        cp.qn_c = L.qn_c(ws); cp.lb_c = L.lb_c(ws); cp.qlen_c = L.qlen_c(ws); cp.qmap = L.qmap(ws); cp.dp = L.dp(ws); cp.gate = gate; cp.epoch = epoch; cp.n = n;
         cp.cus = cu_count_cached(); cp.nq = nq; cp.ticket_base = sync_take_tickets(blk, (uint32_t)nq);
         // ONE launch: merge of the per-stream candidate lists (sparse; stream-major behind the image scans) + exact re-scoring + proof + compaction
         PfRescore ra;
-        ra.db = db; ra.qn = sp.qn; ra.as = as; ra.ai = ai; ra.lengths = lengths; ra.qlen = qlen; ra.out_s = out_scores; ra.out_i = out_idx; ra.flag = flag;
+        ra.db = db; ra.qn = sp.qn; ra.as = L.as(ws); ra.ai = L.ai(ws); ra.lengths = lengths; ra.qlen = qlen; ra.out_s = out_scores; ra.out_i = out_idx; ra.flag = L.flag(ws);
         ra.row_offset = row_offset; ra.err_coef = pf_err_coef(image != nullptr, format) * row_norm_bound; ra.mincov = mincov;
         ra.q_eps = rawq_eps;
-        ra.k = k; ra.kp = L.kp; ra.fp16_range = (image != nullptr && format != MS_PF_BF16X3) ? 1 : 0; ra.cp = cp;
-        const size_t block_lds = (size_t)MS_BLOCK_MERGE_SCRATCH + (((size_t)L.kp * pl.P + 3) & ~(size_t)3) * sizeof(uint2);
-        if (block_lds > 156 * 1024 || pl.P > 256) MS_FAIL(MS_ERR_RANGE, "internal: %d candidate lists of %d entries exceed the merge", pl.P, L.kp);
+        ra.k = k; ra.kp = L.kp; ra.fp16_range = f16 ? 1 : 0; ra.cp = cp;
+        if (!block_merge_takes(L.kp, pl.d.P)) MS_FAIL(MS_ERR_RANGE, "internal: %d candidate lists of %d entries exceed the merge", pl.d.P, L.kp);
+        const size_t block_lds = block_merge_lds(L.kp, pl.d.P);
         if (block_lds > 48 * 1024)
             MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_merge_rescore_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)block_lds));
-        hipLaunchKernelGGL(ms_merge_rescore_kernel, dim3(nq), dim3(256), block_lds, st, sp.part_s, sp.part_i, pl.P, as, ai,
-                           sp.list_sm ? (size_t)pl.nq_pad * L.kp : (size_t)0, ra);
+        hipLaunchKernelGGL(ms_merge_rescore_kernel, dim3(nq), dim3(256), block_lds, st, sp.part_s, sp.part_i, pl.d.P, L.as(ws), L.ai(ws),
+                           sp.list_sm ? (size_t)pl.d.nq_pad * L.kp : (size_t)0, ra);
         MS_LAUNCH_CHECK("ms_merge_rescore_kernel");
         // The exact pass, for the flagged queries ONLY (the reference's semantics are per query: dbsearch.py:234-242): an fp32 scan
         // and a merge over the compacted batch, decomposed on the device (ScanDevPlan), both returning at once when no query was
         // flagged.  No sample pass: the k-th best exact score among a query's candidates is already a lower bound on its k-th
         // best (k rows score at least that), and a tight one.  Always the kernels for any number of query tiles (ms_scan_kernel).
-        ScanParams sx;
-        fill_scan_params(px, db, n, q, nq, nullptr, lengths, lengths != nullptr ? qlen_c : nullptr, mincov, ws, mode, &sx);
-        sx.qn = qn_c;                        // (prepared -- normalised where the mode asks for it -- by the prefilter's stage 1)
+        ScanParams sx = fill_scan_params(px, db, n, q, nq, nullptr, lengths, lengths != nullptr ? cp.qlen_c : nullptr, mincov, ws, mode);
+        sx.qn = cp.qn_c;                     // (prepared -- normalised where the mode asks for it -- by the prefilter's stage 1)
         sx.qnorm_eps = 0.0f;
         sx.gate = gate; sx.gate_epoch = epoch;
-        sx.lb_s = lb_c;
-        sx.k = px.k_pass;
-        sx.dev_plan = dp;
-        sx.part_s = reinterpret_cast<float *>(ws + L.off_xs);
-        sx.part_i = reinterpret_cast<uint32_t *>(ws + L.off_xi);
+        sx.lb_s = cp.lb_c;
+        sx.dev_plan = cp.dp;
+        sx.part_s = L.xs(ws);
+        sx.part_i = L.xi(ws);
         ScanPlan pg = px;
-        pg.grid = L.exact_grid_max; pg.P = L.exact_P_max; pg.qwb = 1;     // (qwb = 1: routes to ms_scan_kernel, whose decomposition is the device plan's)
+        pg.d.grid = L.exact_grid_max; pg.d.P = L.exact_P_max; pg.d.qwb = 1;     // (qwb = 1: routes to ms_scan_kernel, whose decomposition is the device plan's)
         sx.qwb = 1;
         sx.list_sm = 0;                      // (ms_scan_kernel writes rank-major lists)
         // A handful of queries (the reference's own CLI regime over the fp16 image of a large database; round 6): the exact pass merges
@@ -1546,16 +1296,15 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
         // merge them one after the other (4.4 us each) while 255 others have finished; the merge launch stays.
         // (up to 8 queries whatever ms_ip_topk's own threshold is: the serial merge only runs for queries that were flagged -- rare -- while the
         //  second launch costs every call; MS_PF_FUSE_EXACT_MAX_NQ overrides)
-        static const int fuse_max = [] { const char *e = getenv("MS_PF_FUSE_EXACT_MAX_NQ"); return e ? atoi(e) : 8; }();
-        const bool fuse_exact = nq <= fuse_max && L.exact_P_max <= 256 && (size_t)px.k_pass * L.exact_P_max <= 4224;
+        const bool fuse_exact = nq <= set.pf_fuse_exact_max_nq && merge_fits_scan_launch(px.k_pass, L.exact_P_max);
         if (fuse_exact) {
-            sx.fin_s = out_scores; sx.fin_i = out_idx; sx.fin_row_offset = row_offset; sx.fin_stride = k; sx.fin_qmap = qmap;
+            sx.fin_s = out_scores; sx.fin_i = out_idx; sx.fin_row_offset = row_offset; sx.fin_stride = k; sx.fin_qmap = cp.qmap;
             sx.ticket = reinterpret_cast<uint32_t *>(blk);
         }
         rc = launch_scan(pg, sx, st);
         if (rc) return rc;
         if (!fuse_exact) {
-            rc = launch_merge(pg, sx, nq, px.k_pass, row_offset, out_scores, out_idx, k, 0, nullptr, nullptr, st, dp, qmap);
+            rc = launch_merge(pg, sx, nq, px.k_pass, row_offset, out_scores, out_idx, k, 0, nullptr, nullptr, st, cp.dp, cp.qmap);
             if (rc) return rc;
         }
     }
@@ -1587,12 +1336,7 @@ int ms_pf_build_image(const float *db, int64_t n, int pf_format, float row_norm_
 
 size_t ms_ip_topk_prefiltered_workspace_bytes(int64_t n, int nq, int k) {
     if (n < 0 || nq < 1 || k < 1) return 0;
-    size_t m = make_plan(n, nq, k, cu_count_cached()).total;
-    for (int image = 0; image < 3; ++image) {       // no image, split-bf16 image (32-row tiles), fp16 image (64-row tiles)
-        const size_t a = pf_layout(n, nq, k, image ? MS_MODE_COSINE_UNIT : MS_MODE_IP_PRENORM, image != 0, image == 2 ? MS_PF_F16X2 : MS_PF_BF16X3).total;
-        if (a > m) m = a;
-    }
-    return m;
+    return pf_workspace_bytes(ms_settings(), cu_count_cached(), n, nq, k);
 }
 
 int ms_ip_topk_prefiltered(const float *db, const void *pf_image, int pf_format, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
@@ -1645,42 +1389,39 @@ int ms_debug_prefilter_poison(void *workspace, unsigned int slot_counter, unsign
 // Diagnostics (tools/pf_try.py): the candidate lists (approximate scores, rows) the last prefiltered search left in the workspace.
 int ms_debug_prefilter_lists(void *workspace, int64_t n, int nq, int k, int image, float *as_host, int64_t *ai_host, int *kp_out) {
     // image: 0 = none, 1 = split-bf16 image, 2 = fp16 image (the layouts differ in their tile size only)
-    const PfLayout L = pf_layout(n, nq, k, MS_MODE_IP_PRENORM, image != 0, image == 2 ? MS_PF_F16X2 : MS_PF_BF16X3);
+    const PfLayout L = pf_layout(ms_settings(), cu_count_cached(), n, nq, k, MS_MODE_IP_PRENORM, image != 0, image == 2 ? MS_PF_F16X2 : MS_PF_BF16X3);
     if (!L.ok || hipDeviceSynchronize() != hipSuccess) return -1;
     *kp_out = L.kp;
-    if (hipMemcpy(as_host, (char *)workspace + L.off_as, (size_t)nq * L.kp * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    if (hipMemcpy(ai_host, (char *)workspace + L.off_ai, (size_t)nq * L.kp * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(as_host, L.as(workspace), (size_t)nq * L.kp * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(ai_host, L.ai(workspace), (size_t)nq * L.kp * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
+}
+
+// S sorted lists per query, list s of each array s * stride BYTES behind list 0 -> the best k (both merge entry points)
+static int kway_merge(const char *who, bool strided, const float *scores, const int64_t *idx, int64_t score_stride_bytes, int64_t idx_stride_bytes,
+                      int S, int nq, int k, float *out_scores, int64_t *out_idx, ms_stream_t stream) {
+    if (S < 1 || nq < 1 || k < 1 || !scores || !idx || !out_scores || !out_idx)
+        MS_FAIL(MS_ERR_ARG, "%s: need S >= 1, nq >= 1, k >= 1 and non-NULL buffers (S=%d)", who, S);
+    if (strided && (score_stride_bytes % 4 != 0 || idx_stride_bytes % 8 != 0 || ((uintptr_t)idx & 7) != 0))
+        MS_FAIL(MS_ERR_ARG, "%s: strides / index pointer must keep float32 and int64 alignment", who);
+    if (S <= 64)
+        hipLaunchKernelGGL(ms_kway_merge_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
+                           score_stride_bytes, idx_stride_bytes, S, nq, k, out_scores, out_idx);
+    else
+        hipLaunchKernelGGL(ms_kway_merge_any_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
+                           score_stride_bytes, idx_stride_bytes, S, nq, k, out_scores, out_idx);
+    MS_LAUNCH_CHECK("ms_kway_merge_kernel");
+    return MS_OK;
 }
 
 int ms_topk_merge(const float *scores, const int64_t *idx, int S, int nq, int k, float *out_scores,
                   int64_t *out_idx, ms_stream_t stream) {
-    if (S < 1 || nq < 1 || k < 1 || !scores || !idx || !out_scores || !out_idx)
-        MS_FAIL(MS_ERR_ARG, "ms_topk_merge: need S >= 1, nq >= 1, k >= 1 and non-NULL buffers (S=%d)", S);
-    if (S <= 64)
-        hipLaunchKernelGGL(ms_kway_merge_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
-                           (int64_t)nq * k * 4, (int64_t)nq * k * 8, S, nq, k, out_scores, out_idx);
-    else
-        hipLaunchKernelGGL(ms_kway_merge_any_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
-                           (int64_t)nq * k * 4, (int64_t)nq * k * 8, S, nq, k, out_scores, out_idx);
-    MS_LAUNCH_CHECK("ms_kway_merge_kernel");
-    return MS_OK;
+    return kway_merge("ms_topk_merge", false, scores, idx, (int64_t)nq * k * 4, (int64_t)nq * k * 8, S, nq, k, out_scores, out_idx, stream);
 }
 
 int ms_topk_merge_strided(const float *scores, const int64_t *idx, int64_t score_stride_bytes, int64_t idx_stride_bytes,
                           int S, int nq, int k, float *out_scores, int64_t *out_idx, ms_stream_t stream) {
-    if (S < 1 || nq < 1 || k < 1 || !scores || !idx || !out_scores || !out_idx)
-        MS_FAIL(MS_ERR_ARG, "ms_topk_merge_strided: need S >= 1, nq >= 1, k >= 1 and non-NULL buffers (S=%d)", S);
-    if (score_stride_bytes % 4 != 0 || idx_stride_bytes % 8 != 0 || ((uintptr_t)idx & 7) != 0)
-        MS_FAIL(MS_ERR_ARG, "ms_topk_merge_strided: strides / index pointer must keep float32 and int64 alignment");
-    if (S <= 64)
-        hipLaunchKernelGGL(ms_kway_merge_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
-                           score_stride_bytes, idx_stride_bytes, S, nq, k, out_scores, out_idx);
-    else
-        hipLaunchKernelGGL(ms_kway_merge_any_kernel, dim3((nq + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, idx,
-                           score_stride_bytes, idx_stride_bytes, S, nq, k, out_scores, out_idx);
-    MS_LAUNCH_CHECK("ms_kway_merge_kernel");
-    return MS_OK;
+    return kway_merge("ms_topk_merge_strided", true, scores, idx, score_stride_bytes, idx_stride_bytes, S, nq, k, out_scores, out_idx, stream);
 }
 
 }  // extern "C"

@@ -84,6 +84,7 @@ def row_inv_norms(x, eps: float = 1e-8):
 
 class TopKWorkspace:
     """Scratch buffer for ms_ip_topk, grown on demand and reused across calls."""
+    _sizing = "ms_ip_topk_workspace_bytes"
 
     def __init__(self, device):
         self.device = device
@@ -92,12 +93,24 @@ class TopKWorkspace:
     def get(self, n: int, nq: int, k: int):
         torch = _lib.require_gpu()
         with torch.cuda.device(self.device):          # the plan depends on the device's CU count
-            need = int(_lib.load().ms_ip_topk_workspace_bytes(n, nq, k))
+            need = int(getattr(_lib.load(), self._sizing)(n, nq, k))
         if need == 0:
-            raise MerizoHipError(f"ms_ip_topk_workspace_bytes rejected n={n} nq={nq} k={k}")
+            raise MerizoHipError(f"{self._sizing} rejected n={n} nq={nq} k={k}")
         if self.buf is None or self.buf.numel() < need:
             self.buf = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.buf
+
+
+def _out_pair(nq: int, k: int, device, out, who: str):
+    """The (scores f32 [nq,k], idx i64 [nq,k]) outputs of a search: new tensors, or the caller's `out` once it has that form."""
+    torch = _lib.require_gpu()
+    if out is None:
+        return (torch.empty((nq, k), dtype=torch.float32, device=device), torch.empty((nq, k), dtype=torch.int64, device=device))
+    out_s, out_i = out
+    if (tuple(out_s.shape) != (nq, k) or tuple(out_i.shape) != (nq, k) or out_s.dtype != torch.float32
+            or out_i.dtype != torch.int64 or not out_s.is_contiguous() or not out_i.is_contiguous()):
+        raise MerizoHipError(f"{who}: out must be contiguous (float32 [nq,k], int64 [nq,k]) tensors")
+    return out_s, out_i
 
 
 def ip_topk(db, q, k: int, mode: int = MODE_IP_PRENORM, inv_norm=None, lengths=None, qlen=None,
@@ -115,14 +128,7 @@ def ip_topk(db, q, k: int, mode: int = MODE_IP_PRENORM, inv_norm=None, lengths=N
             if t.numel() != size:
                 raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
     ws = workspace if isinstance(workspace, torch.Tensor) else (workspace or TopKWorkspace(db.device)).get(n, nq, k)
-    if out is None:
-        out_s = torch.empty((nq, k), dtype=torch.float32, device=db.device)
-        out_i = torch.empty((nq, k), dtype=torch.int64, device=db.device)
-    else:
-        out_s, out_i = out
-        if (tuple(out_s.shape) != (nq, k) or tuple(out_i.shape) != (nq, k) or out_s.dtype != torch.float32
-                or out_i.dtype != torch.int64 or not out_s.is_contiguous() or not out_i.is_contiguous()):
-            raise MerizoHipError("ip_topk: out must be contiguous (float32 [nq,k], int64 [nq,k]) tensors")
+    out_s, out_i = _out_pair(nq, k, db.device, out, "ip_topk")
     with _on(db, q, inv_norm, lengths, qlen, ws, out_s, out_i) as dev:
         check(_lib.load().ms_ip_topk(ptr(db), n, row_offset, ptr(q), nq, k, mode, ptr(inv_norm), ptr(lengths), ptr(qlen),
                                      mincov, ptr(out_s), ptr(out_i), ptr(ws), ws.numel(), dev.stream), "ms_ip_topk")
@@ -154,16 +160,7 @@ def ip_topk_finish(n: int, nq: int, k: int, ws, out_s, out_i, row_offset: int = 
 
 class PrefilterWorkspace(TopKWorkspace):
     """Scratch buffer for ms_ip_topk_prefiltered (the plain search's workspace plus the candidate lists)."""
-
-    def get(self, n: int, nq: int, k: int):
-        torch = _lib.require_gpu()
-        with torch.cuda.device(self.device):
-            need = int(_lib.load().ms_ip_topk_prefiltered_workspace_bytes(n, nq, k))
-        if need == 0:
-            raise MerizoHipError(f"ms_ip_topk_prefiltered_workspace_bytes rejected n={n} nq={nq} k={k}")
-        if self.buf is None or self.buf.numel() < need:
-            self.buf = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self.buf
+    _sizing = "ms_ip_topk_prefiltered_workspace_bytes"
 
 
 PF_BF16X3, PF_F16X2, PF_F16X1 = _lib.PF_BF16X3, _lib.PF_F16X2, _lib.PF_F16X1
@@ -298,11 +295,7 @@ def ip_topk_prefiltered(db, q, k: int, row_norm_bound: float = 1.0, mode: int = 
     _pf_args(db, image, q, mode, lengths, qlen)
     n, nq = db.shape[0], q.shape[0]
     ws = workspace if isinstance(workspace, torch.Tensor) else (workspace or PrefilterWorkspace(db.device)).get(n, nq, k)
-    if out is None:
-        out_s = torch.empty((nq, k), dtype=torch.float32, device=db.device)
-        out_i = torch.empty((nq, k), dtype=torch.int64, device=db.device)
-    else:
-        out_s, out_i = out
+    out_s, out_i = _out_pair(nq, k, db.device, out, "ip_topk_prefiltered")
     idata, ifmt = (image.data, image.format) if image is not None else (None, 0)
     with _on(db, q, ws, out_s, out_i, idata, lengths, qlen) as dev:
         check(_lib.load().ms_ip_topk_prefiltered(ptr(db), ptr(idata), ifmt, n, row_offset, ptr(q), nq, k, mode, ptr(lengths), ptr(qlen), mincov,
@@ -317,18 +310,13 @@ def ip_topk_prefiltered_stage(stage: str, db, q, k: int, ws, row_norm_bound: flo
     lib = _lib.load()
     n, nq = db.shape[0], q.shape[0]
     idata, ifmt = (image.data, image.format) if image is not None else (None, 0)
+    fin = stage not in ("prepare", "scan")          # 'finish' also takes the row offset and the outputs
+    name = "ms_ip_topk_prefiltered_" + ("finish" if fin else stage)
     with _on(db, q, ws, idata, lengths, qlen) as dev:
-        if stage == "prepare":
-            check(lib.ms_ip_topk_prefiltered_prepare(ptr(db), ptr(idata), ifmt, n, ptr(q), nq, k, mode, ptr(lengths), ptr(qlen), mincov,
-                                                     float(row_norm_bound), ptr(ws), ws.numel(), dev.stream), "ms_ip_topk_prefiltered_prepare")
-        elif stage == "scan":
-            check(lib.ms_ip_topk_prefiltered_scan(ptr(db), ptr(idata), ifmt, n, ptr(q), nq, k, mode, ptr(lengths), ptr(qlen), mincov,
-                                                  float(row_norm_bound), ptr(ws), ws.numel(), dev.stream), "ms_ip_topk_prefiltered_scan")
-        else:
-            out_s, out_i = out
-            check(lib.ms_ip_topk_prefiltered_finish(ptr(db), ptr(idata), ifmt, n, row_offset, ptr(q), nq, k, mode, ptr(lengths), ptr(qlen), mincov,
-                                                    float(row_norm_bound), ptr(out_s), ptr(out_i), ptr(ws), ws.numel(), dev.stream),
-                  "ms_ip_topk_prefiltered_finish")
+        args = (ptr(db), ptr(idata), ifmt, n) + ((row_offset,) if fin else ()) + (
+            ptr(q), nq, k, mode, ptr(lengths), ptr(qlen), mincov, float(row_norm_bound)) + (
+            (ptr(out[0]), ptr(out[1])) if fin else ()) + (ptr(ws), ws.numel(), dev.stream)
+        check(getattr(lib, name)(*args), name)
 
 
 def prefilter_flagged(ws) -> int:

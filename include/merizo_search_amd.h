@@ -233,6 +233,32 @@ int ms_topk_drop_ranges(const float *scores, const int64_t *idx, int nq, int kin
                         float min_score, int kout, float *out_scores, int64_t *out_idx, int32_t *out_count,
                         ms_stream_t stream);
 
+/* Greedy representative clustering of a database of n rows from its neighbour lists: what `cluster` runs behind the
+ * self-search (the reference has no clustering; its users cluster hit tables in other programs).
+ *   nbr_idx int64 [n,k], nbr_score float32 [n,k]: per row k entries (row j, score s) in the layout ms_topk_drop_ranges writes
+ *   ((-inf, -1) padding); lengths int32 [n]: the domain lengths.  The order of a list's entries does not matter.
+ * A directed entry i -> j is VALID when 0 <= j < n, j != i, s is not NaN, s >= min_score and
+ * (float)min(L_i, L_j) >= mincov * (float)max(L_i, L_j) in fp32; every other entry is ignored (rows outside [0, n) are never
+ * dereferenced).  i ~ j when either direction is valid, with the larger of the directed scores as weight (-0.0 counts as +0.0).
+ * Priority: the longer domain, the smaller row on equal length.  The representatives are the lexicographically-first
+ * maximal independent set under that priority (a row is one exactly when none of its higher-priority neighbours is: the
+ * result of cd-hit's sequential greedy pass).  Then, on the final set: out_rep[i] = i, out_rep_score[i] = 1.0f for a
+ * representative; every other row gets the adjacent representative of largest weight, the smaller row on equal weights,
+ * and that weight.  The result is a function of the inputs alone: no run-to-run or launch-order dependence.
+ * out_rep int64 [n], out_rep_score float32 [n]: device.  HOST pointers: *out_n_reps = representatives, *out_rounds = rounds
+ * of the mark / decide launch pair it took (1..n), *out_saturated = rows whose k entries are ALL valid (such a list may
+ * have been cut short by k: neighbours beyond it are unknown to the clustering).
+ * Unlike the entry points above this one SYNCHRONISES: it reads the count of undecided rows back every few rounds, and it
+ * returns after all its work on `stream` has finished.  workspace: ms_cluster_workspace_bytes(n) bytes (0 for n outside
+ * [1, 2^31 - 1]), 16-byte aligned, initialised by the call.
+ * MS_ERR_ARG: NULL pointers, n < 1, n > 2^31 - 1, k < 1, NaN min_score (-inf: no cut), mincov outside [0, 1] or NaN, a
+ * workspace that is too small.  Backward compatible additions: ms_version() stays 210. */
+size_t ms_cluster_workspace_bytes(int64_t n);
+int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int32_t *lengths,
+                      float min_score, float mincov, int64_t *out_rep, float *out_rep_score,
+                      int64_t *out_n_reps, int32_t *out_rounds, int64_t *out_saturated,
+                      void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

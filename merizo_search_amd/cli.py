@@ -1,4 +1,4 @@
-"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments, and `db-search`.
+"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments, `db-search` and `cluster`.
 
 Mirror of merizo_search/merizo.py for the Foldclass path (search :126-226, easy_search :229-407,
 createdb :102-123).  `segment` (the Merizo IPA network) is out of scope: easy-search takes the
@@ -8,9 +8,11 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli createdb <input_dir> <out_db> [-d cuda] [--layout pt|faiss|both]
     python -m merizo_search_amd.cli easy-search <pdb...> <db_name> <output> <tmp> --chopping "71-189,190-290"
     python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
+    python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] ...
 
 `db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
 against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
+`cluster` has none either: it makes a database non-redundant from the neighbour lists of that self-search (foldclass/cluster.py).
 
 Several GPUs of one node: start one process per GPU with torchrun,
 
@@ -298,6 +300,34 @@ def db_search(argv) -> None:
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def cluster(argv) -> None:
+    p = argparse.ArgumentParser(prog="cluster", description="Make a Foldclass database non-redundant on the GPU: search it against "
+                                "itself, pick representatives greedily (the longer domain first) and assign every other domain "
+                                "to its best-scoring representative.", formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("db_name", type=str, help="Database prefix to cluster (either layout).")
+    p.add_argument("output", type=str)
+    p.add_argument("tmp", type=str)
+    p.add_argument("-d", "--device", type=str, default="cuda", help="'cuda' / 'cuda:N' = the MI355X. 'cpu' is refused by this build.")
+    p.add_argument("-k", "--topk", type=int, default=20, help="Neighbours kept per domain.")
+    p.add_argument("-s", "--mincos", type=float, required=True,
+                   help="Minimum cosine similarity of two domains of one cluster (no default: choose it for your database).")
+    p.add_argument("-c", "--mincov", type=float, default=0.7, help="Minimum length of the shorter domain relative to the longer.")
+    p.add_argument("--query_batchsize", type=int, default=4096, help="Rows per scan call.")
+    p.add_argument("--search_batchsize", type=int, default=262144, help="Target rows per block when the database is streamed.")
+    p.add_argument("--output_headers", action="store_true", default=False)
+    args = p.parse_args(argv)
+    _join_process_group(args)
+    tmp = munge_tmp_with_uuid(args.tmp)
+    _log_command("cluster")
+    from .foldclass.cluster import run_cluster
+    t0 = time.time()
+    run_cluster(db_name=args.db_name, output=args.output, tmp=tmp, device=args.device, topk=args.topk, mincos=args.mincos,
+                mincov=args.mincov, query_batchsize=args.query_batchsize, search_batchsize=args.search_batchsize,
+                header=args.output_headers)
+    logging.info(f"Finished cluster in {time.time() - t0:.3f} seconds.")
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def createdb(argv) -> None:
     p = argparse.ArgumentParser(prog="createdb", description="Embed a directory of PDB files into a Foldclass database.",
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -316,9 +346,9 @@ def createdb(argv) -> None:
 
 def main(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
-    modes = {"search": search, "easy-search": easy_search, "createdb": createdb, "db-search": db_search}
+    modes = {"search": search, "easy-search": easy_search, "createdb": createdb, "db-search": db_search, "cluster": cluster}
     if not argv or argv[0] not in modes:
-        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb,db-search} ...  "
+        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb,db-search,cluster} ...  "
               "(segment: out of scope, use the reference)", file=sys.stderr)
         sys.exit(2)
     modes[argv[0]](argv[1:])

@@ -1,0 +1,259 @@
+// ms_cluster_greedy: greedy representative clustering of a database from its k-nearest-neighbour lists.
+//
+// The step behind a self-search (`db-search db db --exclude_self`) that makes a database non-redundant (DESIGN.md section
+// 5.8): the representatives are the lexicographically-first maximal independent set of the undirected neighbour graph under
+// the priority "longer domain first, smaller row on equal length" -- what cd-hit's sequential greedy pass yields -- and
+// every other row goes to its best-scoring adjacent representative.
+//
+// The graph is never transposed.  An edge may be held by one endpoint's list only; the other endpoint learns of it by being
+// WRITTEN TO.  A round is two launches ordered by the stream (the kernel boundary is the only cross-workgroup hand-off):
+//   mark    one thread per list entry i->j, status read-only: an undecided i stores `blocked` into a lower-priority j (push) or
+//           into itself when a higher-priority j is still undecided (pull); a new representative stores `covered` into its
+//           neighbours, an undecided i into itself next to a representative.  All stores write the value 1: any order, any
+//           multiplicity gives the same bytes.
+//   decide  one thread per row: undecided + covered -> member; undecided, neither covered nor blocked -> representative;
+//           its `blocked` byte is cleared for the next round; the rows still undecided are counted.
+// The highest-priority undecided row is never blocked, so every round decides a row.  Decided rows skip their lists (a
+// representative reads its list once more, the round after it was chosen, to cover its neighbours).
+// Assignment runs once on the final set: 64-bit atomicMax on {order-preserving score bits, ~row}, pushed and pulled in the
+// same way, so the result depends on the set alone.  Vector stores and vector atomics only; no LDS, no scratch.
+#include "ms_common.h"
+
+#define MS_CL_THREADS 256
+#define MS_CL_MAX_BLOCKS (1 << 20)     // grid-stride above this many workgroups (2^28 threads: inside HIP's 2^32 per launch)
+#define MS_CL_GROUP 4                  // rounds enqueued between two looks at the undecided counts
+#define MS_CL_HEAD_BYTES 64            // counters in front of the per-row arrays
+
+#define MS_CL_UNDECIDED 0
+#define MS_CL_MEMBER 1
+#define MS_CL_REP_NEW 2                // chosen by the last decide launch: covers its neighbours in the next mark launch
+#define MS_CL_REP 3
+
+struct ms_cl_head {                    // the first MS_CL_HEAD_BYTES of the workspace
+    uint32_t remaining[MS_CL_GROUP];   // rows still undecided after round (slot) of the current group
+    unsigned long long n_reps;
+    unsigned long long saturated;
+};
+
+struct ms_cl_view {                    // the workspace, carved (host and device)
+    ms_cl_head *head;
+    unsigned long long *best;          // [n] assignment key of a member
+    uint8_t *status, *blocked, *covered, *cut;      // [n] each; cut: the row's list holds an entry that is not valid
+};
+
+static inline size_t ms_cl_rows_bytes(int64_t n) { return ms_align_up((size_t)n, 16); }
+
+static inline ms_cl_view ms_cl_carve(void *workspace, int64_t n) {
+    char *p = (char *)workspace;
+    ms_cl_view v;
+    v.head = (ms_cl_head *)p;
+    v.best = (unsigned long long *)(p + MS_CL_HEAD_BYTES);
+    v.status = (uint8_t *)(p + MS_CL_HEAD_BYTES + 8 * (size_t)n);
+    v.blocked = v.status + ms_cl_rows_bytes(n);
+    v.covered = v.blocked + ms_cl_rows_bytes(n);
+    v.cut = v.covered + ms_cl_rows_bytes(n);
+    return v;
+}
+
+// Priority: the longer domain, the smaller row on equal length.
+__device__ __forceinline__ bool ms_cl_before(int32_t la, int64_t a, int32_t lb, int64_t b) { return la > lb || (la == lb && a < b); }
+
+__device__ __forceinline__ bool ms_cl_is_rep(uint8_t st) { return st >= MS_CL_REP_NEW; }
+
+// A directed entry i->j counts when j is a row other than i, the score is a number at or above min_score and the shorter
+// domain covers mincov of the longer one (fp32, this operand order).  lengths[j] is read only behind the range check.
+__device__ __forceinline__ bool ms_cl_valid(int64_t i, int64_t j, float s, int64_t n, const int32_t *lengths, int32_t li,
+                                            float min_score, float mincov, int32_t *lj_out) {
+    if (j < 0 || j >= n || j == i) return false;
+    if (!(s >= min_score)) return false;                                  // (NaN fails every comparison)
+    const int32_t lj = lengths[j];
+    *lj_out = lj;
+    const int32_t lmin = li < lj ? li : lj, lmax = li < lj ? lj : li;
+    return (float)lmin >= mincov * (float)lmax;
+}
+
+// {score, row} as one unsigned key: a larger score wins, then the smaller row; -0.0 ranks as +0.0; never 0 for a real entry.
+__device__ __forceinline__ unsigned long long ms_cl_key(float s, int64_t row) {
+    uint32_t b = __float_as_uint(s + 0.0f);
+    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((unsigned long long)b << 32) | (unsigned long long)(~(uint32_t)row);
+}
+
+// The entry a thread of a grid-stride pass works on: entry e = base + thread of the [n,k] lists, its row i (one 64-bit
+// division per workgroup and pass, a 32-bit one per thread).
+#define MS_CL_FOR_ENTRIES(total)                                                                                   \
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < (total); base += (int64_t)gridDim.x * MS_CL_THREADS)
+
+__device__ __forceinline__ int64_t ms_cl_entry_row(int64_t base, int k) {
+    const int64_t row0 = base / k;
+    const uint32_t local = (uint32_t)(base - row0 * k) + threadIdx.x;      // < k + 256
+    return row0 + (int64_t)(local / (uint32_t)k);
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_kernel(
+        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
+        uint8_t *blocked, uint8_t *covered, uint32_t *remaining_slot) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *remaining_slot = 0u;         // (this round's decide launch counts into it)
+    const int64_t total = n * (int64_t)k;
+    MS_CL_FOR_ENTRIES(total) {
+        const int64_t i = ms_cl_entry_row(base, k);
+        if (i >= n) continue;
+        const uint8_t st = status[i];
+        if (st != MS_CL_UNDECIDED && st != MS_CL_REP_NEW) continue;        // decided rows have nothing left to say
+        const int64_t e = base + threadIdx.x;
+        const int64_t j = nbr_idx[e];
+        const float s = nbr_score[e];
+        const int32_t li = lengths[i];
+        int32_t lj;
+        if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) continue;
+        if (st == MS_CL_REP_NEW) { covered[j] = 1; continue; }
+        const uint8_t sj = status[j];
+        if (ms_cl_before(li, i, lj, j)) {
+            if (sj == MS_CL_UNDECIDED) blocked[j] = 1;                     // push: j must wait for i
+        } else if (sj == MS_CL_UNDECIDED) {
+            blocked[i] = 1;                                                // pull: i must wait for j
+        } else if (ms_cl_is_rep(sj)) {
+            covered[i] = 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_decide_kernel(int64_t n, uint8_t *status, uint8_t *blocked,
+                                                                          const uint8_t *covered, uint32_t *remaining_slot) {
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        bool waits = false;
+        if (i < n) {
+            const uint8_t st = status[i];
+            if (st == MS_CL_REP_NEW) {
+                status[i] = MS_CL_REP;                                     // (it covered its neighbours in this round's mark launch)
+            } else if (st == MS_CL_UNDECIDED) {
+                const uint8_t b = blocked[i];
+                if (b) blocked[i] = 0;
+                if (covered[i]) status[i] = MS_CL_MEMBER;
+                else if (!b) status[i] = MS_CL_REP_NEW;
+                else waits = true;
+            }
+        }
+        const unsigned long long m = __ballot(waits);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(remaining_slot, (uint32_t)__popcll(m));
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_kernel(
+        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
+        unsigned long long *best, uint8_t *cut) {
+    const int64_t total = n * (int64_t)k;
+    MS_CL_FOR_ENTRIES(total) {
+        const int64_t i = ms_cl_entry_row(base, k);
+        if (i >= n) continue;
+        const int64_t e = base + threadIdx.x;
+        const int64_t j = nbr_idx[e];
+        const float s = nbr_score[e];
+        const int32_t li = lengths[i];
+        int32_t lj;
+        if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) { cut[i] = 1; continue; }
+        const bool rep_i = ms_cl_is_rep(status[i]), rep_j = ms_cl_is_rep(status[j]);
+        if (rep_j && !rep_i) atomicMax(best + i, ms_cl_key(s, j));         // pull
+        if (rep_i && !rep_j) atomicMax(best + j, ms_cl_key(s, i));         // push
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_finish_kernel(int64_t n, const uint8_t *__restrict__ status,
+                                                                          const unsigned long long *__restrict__ best,
+                                                                          const uint8_t *__restrict__ cut, int64_t *out_rep,
+                                                                          float *out_rep_score, ms_cl_head *head) {
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        bool rep = false, full = false;
+        if (i < n) {
+            rep = ms_cl_is_rep(status[i]);
+            full = !cut[i];
+            int64_t r = i;
+            float s = 1.0f;
+            if (!rep) {
+                const unsigned long long key = best[i];
+                const uint32_t b = (uint32_t)(key >> 32);
+                r = key ? (int64_t)(~(uint32_t)key) : -1;                  // (a member always has an adjacent representative)
+                s = key ? __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b) : -INFINITY;
+            }
+            out_rep[i] = r;
+            out_rep_score[i] = s;
+        }
+        const unsigned long long mr = __ballot(rep), mf = __ballot(full);
+        if ((threadIdx.x & 63) == 0) {
+            if (mr) atomicAdd(&head->n_reps, (unsigned long long)__popcll(mr));
+            if (mf) atomicAdd(&head->saturated, (unsigned long long)__popcll(mf));
+        }
+    }
+}
+
+extern "C" size_t ms_cluster_workspace_bytes(int64_t n) {
+    if (n < 1 || n > 2147483647LL) return 0;
+    return MS_CL_HEAD_BYTES + 8 * (size_t)n + 4 * ms_cl_rows_bytes(n);
+}
+
+static inline unsigned ms_cl_blocks(int64_t items) {
+    const int64_t b = (items + MS_CL_THREADS - 1) / MS_CL_THREADS;
+    return (unsigned)(b < MS_CL_MAX_BLOCKS ? b : MS_CL_MAX_BLOCKS);
+}
+
+extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int32_t *lengths,
+                                 float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
+                                 int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
+                                 ms_stream_t stream) {
+    if (!nbr_idx || !nbr_score || !lengths || !out_rep || !out_rep_score || !out_n_reps || !out_rounds || !out_saturated || !workspace)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: NULL pointer");
+    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
+    if (k < 1) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need k >= 1 (k=%d)", k);
+    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: min_score is NaN (-inf: no cut)");
+    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: mincov must lie in [0, 1]");
+    const size_t need = ms_cluster_workspace_bytes(n);
+    if (workspace_bytes < need)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: workspace of %zu bytes, ms_cluster_workspace_bytes(%lld) = %zu", workspace_bytes,
+                (long long)n, need);
+    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: workspace must be 16-byte aligned");
+
+    hipStream_t st = (hipStream_t)stream;
+    const ms_cl_view v = ms_cl_carve(workspace, n);
+    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), row_blocks = ms_cl_blocks(n);
+    MS_HIP_CHECK(hipMemsetAsync(workspace, 0, need, st));                  // every row undecided, no flag, no key, counters 0
+
+    int64_t rounds = 0;
+    for (bool done = false; !done;) {
+        for (int g = 0; g < MS_CL_GROUP; ++g) {
+            hipLaunchKernelGGL(ms_cluster_mark_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
+                               min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
+            MS_LAUNCH_CHECK("ms_cluster_mark_kernel");
+            hipLaunchKernelGGL(ms_cluster_decide_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.blocked, v.covered,
+                               v.head->remaining + g);
+            MS_LAUNCH_CHECK("ms_cluster_decide_kernel");
+        }
+        uint32_t remaining[MS_CL_GROUP];
+        MS_HIP_CHECK(hipMemcpyAsync(remaining, v.head->remaining, sizeof(remaining), hipMemcpyDeviceToHost, st));
+        MS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int g = 0; g < MS_CL_GROUP && !done; ++g) {
+            ++rounds;
+            done = remaining[g] == 0u;                                     // (the rounds behind it in the group changed nothing)
+        }
+        if (!done && rounds > n)                                           // every round decides a row: unreachable on sound memory
+            MS_FAIL(MS_ERR_HIP, "ms_cluster_greedy: %lld rows still undecided after %lld rounds", (long long)remaining[MS_CL_GROUP - 1],
+                    (long long)rounds);
+    }
+
+    hipLaunchKernelGGL(ms_cluster_assign_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
+                       min_score, mincov, v.status, v.best, v.cut);
+    MS_LAUNCH_CHECK("ms_cluster_assign_kernel");
+    hipLaunchKernelGGL(ms_cluster_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.best, v.cut, out_rep,
+                       out_rep_score, v.head);
+    MS_LAUNCH_CHECK("ms_cluster_finish_kernel");
+    ms_cl_head head;
+    MS_HIP_CHECK(hipMemcpyAsync(&head, v.head, sizeof(head), hipMemcpyDeviceToHost, st));
+    MS_HIP_CHECK(hipStreamSynchronize(st));
+    *out_n_reps = (int64_t)head.n_reps;
+    *out_saturated = (int64_t)head.saturated;
+    *out_rounds = (int32_t)rounds;
+    return MS_OK;
+}

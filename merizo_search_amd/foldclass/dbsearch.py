@@ -586,6 +586,61 @@ class _DeviceTimes:
             self.sink[name + "_calls"] = len(spans)
 
 
+class _BatchScan:
+    """A database as the target of query batches taken from a database (run_dbsearch_db, cluster.run_cluster): this rank's rows
+    made resident once (streamed through engine.device_blocks beyond the HBM budget), then per batch of query rows [b0, b1)
+    the scan at k', the exchange + merge under several ranks, and the drop step down to kout entries at or above min_score."""
+
+    def __init__(self, target_db: dict, qdb, engine, same: bool, nq_batch: int, kk: int, search_batchsize: int, times):
+        self.target_db, self.qdb, self.engine, self.kk, self.times = target_db, qdb, engine, int(kk), times
+        self.search_batchsize = int(search_batchsize)
+        self.shard = self.dbmm = None
+        rank, world = sharded.rank_world()
+        if target_db["faiss"]:
+            dbinfo = read_dbinfo(target_db["database"])
+            n_target = int(dbinfo["DB_SIZE"])
+            self.dbmm = db_memmap(filename=os.path.join(os.path.dirname(target_db["database"]), dbinfo["dbfname_IP"]),
+                                  shape=(dbinfo["DB_SIZE"], dbinfo["DB_DIM"]))
+            self.lo, self.hi = sharded.shard_bounds(n_target, world, rank)
+            self.shard = _resident_shard(target_db, engine, self.dbmm, self.lo, self.hi, int(nq_batch), self.kk)
+            if self.shard is None:
+                logger.info("database shard of %d rows exceeds the resident budget: streaming blocks of %d rows per query batch"
+                            % (self.hi - self.lo, self.search_batchsize))
+        else:
+            _to_engine(target_db, engine)
+        # the same faiss-layout database on one rank: the resident rows ARE the queries (normalised, 16-byte aligned at 512 B per
+        # row), read in place by the scan.  (`.pt`: the resident rows were normalised in place, the raw queries come from the file.)
+        self.in_place = bool(same and qdb.faiss and world == 1 and self.shard is not None)
+        self.streamed = bool(target_db["faiss"] and self.shard is None)
+
+    def search(self, b0: int, b1: int, seqs, mincov: float, d_lo, d_hi, kout: int, min_score: float, out=None):
+        """Query rows [b0, b1) of the query database -> (scores [nq,kout], rows [nq,kout], count [nq]) on the device, the rows
+        [d_lo[q], d_hi[q]) of each query excluded; seqs: the queries' sequences (the `.pt` layout's length mask; unused in the
+        faiss layout).  out: the preallocated triple the drop step writes into."""
+        target_db, engine, qdb, kk, times = self.target_db, self.engine, self.qdb, self.kk, self.times
+        q = self.shard[b0:b1] if self.in_place else engine.to_device(qdb.embeddings(b0, b1))
+        t0 = times.mark()
+        if not target_db["faiss"]:
+            top = search_query_against_db({"seq": seqs, "embedding": q}, target_db, mincov, kk, engine=engine)
+            Ds, Is = top["scores"], top["indices"]
+        else:
+            if self.shard is not None:
+                Ds, Is = knn_exact(q, [self.shard], kk, engine, log=_QUIET, row_offset=self.lo, to_host=False, raw_queries=not qdb.normalized,
+                                   row_norm_bound=target_db["_resident"].get("row_norm_bound"),
+                                   pf_image=target_db["_resident"].get("pf_image"))
+            else:
+                qn = q if qdb.normalized else engine.normalized(q, 1e-12)
+                Ds, Is = knn_exact(qn, db_iterator(self.dbmm[self.lo:self.hi], self.search_batchsize), kk, engine, log=_QUIET,
+                                   row_offset=self.lo, to_host=False)
+            Ds, Is = sharded.exchange_and_merge(Ds, Is, engine)
+        t1 = times.mark()
+        times.add("scan", t0, t1)
+        kw = {} if out is None else {"out": out}
+        dropped = engine.topk_drop_ranges(Ds, Is, d_lo, d_hi, int(kout), float(min_score), **kw)
+        times.add("drop", t1)
+        return dropped
+
+
 def _append_tsv(results, path: str, part: str, fields, header: bool) -> None:
     """One batch's rows behind what `path` holds already, written by results.write_search_results itself."""
     from .results import write_search_results
@@ -684,25 +739,15 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     times = _DeviceTimes(engine, timings)
     network = SimpleNamespace(engine=engine)
     aligner_device = _aligner_device(network, device)
-    shard = None
-    if target_db["faiss"]:
-        dbmm = db_memmap(filename=path("dbfname_IP"), shape=(dbinfo["DB_SIZE"], dbinfo["DB_DIM"]))
-        lo, hi = sharded.shard_bounds(n_target, world, rank)
-        shard = _resident_shard(target_db, engine, dbmm, lo, hi, min(int(query_batchsize), q_hi - q_lo), kk)
-        if shard is None:
-            logger.info("database shard of %d rows exceeds the resident budget: streaming blocks of %d rows per query batch"
-                        % (hi - lo, int(search_batchsize)))
-    else:
-        _to_engine(target_db, engine)
-    # the same faiss-layout database on one rank: the resident rows ARE the queries (normalised, 16-byte aligned at 512 B per
-    # row), read in place by the scan.  (`.pt`: the resident rows were normalised in place, the raw queries come from the file.)
-    in_place = same and qdb.faiss and world == 1 and shard is not None
+    nq_batch = min(int(query_batchsize), q_hi - q_lo)
+    scan = _BatchScan(target_db, qdb, engine, same, nq_batch, kk, search_batchsize, times)
+    in_place = scan.in_place
     logger.info("db-search: %d queries of %s against %d rows of %s in batches of %d (k = %d%s)%s"
                 % (q_hi - q_lo, query_db, n_target, db_name, int(query_batchsize), int(topk),
                    ", %d fetched: up to %d rows excluded per query" % (kk, max_excluded) if exclude_self else "",
                    "; queries read in place from the resident rows" if in_place else ""))
     if timings is not None:
-        timings["in_place"], timings["streamed"] = bool(in_place), bool(target_db["faiss"] and shard is None)
+        timings["in_place"], timings["streamed"] = bool(in_place), scan.streamed
     d_lo, d_hi = engine.to_device(ex_lo), engine.to_device(ex_hi)        # once for the run: a batch's ranges are a slice
     md_all = {}
     tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
@@ -715,25 +760,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
             seqs = [qd["seq"] for qd in query_dicts]
         elif not target_db["faiss"]:
             seqs = qdb.seqs(b0, b1)                                       # (every rank masks by query length)
-        q = shard[b0:b1] if in_place else engine.to_device(qdb.embeddings(b0, b1))
-        t0 = times.mark()
-        if not target_db["faiss"]:
-            top = search_query_against_db({"seq": seqs, "embedding": q}, target_db, mincov, kk, engine=engine)
-            Ds, Is = top["scores"], top["indices"]
-        else:
-            if shard is not None:
-                Ds, Is = knn_exact(q, [shard], kk, engine, log=_QUIET, row_offset=lo, to_host=False, raw_queries=not qdb.normalized,
-                                   row_norm_bound=target_db["_resident"].get("row_norm_bound"),
-                                   pf_image=target_db["_resident"].get("pf_image"))
-            else:
-                qn = q if qdb.normalized else engine.normalized(q, 1e-12)
-                Ds, Is = knn_exact(qn, db_iterator(dbmm[lo:hi], int(search_batchsize)), kk, engine, log=_QUIET, row_offset=lo,
-                                   to_host=False)
-            Ds, Is = sharded.exchange_and_merge(Ds, Is, engine)
-        t1 = times.mark()
-        times.add("scan", t0, t1)
-        Ds, Is, Cs = engine.topk_drop_ranges(Ds, Is, d_lo[b0 - q_lo: b1 - q_lo], d_hi[b0 - q_lo: b1 - q_lo], int(topk), float(mincos))
-        times.add("drop", t1)
+        Ds, Is, Cs = scan.search(b0, b1, seqs, mincov, d_lo[b0 - q_lo: b1 - q_lo], d_hi[b0 - q_lo: b1 - q_lo], int(topk), float(mincos))
         if rank != 0:
             continue
         D, I, C = Ds.cpu().numpy(), Is.cpu().numpy(), Cs.cpu().numpy()

@@ -232,9 +232,14 @@ class HipEngine:
         """Global top-k from the all-gathered per-shard blocks, read in place (ms_topk_merge_strided)."""
         return exchange.merge()
 
-    def topk_drop_ranges(self, scores, idx, lo, hi, kout: int, min_score: float = float("-inf")):
-        """Rows [lo[q], hi[q]) and scores below min_score taken out of sorted lists (ms_topk_drop_ranges)."""
-        return self._ops.topk_drop_ranges(scores, idx, lo, hi, kout, min_score)
+    def topk_drop_ranges(self, scores, idx, lo, hi, kout: int, min_score: float = float("-inf"), out=None):
+        """Rows [lo[q], hi[q]) and scores below min_score taken out of sorted lists (ms_topk_drop_ranges); out: the
+        preallocated (scores, rows, count) it writes into."""
+        return self._ops.topk_drop_ranges(scores, idx, lo, hi, kout, min_score, out=out)
+
+    def cluster_greedy(self, nbr_idx, nbr_score, lengths, min_score: float, mincov: float = 0.0):
+        """Representatives and assignments from neighbour lists (ms_cluster_greedy) -> (rep, rep_score, info)."""
+        return self._ops.cluster_greedy(nbr_idx, nbr_score, lengths, min_score, mincov)
 
     # -- database residency ----------------------------------------------------------
     STAGE_ROWS = 1 << 19          # 256 MiB pinned staging buffers

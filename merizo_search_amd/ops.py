@@ -452,6 +452,50 @@ def topk_excluding(db, q, k: int, lo, hi, mode: int = MODE_IP_PRENORM, row_norm_
     return topk_drop_ranges(s, i, lo, hi, int(k), min_score)
 
 
+def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float = 0.0, out=None, workspace=None):
+    """Greedy representative clustering of n rows from their neighbour lists (ms_cluster_greedy: the definition is the
+    header's).  nbr_idx int64 [n,k], nbr_score float32 [n,k] as topk_drop_ranges writes them, lengths int32 [n] (a tensor, or a
+    host array that is uploaded).  -> (rep int64 [n], rep_score float32 [n], info) with info = {'n_reps', 'rounds',
+    'saturated'}.  Synchronises: the call returns when the clustering has finished.  out: optional preallocated (rep,
+    rep_score); workspace: optional uint8 tensor of ms_cluster_workspace_bytes(n)."""
+    import ctypes
+    torch = _lib.require_gpu()
+    if (not isinstance(nbr_idx, torch.Tensor) or not isinstance(nbr_score, torch.Tensor) or nbr_score.dim() != 2
+            or nbr_idx.shape != nbr_score.shape or nbr_score.dtype != torch.float32 or nbr_idx.dtype != torch.int64 or not nbr_score.is_cuda):
+        raise MerizoHipError("cluster_greedy: expected int64 / float32 CUDA tensors of one shape [n,k]")
+    if not (nbr_idx.is_contiguous() and nbr_score.is_contiguous()):
+        raise MerizoHipError("cluster_greedy: the neighbour lists must be contiguous")
+    n, k = nbr_score.shape
+    if n < 1 or k < 1:
+        raise MerizoHipError(f"cluster_greedy: need n >= 1 and k >= 1 (n={n} k={k})")
+    t = lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)))
+    if t.is_floating_point() or t.dim() != 1 or t.numel() != n:
+        raise MerizoHipError(f"cluster_greedy: lengths: expected {n} integers, got {t.dtype} of shape {tuple(t.shape)}")
+    t = t.to(device=nbr_score.device, dtype=torch.int32).contiguous()
+    if out is None:
+        rep = torch.empty((n,), dtype=torch.int64, device=nbr_score.device)
+        rep_score = torch.empty((n,), dtype=torch.float32, device=nbr_score.device)
+    else:
+        rep, rep_score = out
+        if (tuple(rep.shape) != (n,) or tuple(rep_score.shape) != (n,) or rep.dtype != torch.int64 or rep_score.dtype != torch.float32
+                or not (rep.is_contiguous() and rep_score.is_contiguous())):
+            raise MerizoHipError("cluster_greedy: out must be contiguous (int64 [n], float32 [n]) tensors")
+    lib = _lib.load()
+    need = int(lib.ms_cluster_workspace_bytes(n))
+    if need == 0:
+        raise MerizoHipError(f"ms_cluster_workspace_bytes rejected n={n}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=nbr_score.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise MerizoHipError(f"cluster_greedy: workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    with _on(nbr_idx, nbr_score, t, rep, rep_score, workspace) as dev:
+        check(lib.ms_cluster_greedy(ptr(nbr_idx), ptr(nbr_score), n, k, ptr(t), float(min_score), float(mincov), ptr(rep), ptr(rep_score),
+                                    ctypes.addressof(n_reps), ctypes.addressof(rounds), ctypes.addressof(saturated), ptr(workspace),
+                                    workspace.numel(), dev.stream), "ms_cluster_greedy")
+    return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+
+
 class EgnnEncoder:
     """The Foldclass structure encoder on one GPU: prepared weights + positional table.
 

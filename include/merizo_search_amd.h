@@ -259,6 +259,33 @@ int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n,
                       int64_t *out_n_reps, int32_t *out_rounds, int64_t *out_saturated,
                       void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* The score matrices of the multi-domain search's `exhaustive_cosine` mode: step 3 of dbsearch_fulllength.py (:468-483) with
+ * the search's own score in place of TM-align -- the "embscore mode" that file leaves as a TODO (:202-203, :558-571).
+ * Candidate c = cand[c] = {q0, nqd, t_off, nhd} is one (query chain, target chain) pair: its query domains are rows
+ * [q0, q0 + nqd) of q [nq,128], its target domains the nhd rows db[trows[t_off + j]] of db [n,128] (trows int64 [ntrows], a
+ * ragged list; rows may repeat).  Its matrix is written row-major [nqd,nhd] at out_scores + mat_off[c] (mat_off int64
+ * [ncand], in floats; the caller lays the matrices out, gaps are left alone).
+ *   cell (i, j) = EXACTLY the score ms_ip_topk reports for query q0 + i and row trows[t_off + j] in `mode`, bit for bit:
+ *        MS_MODE_IP_PRENORM, MS_MODE_IP_NORMQ or MS_MODE_COSINE_UNIT (others: MS_ERR_ARG); the queries are prepared by the
+ *        scan's own preparation launch into the workspace, the dot is the scan's chain (s = 0..63: element s, then element
+ *        64 + s, one fmaf each), MS_MODE_COSINE_UNIT multiplies by the length mask (qlen[q] >= lengths[row] * mincov;
+ *        lengths float32 [n] and qlen float32 [nq] go together, NULL NULL = no mask; NULL in the other modes);
+ *   cut: a score that is NaN or < min_score is stored as +0.0f; a score equal to min_score stays; -inf cuts nothing;
+ *   out_match int32 [ncand][2] = {rows of the matrix with a non-zero entry, columns with a non-zero entry} after the cut
+ *        (-0.0 is zero): the caller keeps a candidate only if [0] == nqd and [1] >= nqd.
+ * Descriptors are data, not trusted: a trows entry outside [0, n) is never dereferenced, its cells are +0.0f; a candidate
+ * with nqd < 1, nhd < 1, nqd or nhd > 4096, [q0, q0 + nqd) outside [0, nq] or [t_off, t_off + nhd) outside [0, ntrows]
+ * gets out_match = {-1, -1} and nothing else is written for it.
+ * ncand == 0 succeeds without a launch.  MS_ERR_ARG: NULL pointers, nq < 1, ncand < 0, another mode, a NaN min_score, db or
+ * workspace not 16-byte aligned; MS_ERR_WORKSPACE: fewer than ms_md_chain_scores_workspace_bytes(nq) bytes (0 for nq < 1).
+ * One wave per candidate, one lane per cell (the chain is sequential); vector stores only.  Backward compatible
+ * additions: ms_version() stays 210. */
+size_t ms_md_chain_scores_workspace_bytes(int nq);
+int ms_md_chain_scores(const float *db, int64_t n, const float *q, int nq, int mode, const float *lengths, const float *qlen,
+                       float mincov, const int32_t *cand, int ncand, const int64_t *trows, int64_t ntrows,
+                       const int64_t *mat_off, float min_score, float *out_scores, int32_t *out_match, void *workspace,
+                       size_t workspace_bytes, ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

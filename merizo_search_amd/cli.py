@@ -10,6 +10,12 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
     python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] ...
 
+`--multi_domain_search` (search, easy-search, db-search) also writes `<output>_search_multi_dom.tsv`: the target chains that match
+every domain of a query chain.  `--multi_domain_mode exhaustive_tmalign` (the reference's; search and easy-search) aligns every
+query domain with every domain of every hit chain and needs a TM-align binary or `--tmalign_backend hip`;
+`exhaustive_cosine` (the only mode of db-search, where the query chains are the runs of adjacent query rows with one chain id)
+scores those pairs with the search's own embedding score on the GPU and needs neither (foldclass/multidomain.py).
+
 `db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
 against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
 `cluster` has none either: it makes a database non-redundant from the neighbour lists of that self-search (foldclass/cluster.py).
@@ -63,10 +69,13 @@ def _add_search_flags(p: argparse.ArgumentParser, default_format: str) -> None:
     p.add_argument("--metadata_json", action="store_true", default=False)
     p.add_argument("--multi_domain_search", action="store_true", default=False,
                    help="Search DB for entries that match all query domains (all query structures are treated as single "
-                        "domains coming from one chain).  Needs a TM-align binary ($MERIZO_TMALIGN).")
-    p.add_argument("--multi_domain_mode", type=str, default="exhaustive_tmalign", choices=["exhaustive_tmalign"],
-                   help="If --multi_domain_search is used, specifies the multi-domain search mode. Currently only "
-                        "'exhaustive_tmalign' is supported.")
+                        "domains coming from one chain).  'exhaustive_tmalign' needs a TM-align binary ($MERIZO_TMALIGN) or "
+                        "--tmalign_backend hip.")
+    p.add_argument("--multi_domain_mode", type=str, default="exhaustive_tmalign", choices=["exhaustive_tmalign", "exhaustive_cosine"],
+                   help="If --multi_domain_search is used, specifies the multi-domain search mode. 'exhaustive_tmalign': TM-align "
+                        "every query domain with every domain of every hit chain. 'exhaustive_cosine': score those pairs with "
+                        "the search's own embedding score on the GPU instead (entries below --mincos count as no match); needs "
+                        "no TM-align binary.")
     p.add_argument("--skip_tmalign", action="store_true", default=False,
                    help="Embedding-only search (automatic when no TM-align binary is found and --tmalign_backend is auto).")
     p.add_argument("--tmalign_backend", type=str, default="auto", choices=["auto", "hip"],
@@ -144,15 +153,20 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         if os.path.exists(path):
             logging.warning(f"Search output file '{path}' already exists. Results will be overwritten!")
     multi_output = args.output + "_search_multi_dom.tsv"
+    cosine_md = args.multi_domain_search and args.multi_domain_mode == "exhaustive_cosine"
     if args.multi_domain_search:
-        if not hip and tm.find_tmalign() is None:
+        if not cosine_md and not hip and tm.find_tmalign() is None:
             logging.error("--multi_domain_search aligns every query domain with every candidate target domain and needs a "
                           "TM-align binary (set $MERIZO_TMALIGN).")
             sys.exit(1)
         if os.path.exists(multi_output):
             logging.warning(f"Multi-domain search output file '{multi_output}' already exists. Results will be overwritten!")
+    network = None
+    if cosine_md:       # the multi-domain step re-embeds the query domains with the encoder the search runs with
+        from .foldclass import dbsearch as _ds
+        network, _device = _ds.network_setup(threads=args.threads, device=args.device, weights_path=args.weights)
     results, all_results = run_dbsearch(
-        inputs=inputs, db_name=args.db_name, tmp=tmp, device=args.device, topk=args.topk, fastmode=args.fastmode,
+        network=network, inputs=inputs, db_name=args.db_name, tmp=tmp, device=args.device, topk=args.topk, fastmode=args.fastmode,
         threads=args.threads, mincos=args.mincos, mintm=args.mintm, mincov=args.mincov, inputs_are_ca=inputs_are_ca,
         pdb_chain=pdb_chain, search_batchsize=args.search_batchsize, search_type=args.search_metric,
         skip_tmalign=skip, weights_path=args.weights, tmalign_backend=args.tmalign_backend)
@@ -172,7 +186,7 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         mda = multi_domain_search(queries=inputs, search_results=results, db_name=args.db_name, tmp_root=tmp, device=args.device,
                                   fastmode=args.fastmode, threads=args.threads, mintm=args.mintm,
                                   inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain,
-                                  tmalign_backend=args.tmalign_backend)
+                                  tmalign_backend=args.tmalign_backend, mincos=args.mincos, mincov=args.mincov, network=network)
         write_all_dom_search_results(mda, multi_output, args.output_headers)
 
 
@@ -282,6 +296,12 @@ def db_search(argv) -> None:
     p.add_argument("--exclude_same_chain", action="store_true", default=False,
                    help="query_db and target_db are the same database: report no domain of the query's own chain "
                         "(implies --exclude_self).")
+    p.add_argument("--multi_domain_search", action="store_true", default=False,
+                   help="Also search for target chains that match ALL domains of a query chain (the runs of adjacent query rows "
+                        "with one chain id) and write <output>_search_multi_dom.tsv.")
+    p.add_argument("--multi_domain_mode", type=str, default="exhaustive_cosine", choices=["exhaustive_cosine"],
+                   help="The multi-domain search mode: every query domain against every domain of every hit chain, scored with "
+                        "the search's own embedding score on the GPU (entries below --mincos count as no match).")
     args = p.parse_args(argv)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
@@ -295,7 +315,8 @@ def db_search(argv) -> None:
                         query_batchsize=args.query_batchsize, query_rows=args.query_rows, exclude_self=args.exclude_self,
                         exclude_same_chain=args.exclude_same_chain, format_list=fields,
                         header=args.output_headers, metadata_json=args.metadata_json,
-                        report_insignificant_hits=args.report_insignificant_hits)
+                        report_insignificant_hits=args.report_insignificant_hits, multi_domain_search=args.multi_domain_search,
+                        multi_domain_mode=args.multi_domain_mode)
     logging.info(f"Finished db-search of {n} queries in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 

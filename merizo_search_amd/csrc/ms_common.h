@@ -32,6 +32,10 @@ extern thread_local char ms_err_buf[512];
 
 static inline size_t ms_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Queries -> the [nq_pad,128] copy the scan of `mode` multiplies with (ms_search.hip: zero padding behind nq; L2-normalised
+// with the mode's eps unless the mode takes them as given).  One launch on st.
+int ms_launch_prepare_queries(const float *q, int nq, int nq_pad, int mode, float *qn, hipStream_t st);
+
 // ---------------------------------------------------------------- device helpers ------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -91,6 +91,15 @@ __global__ __launch_bounds__(256) void ms_prepare_queries_kernel(const float *q,
     *(reinterpret_cast<float2 *>(qn + (size_t)row * MS_DIM) + lane) = v;
 }
 
+// The one mapping from a search mode to the preparation of its queries (ms_common.h): the scan's own launch, and what
+// ms_md_chain_scores (ms_multidom.hip) scores its cells with.
+int ms_launch_prepare_queries(const float *q, int nq, int nq_pad, int mode, float *qn, hipStream_t st) {
+    hipLaunchKernelGGL(ms_prepare_queries_kernel, dim3((nq_pad + 3) / 4), dim3(256), 0, st, q, nq, nq_pad,
+                       mode != MS_MODE_IP_PRENORM ? 1 : 0, mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f, qn);
+    MS_LAUNCH_CHECK("ms_prepare_queries_kernel");
+    return MS_OK;
+}
+
 #include "ms_scan.h"
 #include "ms_scan_pf.h"
 #include "ms_scan_pf16.h"
@@ -1025,9 +1034,8 @@ int prepare_scan(const ScanPlan &pl, const float *db, int64_t n, const float *q,
                  const float *inv_norm, const float *lengths, const float *qlen, float mincov, char *ws,
                  hipStream_t st, ScanParams *sp) {
     if (!queries_used_in_place(q, mode, pl)) {
-        hipLaunchKernelGGL(ms_prepare_queries_kernel, dim3((pl.d.nq_pad + 3) / 4), dim3(256), 0, st, q, nq, pl.d.nq_pad,
-                           mode != MS_MODE_IP_PRENORM ? 1 : 0, mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f, pl.qn(ws));
-        MS_LAUNCH_CHECK("ms_prepare_queries_kernel");
+        const int rc = ms_launch_prepare_queries(q, nq, pl.d.nq_pad, mode, pl.qn(ws), st);
+        if (rc) return rc;
     }
     if (mode == MS_MODE_COSINE_RAW && inv_norm == nullptr && n > 0) {
         hipLaunchKernelGGL(ms_row_inv_norms_kernel, row_grid(n), dim3(256), 0, st, db, n, 1e-8f, pl.inv(ws));

@@ -641,6 +641,101 @@ class _BatchScan:
         return dropped
 
 
+class _ChainStep:
+    """The multi-domain step of a db-search (multidomain.cosine_step, mode `exhaustive_cosine`): the query chains are the runs of
+    adjacent query rows with one chain id inside [q_lo, q_hi); a batch's step covers the chains that END in it, the reported
+    results of a chain's earlier rows are carried over on the host.  Target rows: the resident matrix when this process
+    holds all rows (one rank, not streamed), else the needed chain runs read from the database files (rank 0)."""
+
+    def __init__(self, qdb, q_lo: int, q_hi: int, target_db: dict, db_name: str, same: bool, exclude_self: bool, engine, scan,
+                 mincos: float, mincov: float, max_mapping_paths: int, times, timings):
+        from . import multidomain as md
+        from .dbquery import QueryDB
+        self.md, self.qdb, self.q_lo, self.engine, self.scan, self.target_db = md, qdb, q_lo, engine, scan, target_db
+        self.mincos, self.mincov, self.max_paths, self.times = float(mincos), float(mincov), int(max_mapping_paths), times
+        self.exclude_self = exclude_self
+        chains = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
+        self.chains = chains
+        self.run_end = np.empty(q_hi - q_lo, np.int64)          # one past the last row (global) of each query row's run
+        a = 0
+        while a < len(chains):
+            b = a + 1
+            while b < len(chains) and chains[b] == chains[a]:
+                b += 1
+            self.run_end[a:b] = q_lo + b
+            a = b
+        self.reader = qdb if same else QueryDB(db_name)
+        self.owns_reader = not same
+        self.resident = bool(sharded.rank_world()[1] == 1 and not scan.streamed)
+        if target_db["faiss"]:
+            self.score_mode = "ip_prenorm" if qdb.normalized else "ip"
+        else:
+            self.score_mode = "cosine"
+        if timings is not None:
+            timings["md_resident"] = self.resident
+            timings["md_candidates_skipped"] = 0
+        self.timings = timings
+        self.pending = []                                      # (global row, query name, its reported results) of the open chain
+        self.skipped = []
+
+    def close(self) -> None:
+        if self.owns_reader:
+            self.reader.close()
+
+    def _target_rows(self, rows):
+        if not self.resident:
+            return self.md.compact_target_rows(self.engine, self.reader, rows)
+        if self.target_db["faiss"]:
+            return self.scan.shard, None, rows - self.scan.lo
+        return self.target_db["database"], self.target_db["lengths"], rows - self.target_db["row_lo"]
+
+    def batch(self, b0: int, b1: int, query_dicts, results) -> list:
+        """The result tuples of the chains that end in query rows [b0, b1), in query-chain order."""
+        rows = self.pending + [(b0 + r, _query_name(qd), res) for r, (qd, res) in enumerate(zip(query_dicts, results))]
+        ended = [e for e in rows if self.run_end[e[0] - self.q_lo] <= b1]
+        self.pending = rows[len(ended):]
+        out, group, seen = [], [], set()
+        for e in ended:                                         # one step per batch -- split only where a chain id comes back
+            qc = self.chains[e[0] - self.q_lo]
+            if qc in seen and self.chains[group[-1][0] - self.q_lo] != qc:
+                out.extend(self._step(group))
+                group, seen = [], set()
+            group.append(e)
+            seen.add(qc)
+        if group:
+            out.extend(self._step(group))
+        return out
+
+    def _step(self, group) -> list:
+        md, engine = self.md, self.engine
+        r0, r1 = group[0][0], group[-1][0] + 1
+        chains = self.chains[r0 - self.q_lo: r1 - self.q_lo]
+        hits = md.group_hits([e[1] for e in group], chains, [e[2] for e in group])
+        if all(len(domains) < 2 for domains in hits.values()):
+            for qc in hits:
+                logger.debug("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+            return []
+        q_first, own = {}, {}
+        for i, qc in enumerate(chains):
+            if qc not in q_first:
+                q_first[qc] = i
+                if self.exclude_self:
+                    first, last = self.qdb.exclusion_ranges(r0 + i, r0 + i + 1, True)
+                    own[qc] = (int(first[0]), int(last[0]))
+        q_emb = engine.to_device(self.qdb.embeddings(r0, r1))
+        qlen = None
+        if self.score_mode == "cosine":
+            qlen = engine.to_device(np.asarray([len(s) for s in self.qdb.seqs(r0, r1)], dtype=np.float32))
+        skipped = []
+        res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader.store, self._target_rows, self.mincos,
+                             qlen=qlen, mincov=self.mincov if self.score_mode == "cosine" else 0.0, own_rows=own or None,
+                             max_mapping_paths=self.max_paths, log=logger.debug, skipped=skipped, times=self.times)
+        self.skipped.extend(skipped)
+        if self.timings is not None:
+            self.timings["md_candidates_skipped"] = len(self.skipped)
+        return res
+
+
 def _append_tsv(results, path: str, part: str, fields, header: bool) -> None:
     """One batch's rows behind what `path` holds already, written by results.write_search_results itself."""
     from .results import write_search_results
@@ -655,7 +750,9 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
                     search_type: str = "IP", skip_tmalign: bool = False, tmalign_backend: str = "auto",
                     query_batchsize: int = 4096, query_rows: Optional[str] = None, exclude_self: bool = False,
                     exclude_same_chain: bool = False, format_list=None, header: bool = False, metadata_json: bool = False,
-                    report_insignificant_hits: bool = False, engine=None, timings: Optional[dict] = None) -> int:
+                    report_insignificant_hits: bool = False, engine=None, timings: Optional[dict] = None,
+                    multi_domain_search: bool = False, multi_domain_mode: str = "exhaustive_cosine",
+                    max_mapping_paths: Optional[int] = None) -> int:
     """Search the rows of database `query_db` (all, or the slice query_rows = 'LO:HI') against database `db_name` and write
     `<output>_search.tsv` (+ `_search_insignificant.tsv`), in query-row order: `search` with a database in the place of the
     PDB files.  No structure is parsed or embedded -- the stored embeddings are the queries (dbquery.QueryDB), so the
@@ -666,6 +763,10 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     exclude_self / exclude_same_chain (query and target the SAME database): the query's own row / every row of its chain
     is taken out of its list EXACTLY: the scan fetches k' = k + the longest excluded run and the drop kernel removes
     them (include/merizo_search_amd.h).  mincos is the kernel's min_score: only surviving hits are retrieved.
+    multi_domain_search: also write `<output>_search_multi_dom.tsv`, the multi-domain search in mode `exhaustive_cosine` (the only
+    one here; multidomain.cosine_step): the query chains are the runs of adjacent query rows with one chain id, the hits that
+    seed the candidates are each batch's reported results, and with exclude_self a query chain is never its own candidate
+    (_ChainStep).  max_mapping_paths: multidomain.MAX_MAPPING_PATHS unless given.
     Everything else -- thresholds, hit records, columns -- is the code of dbsearch / dbsearch_faiss.  Returns the number of
     queries searched.  `timings`: a dict that receives which path ran ('in_place': the queries were row ranges of the resident
     matrix; 'streamed': the target went through engine.device_blocks) and HIP-event totals of the scan calls and the drop step."""
@@ -683,6 +784,8 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         _refuse("tmalign_backend must be one of %s, got %r" % (", ".join(tm.BACKENDS), tmalign_backend))
     if topk < 1 or query_batchsize < 1 or search_batchsize < 1:
         _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
+    if multi_domain_search and multi_domain_mode != "exhaustive_cosine":
+        _refuse("db-search --multi_domain_mode: only 'exhaustive_cosine' is available here, got %r." % (multi_domain_mode,))
     exclude_self = exclude_self or exclude_same_chain
     same = same_database(query_db, db_name)
     if exclude_self and not same:
@@ -729,8 +832,9 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         os.makedirs(tmp, exist_ok=True)
     search_output, all_output = output + "_search.tsv", output + "_search_insignificant.tsv"
     written = (search_output, all_output) if report_insignificant_hits else (search_output,)      # the files this run writes
+    multi_output = output + "_search_multi_dom.tsv"
     if rank == 0:
-        for out_path in written:
+        for out_path in written + ((multi_output,) if multi_domain_search else ()):
             if os.path.exists(out_path):
                 logger.warning(f"Search output file '{out_path}' already exists. Results will be overwritten!")
             open(out_path, "w").close()
@@ -749,6 +853,11 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     if timings is not None:
         timings["in_place"], timings["streamed"] = bool(in_place), scan.streamed
     d_lo, d_hi = engine.to_device(ex_lo), engine.to_device(ex_hi)        # once for the run: a batch's ranges are a slice
+    chain_step = None
+    if multi_domain_search and rank == 0:
+        from .multidomain import MAX_MAPPING_PATHS
+        chain_step = _ChainStep(qdb, q_lo, q_hi, target_db, db_name, same, exclude_self, engine, scan, mincos, mincov,
+                                MAX_MAPPING_PATHS if max_mapping_paths is None else max_mapping_paths, times, timings)
     md_all = {}
     tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
     t_loop = time.perf_counter()
@@ -785,6 +894,12 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         _append_tsv(results, search_output, part, fields, header and b0 == q_lo)
         if report_insignificant_hits:
             _append_tsv(all_results, all_output, part, fields, header and b0 == q_lo)
+        if chain_step is not None:
+            from .results import write_all_dom_search_results
+            write_all_dom_search_results(chain_step.batch(b0, b1, query_dicts, results), part, header and b0 == q_lo)
+            with open(part, "rb") as src, open(multi_output, "ab") as dst:
+                dst.write(src.read())
+            os.remove(part)
         if metadata_json:
             for out_path, per_batch in zip(written, (results, all_results)):
                 md_all.setdefault(out_path, []).extend(hit["metadata"] for per_query in per_batch for hit in per_query.values()
@@ -793,6 +908,8 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     times.finish()
     if timings is not None:
         timings["setup_s"], timings["loop_s"] = t_loop - t_start, time.perf_counter() - t_loop
+    if chain_step is not None:
+        chain_step.close()
     qdb.close()
     if rank == 0 and metadata_json:                                       # (results.write_search_results' file, for the whole run)
         import ast

@@ -21,6 +21,8 @@ Engine interface (tensors are torch tensors on the engine's device):
     merge_gathered(PackedExchange)                          -> (scores [nq,k], idx [nq,k])  multi-rank merge
     topk_drop_ranges(scores, idx, lo, hi, kout, min_score)  -> (scores [nq,kout], idx [nq,kout], count int32 [nq]): the lists without
                                                                the rows [lo[q], hi[q]) and without scores below min_score (db-search)
+    md_chain_scores(db, q, mode, cand, trows, mat_off, min_score, lengths, qlen, mincov) -> (scores [total], match int32 [ncand,2]):
+                                                               the multi-domain search's score matrices in the search's own arithmetic
     upload_rows(matrix, lo, hi)                             -> rows [lo,hi) of a host matrix as ONE device tensor
     device_blocks(blocks)                                   -> iterator of device tensors (out-of-core streaming)
     resident_budget(nq, k)                                  -> bytes a resident matrix may occupy
@@ -240,6 +242,20 @@ class HipEngine:
     def cluster_greedy(self, nbr_idx, nbr_score, lengths, min_score: float, mincov: float = 0.0):
         """Representatives and assignments from neighbour lists (ms_cluster_greedy) -> (rep, rep_score, info)."""
         return self._ops.cluster_greedy(nbr_idx, nbr_score, lengths, min_score, mincov)
+
+    def md_chain_scores(self, db, q, mode: str, cand, trows, mat_off, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
+                        total: Optional[int] = None):
+        """Score matrices of (query chain, target chain) candidates in the search's own arithmetic (ms_md_chain_scores).
+        mode: 'ip' = the scores of ip_topk(normalize_queries=True), 'ip_prenorm' = of ip_topk on queries used as given,
+        'cosine' = of cosine_topk over cosine_rows (with lengths / qlen / mincov) -> (scores [total], match [ncand,2]).
+        total: the floats the matrices take, when the caller packed them without gaps."""
+        ops = self._ops
+        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        out = None
+        if total is not None:           # (the caller laid the matrices out: no copy of the descriptors back to the host)
+            out = (self.torch.empty((int(total),), dtype=self.torch.float32, device=self.device),
+                   self.torch.empty((int(cand.shape[0]), 2), dtype=self.torch.int32, device=self.device))
+        return ops.md_chain_scores(db, q, code, cand, trows, mat_off, min_score, lengths=lengths, qlen=qlen, mincov=mincov, out=out)
 
     # -- database residency ----------------------------------------------------------
     STAGE_ROWS = 1 << 19          # 256 MiB pinned staging buffers

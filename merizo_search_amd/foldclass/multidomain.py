@@ -14,6 +14,13 @@ Step 3 needs a TM-align executable ($MERIZO_TMALIGN): without one the reference 
 mode either, and `multi_domain_search` raises -- unless tmalign_backend='hip', which aligns the pairs of ALL query
 chains in one GPU batch (ms_tmalign.hip) from the coordinates in memory, without files or processes.  Steps 1, 2 and 4 are plain functions, tested
 against outputs of the reference's own functions (tests/golden/multidomain.json).
+
+mode='exhaustive_cosine' (the "embscore mode" the reference leaves as a TODO, :202-203, :558-571) runs the same steps 1, 2 and
+4 with another step 3: the matrix holds the SEARCH'S OWN score of (query domain, database row) -- bit for bit the emb_score
+the per-domain search reports for that pair -- with entries below mincos set to 0.  All matrices of a call come from one
+launch of ms_md_chain_scores (`cosine_step`), which also takes chain_mappings' two early exits on the device:
+names and metadata are fetched only for the (query chain, hit chain) pairs that survive them.  No coordinates, no files, no
+processes, no TM-align binary.
 """
 from __future__ import annotations
 
@@ -36,6 +43,11 @@ logger = logging.getLogger(__name__)
 
 FIELD_SET_SEPARATOR = ","       # between the per-domain entries of one mapping
 FIELD_SEPARATOR = ":"           # inside an entry: query domain : hit domain : TM score
+
+MODES = ("exhaustive_tmalign", "exhaustive_cosine")
+# exhaustive_cosine: chain_mappings enumerates a Cartesian product; a (query chain, hit chain) pair with more paths than
+# this is skipped with a warning (at database scale one pair of 12-domain chains could run for hours)
+MAX_MAPPING_PATHS = 1_000_000
 
 _TWO_DIGITS = re.compile(r"[0-9]{2}$")
 _MERIZO_SUFFIX = re.compile(r"_merizo_[0-9]*$")
@@ -189,6 +201,15 @@ class _TargetStore:
         start, end = dbutil.retrieve_start_end_by_idx([row], pair[0])[0]
         return dbutil.retrieve_bytes(start, end, mm=pair[1], typeconv=conv)
 
+    def entry_name(self, row: int) -> str:
+        """The domain name entry() reports for a database row."""
+        return self.name(row) if self.faiss else os.path.basename(self.index[row][0]).replace(".pdb", "")
+
+    def name_meta(self, row: int):
+        """(domain name, metadata json) of a database row, as entry() gives them -- without its coordinates and sequence."""
+        metadata = self._blob(self.meta, row, dbutil.ascii_conv) if self.meta is not None else "{ }"
+        return self.entry_name(row), metadata
+
     def entry(self, row: int):
         """(domain name, coords [N,3], sequence, row, metadata json) of a database row (:426-466)."""
         metadata = self._blob(self.meta, row, dbutil.ascii_conv) if self.meta is not None else "{ }"
@@ -201,13 +222,20 @@ class _TargetStore:
 
 def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, device=None, fastmode: bool = False,
                         threads: int = -1, mintm: float = 0.5, inputs_from_easy_search: bool = False,
-                        mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto"):
+                        mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto",
+                        mincos: float = 0.5, mincov: float = 0.7, network=None, max_mapping_paths: int = MAX_MAPPING_PATHS):
     """The reference's multi_domain_search (:183-574): same arguments, same result tuples (feed
     them to results.write_all_dom_search_results).  `queries`: PDB file names (search) or domain
     dicts with 'coords', 'seq', 'name' (easy-search).  tmalign_backend: 'auto' = the TM-align binary (required),
-    'hip' = the GPU aligner on `device`."""
-    if mode != "exhaustive_tmalign":
+    'hip' = the GPU aligner on `device`.
+    mode='exhaustive_cosine': step 3 scores with the search's own embedding score instead (entries below `mincos` -> 0; the
+    `.pt` layout masks by `mincov` as its search does); needs no aligner.  `network`: the encoder the search ran with (set up
+    from `device` when absent) -- the query embeddings are recomputed with it, bit-identical to the search's."""
+    if mode not in MODES:
         raise ValueError("Unrecognised multi-domain search mode: " + mode)
+    if mode == "exhaustive_cosine":
+        return _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov,
+                                    network, threads, max_mapping_paths)
     check_backend(tmalign_backend, device)
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
@@ -313,3 +341,156 @@ def _multi_domain_hip(hits, structures, store, fastmode: bool, mintm: float, dev
             results.extend(chain_mappings(scores[:, cols], qc, str(hc), qds, [info[c] for c in cols]))
         logger.info("Finished multi-domain search for query chain %s." % qc)
     return results
+
+
+# ------------------------------------------------------------------ exhaustive_cosine ---
+def _query_structures(queries, inputs_from_easy_search: bool, pdb_chain: Optional[str]):
+    """(names, query chains, structures) of multi_domain_search's inputs (:183-245)."""
+    if not inputs_from_easy_search:
+        chains = pdb_chain.rstrip(",").split(",") if pdb_chain else ["A"] * len(queries)
+        if len(chains) == 1:
+            chains = chains * len(queries)
+        queries = [read_pdb(pdbfile=q, pdb_chain=c) for q, c in zip(queries, chains)]
+    names = [os.path.basename(q["name"]) for q in queries]
+    names = [n[: -len(".pdb")] if n.endswith(".pdb") else n for n in names]
+    query_chains = [_MERIZO_SUFFIX.sub("", n) for n in names] if inputs_from_easy_search else ["A"] * len(names)
+    return names, query_chains, list(queries)
+
+
+def chain_target_rows(qc: str, domains: dict, n_rows: int, name_of: Callable[[int], str], own_rows=None, log=logger.info):
+    """Step 2 for one query chain: the sorted database rows of every hit chain with at least as many domains as the query
+    chain has (_chain_entries' row logic), or None (with the reference's log line) when there is nothing to score.
+    own_rows = (lo, hi): hits inside that row range -- the query chain itself in a self-search -- seed no candidate."""
+    nqd = len(domains)
+    if nqd < 2:
+        log("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+        return None
+    rows = set()
+    for per_domain in domains.values():
+        for hit in per_domain:
+            if own_rows is not None and own_rows[0] <= hit["hi"] < own_rows[1]:
+                continue
+            chain_rows = sibling_rows(hit["hi"], hit["hc"], n_rows, name_of)
+            if len(chain_rows) >= nqd:
+                rows.update(chain_rows)
+    if not rows:
+        log("Query chain %s: every hit chain has fewer domains than the query; try a larger -k." % qc)
+        return None
+    return sorted(rows)
+
+
+def compact_target_rows(engine, reader, rows: np.ndarray):
+    """Target rows read from the database files and uploaded as a compact matrix -- the path of a process that does not hold
+    all rows resident (several ranks, a streamed target, `search` / `easy-search`).  reader: a dbquery.QueryDB of the target;
+    rows: sorted unique global rows.  -> (matrix on the device, lengths on the device or None, local index of each row).
+    `.pt` rows are normalised on the device by engine.cosine_rows (ms_l2_normalize_rows, eps 1e-8): the call the resident
+    copy was made with, so the bits are the resident copy's."""
+    rows = np.asarray(rows, dtype=np.int64)
+    parts, lens = [], []
+    a = 0
+    while a < len(rows):                                      # one read per run of adjacent rows (a chain is one run)
+        b = a + 1
+        while b < len(rows) and rows[b] == rows[b - 1] + 1:
+            b += 1
+        lo, hi = int(rows[a]), int(rows[b - 1]) + 1
+        parts.append(reader.embeddings(lo, hi))
+        if not reader.faiss:
+            lens.extend(len(s) for s in reader.seqs(lo, hi))
+        a = b
+    matrix = engine.to_device(np.concatenate(parts, axis=0) if parts else np.zeros((0, 128), np.float32))
+    if reader.faiss:
+        return matrix, None, np.arange(len(rows), dtype=np.int64)
+    return engine.cosine_rows(matrix), engine.to_device(np.asarray(lens, dtype=np.float32)), np.arange(len(rows), dtype=np.int64)
+
+
+def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable,
+                mincos: float, qlen=None, mincov: float = 0.0, own_rows: Optional[dict] = None,
+                max_mapping_paths: int = MAX_MAPPING_PATHS, log=logger.info, skipped: Optional[list] = None, times=None) -> list:
+    """Steps 2-4 of `exhaustive_cosine` for the query chains of `hits` (group_hits' dictionary) -> result tuples.
+    q_emb [nq,128] on the engine's device holds the query embeddings as the search took them, the domains of chain qc in
+    rows [q_first[qc], q_first[qc] + nqd) in the order of hits[qc]; score_mode: 'ip' (raw queries, faiss layout), 'ip_prenorm'
+    (stored faiss rows as queries) or 'cosine' (`.pt` layout, with qlen / mincov).  target_rows(sorted unique global rows) ->
+    (matrix, lengths or None, local index per row).  ONE engine.md_chain_scores call scores every (query chain, hit chain)
+    matrix; names and metadata are read for the pairs its match counts keep.  skipped: receives (qc, hc, paths) of the pairs
+    above max_mapping_paths; times: dbsearch._DeviceTimes, which then receives the span of the scoring call ('md_scores')."""
+    plans = []                                                # (qc, hc, q0, nqd, global rows of the hit chain)
+    for qc, domains in hits.items():
+        rows = chain_target_rows(qc, domains, store.n, store.name, own_rows.get(qc) if own_rows else None, log)
+        if rows is None:
+            continue
+        hit_chain = np.asarray([domid2chainid(store.entry_name(r)) for r in rows])
+        rows = np.asarray(rows, dtype=np.int64)
+        for hc in np.unique(hit_chain):
+            plans.append((qc, str(hc), int(q_first[qc]), len(domains), rows[hit_chain == hc]))
+    if not plans:
+        return []
+    needed = np.unique(np.concatenate([p[4] for p in plans]))
+    matrix, lengths, local = target_rows(needed)
+    cand = np.empty((len(plans), 4), np.int32)
+    mat_off = np.empty(len(plans), np.int64)
+    trows, t_off, m_off = [], 0, 0
+    for c, (_qc, _hc, q0, nqd, grows) in enumerate(plans):
+        cand[c] = (q0, nqd, t_off, len(grows))
+        mat_off[c] = m_off
+        trows.append(local[np.searchsorted(needed, grows)])
+        t_off += len(grows)
+        m_off += nqd * len(grows)
+    cand_d, trows_d, off_d = engine.to_device(cand), engine.to_device(np.concatenate(trows)), engine.to_device(mat_off)
+    t0 = times.mark() if times is not None else None
+    scores, match = engine.md_chain_scores(matrix, q_emb, score_mode, cand_d, trows_d, off_d, float(mincos),
+                                           lengths=lengths, qlen=qlen, mincov=float(mincov), total=m_off)
+    if times is not None:
+        times.add("md_scores", t0)
+    scores, match = scores.cpu().numpy(), match.cpu().numpy()
+    results = []
+    for c, (qc, hc, _q0, nqd, grows) in enumerate(plans):
+        if match[c, 0] != nqd or match[c, 1] < nqd:           # chain_mappings' two early exits
+            continue
+        tm = scores[mat_off[c]: mat_off[c] + nqd * len(grows)].reshape(nqd, len(grows))
+        paths = 1
+        for row in range(nqd):
+            paths *= int(np.count_nonzero(tm[row]))
+        if paths > max_mapping_paths:
+            logger.warning("multi-domain search: query chain %s x hit chain %s has %d candidate mappings (more than %d): skipped"
+                           % (qc, hc, paths, max_mapping_paths))
+            if skipped is not None:
+                skipped.append((qc, hc, paths))
+            continue
+        info = []
+        for r in grows:
+            hd, hm = store.name_meta(int(r))
+            info.append({"hd": hd, "hc": hc, "hi": int(r), "hm": hm})
+        results.extend(chain_mappings(tm, qc, hc, list(hits[qc].keys()), info))
+    return results
+
+
+def _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
+                         threads, max_mapping_paths):
+    """multi_domain_search(mode='exhaustive_cosine'): the query embeddings recomputed with the search's encoder (ragged
+    embedding is bit-identical to one-by-one), the target rows read from the database files (compact_target_rows)."""
+    if len(queries) == 1:
+        logger.warning("Cannot execute multi-domain search with only one query domain.")
+        return None
+    from .dbquery import QueryDB
+    names, query_chains, structures = _query_structures(queries, inputs_from_easy_search, pdb_chain)
+    if len(set(names)) != len(names):
+        raise ValueError("multi-domain search: query domain names must be unique")
+    hits = group_hits(names, query_chains, search_results)
+    if network is None:
+        from . import dbsearch
+        network, _device = dbsearch.network_setup(threads=threads, device=device)
+    engine = network.engine
+    order = [i for qc in hits for i, c in enumerate(query_chains) if c == qc]        # the domains of a chain made adjacent
+    q_first, at = {}, 0
+    for qc, domains in hits.items():
+        q_first[qc] = at
+        at += len(domains)
+    q_emb = engine.to_device(network.embed_many([structures[i]["coords"] for i in order]))
+    reader = QueryDB(db_name)
+    try:
+        qlen = None if reader.faiss else engine.to_device(np.asarray([len(structures[i]["seq"]) for i in order], dtype=np.float32))
+        return cosine_step(hits, q_first, q_emb, "ip" if reader.faiss else "cosine", engine, reader.store,
+                           lambda rows: compact_target_rows(engine, reader, rows), mincos, qlen=qlen,
+                           mincov=mincov if not reader.faiss else 0.0, max_mapping_paths=max_mapping_paths)
+    finally:
+        reader.close()

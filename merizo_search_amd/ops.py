@@ -496,6 +496,68 @@ def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float 
     return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
 
 
+def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
+                    out=None, workspace=None):
+    """Score matrices of (query chain, target chain) candidates (ms_md_chain_scores: the definition is the header's).
+    db float32 [n,128], q float32 [nq,128] (raw, as the search of `mode` takes them); cand int32 [ncand,4] = (q0, nqd, t_off,
+    nhd), trows int64 [ntrows], mat_off int64 [ncand]: tensors, or host arrays that are uploaded.
+    -> (scores float32 [total], match int32 [ncand,2]); candidate c's matrix is scores[mat_off[c]:][:nqd * nhd] row-major,
+    every cell bit for bit the score ip_topk gives that (query, row) in `mode`, below min_score -> +0.0.  Asynchronous.
+    out: optional preallocated (scores, match) -- without it `scores` is sized from the descriptors (zero-filled, so gaps
+    between matrices read 0; device descriptors cost a copy to the host for that); workspace: optional uint8 tensor of
+    ms_md_chain_scores_workspace_bytes(nq)."""
+    torch = _lib.require_gpu()
+    _f32_cuda(db, "db", DIM)
+    _f32_cuda(q, "q", DIM)
+    n, nq = db.shape[0], q.shape[0]
+    for name, t, size in (("lengths", lengths, n), ("qlen", qlen, nq)):
+        if t is not None:
+            _f32_cuda(t, name)
+            if t.numel() != size:
+                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+
+    def dev(x, dtype, name, cols=None):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
+        if t.is_floating_point():
+            raise MerizoHipError(f"md_chain_scores: {name}: expected integers, got {t.dtype}")
+        t = t.to(device=db.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+        if (cols is None and t.dim() != 1) or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
+            raise MerizoHipError(f"md_chain_scores: {name}: unexpected shape {tuple(t.shape)}")
+        return t
+
+    cand_t, trows_t, off_t = dev(cand, np.int32, "cand", 4), dev(trows, np.int64, "trows"), dev(mat_off, np.int64, "mat_off")
+    ncand = cand_t.shape[0]
+    if off_t.numel() != ncand:
+        raise MerizoHipError(f"md_chain_scores: mat_off: expected {ncand} entries, got {off_t.numel()}")
+    if out is None:
+        c_h = (cand if not isinstance(cand, torch.Tensor) else cand.cpu().numpy()).reshape(-1, 4).astype(np.int64)
+        o_h = np.asarray(mat_off if not isinstance(mat_off, torch.Tensor) else mat_off.cpu().numpy(), dtype=np.int64).reshape(-1)
+        ends = o_h + np.clip(c_h[:, 1], 0, None) * np.clip(c_h[:, 3], 0, None)
+        total = int(ends.max()) if ncand else 0
+        scores = torch.zeros((max(total, 1),), dtype=torch.float32, device=db.device)[:total]
+        match = torch.empty((ncand, 2), dtype=torch.int32, device=db.device)
+    else:
+        scores, match = out
+        if (scores.dtype != torch.float32 or match.dtype != torch.int32 or tuple(match.shape) != (ncand, 2)
+                or not (scores.is_contiguous() and match.is_contiguous()) or not scores.is_cuda):
+            raise MerizoHipError("md_chain_scores: out must be contiguous (float32 [total], int32 [ncand,2]) CUDA tensors")
+    if ncand == 0:                      # (nothing to score: the library would not launch either)
+        return scores, match
+    lib = _lib.load()
+    need = int(lib.ms_md_chain_scores_workspace_bytes(nq))
+    if need == 0:
+        raise MerizoHipError(f"ms_md_chain_scores_workspace_bytes rejected nq={nq}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise MerizoHipError("md_chain_scores: workspace must be a contiguous uint8 tensor")
+    with _on(db, q, lengths, qlen, cand_t, trows_t, off_t, scores, match, workspace) as d:
+        check(lib.ms_md_chain_scores(ptr(db), n, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov), ptr(cand_t), ncand,
+                                     ptr(trows_t), trows_t.numel(), ptr(off_t), float(min_score), ptr(scores), ptr(match),
+                                     ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scores")
+    return scores, match
+
+
 class EgnnEncoder:
     """The Foldclass structure encoder on one GPU: prepared weights + positional table.
 

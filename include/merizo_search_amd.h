@@ -286,6 +286,39 @@ int ms_md_chain_scores(const float *db, int64_t n, const float *q, int nq, int m
                        const int64_t *mat_off, float min_score, float *out_scores, int32_t *out_match, void *workspace,
                        size_t workspace_bytes, ms_stream_t stream);
 
+/* The pass over ALL rows of the multi-domain search's `database_cosine` mode: which (query chain, target chain) pairs of a
+ * whole database pass the two early exits of the mapping step -- the pairs ms_md_chain_scores would report with
+ * out_match == {nqd, >= nqd} if it were given every pair as a candidate -- found in one read of the rows, without matrices.
+ * Target chain c is the run of rows [chain_start[c], chain_start[c + 1]) of db [n,128] (chain_start int64 [nchains + 1],
+ * device; database rows of one chain are adjacent).  Rules: chain_start[0] == 0, chain_start[nchains] == n, strictly
+ * increasing.  The table is data, not trusted: it is VALIDATED by a small launch of its own before any row is read; a table
+ * that breaks a rule gives *out_count = -1 and no pair, and no address outside db [0, n) is ever formed from it.
+ * Query chain g is rows [q0, q0 + nqd) of q [nq,128], with qchain int32 [nqc][2] = {q0, nqd} (device).
+ *   cell (i, j) of the pair (g, c) = EXACTLY the cell ms_md_chain_scores writes for query q0 + i and row chain_start[c] + j in
+ *        `mode` (MS_MODE_IP_PRENORM, MS_MODE_IP_NORMQ or MS_MODE_COSINE_UNIT): the queries prepared by the scan's own
+ *        preparation launch into the workspace, the same chain of 128 fmaf, the length mask of MS_MODE_COSINE_UNIT (lengths
+ *        float32 [n], qlen float32 [nq], mincov; NULL NULL = no mask; NULL in the other modes), and the same cut: NaN or
+ *        < min_score counts as +0.0f, a score equal to min_score stays, -0.0 is zero, -inf cuts nothing;
+ *   (g, c) QUALIFIES iff every one of the nqd rows of that matrix has a non-zero cell and at least nqd columns have one.
+ * *out_count (int64, device) = the number of qualifying pairs over all (g, c); the first min(count, cap) slots of out_pairs
+ * (int64 [cap][2] = {query chain, target chain}, device) hold distinct qualifying pairs in unspecified order; nothing is
+ * written at or behind slot cap; cap == 0 only counts (out_pairs may then be NULL).
+ * out_qstatus int32 [nqc] (device) = 0, or -1 for a descriptor with nqd < 1, nqd > 64 or [q0, q0 + nqd) outside [0, nq]: such a
+ * query chain reports no pair.  64 query domains per query chain is the limit of this entry point (one 64-bit mask of matched
+ * query domains per target chain).  A target chain may have ANY number of rows: one longer than a wave's tile of 64 rows is
+ * looped over (there is no 4096 limit here).
+ * nqc == 0, nchains == 0 or n == 0 succeed with *out_count = 0.  MS_ERR_ARG: NULL pointers, nq < 1, n, nchains, nqc or cap < 0,
+ * another mode, a NaN min_score, db or workspace not 16-byte aligned; MS_ERR_WORKSPACE: fewer than
+ * ms_md_chain_scan_workspace_bytes(n, nq) bytes (0 for nq < 1 or n < 0).
+ * Asynchronous on `stream`, never allocates, vector stores only.  The slot counter and the table's status word live in the
+ * workspace and are reset by the call itself: a workspace serves the next call without any clean-up by the host.
+ * One lane per target row, whole chains per wave.  Backward compatible additions: ms_version() stays 210. */
+size_t ms_md_chain_scan_workspace_bytes(int64_t n, int nq);
+int ms_md_chain_scan(const float *db, int64_t n, const int64_t *chain_start, int64_t nchains, const float *q, int nq, int mode,
+                     const float *lengths, const float *qlen, float mincov, const int32_t *qchain, int nqc, float min_score,
+                     int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, void *workspace,
+                     size_t workspace_bytes, ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

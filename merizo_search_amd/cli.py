@@ -15,6 +15,8 @@ every domain of a query chain.  `--multi_domain_mode exhaustive_tmalign` (the re
 query domain with every domain of every hit chain and needs a TM-align binary or `--tmalign_backend hip`;
 `exhaustive_cosine` (the only mode of db-search, where the query chains are the runs of adjacent query rows with one chain id)
 scores those pairs with the search's own embedding score on the GPU and needs neither (foldclass/multidomain.py).
+`database_cosine` (search and easy-search) gives exhaustive_cosine's answer for the WHOLE database -- every target chain, not only
+the chains the top-k lists name -- from one more pass over the rows on the GPU: it needs no aligner and does not depend on -k.
 
 `db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
 against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
@@ -71,11 +73,13 @@ def _add_search_flags(p: argparse.ArgumentParser, default_format: str) -> None:
                    help="Search DB for entries that match all query domains (all query structures are treated as single "
                         "domains coming from one chain).  'exhaustive_tmalign' needs a TM-align binary ($MERIZO_TMALIGN) or "
                         "--tmalign_backend hip.")
-    p.add_argument("--multi_domain_mode", type=str, default="exhaustive_tmalign", choices=["exhaustive_tmalign", "exhaustive_cosine"],
+    p.add_argument("--multi_domain_mode", type=str, default="exhaustive_tmalign",
+                   choices=["exhaustive_tmalign", "exhaustive_cosine", "database_cosine"],
                    help="If --multi_domain_search is used, specifies the multi-domain search mode. 'exhaustive_tmalign': TM-align "
                         "every query domain with every domain of every hit chain. 'exhaustive_cosine': score those pairs with "
                         "the search's own embedding score on the GPU instead (entries below --mincos count as no match); needs "
-                        "no TM-align binary.")
+                        "no TM-align binary. 'database_cosine': exhaustive_cosine's scores and output for EVERY chain of the database, "
+                        "found by one pass over all its rows on the GPU; needs no aligner and does not depend on -k.")
     p.add_argument("--skip_tmalign", action="store_true", default=False,
                    help="Embedding-only search (automatic when no TM-align binary is found and --tmalign_backend is auto).")
     p.add_argument("--tmalign_backend", type=str, default="auto", choices=["auto", "hip"],
@@ -153,7 +157,8 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         if os.path.exists(path):
             logging.warning(f"Search output file '{path}' already exists. Results will be overwritten!")
     multi_output = args.output + "_search_multi_dom.tsv"
-    cosine_md = args.multi_domain_search and args.multi_domain_mode == "exhaustive_cosine"
+    cosine_md = args.multi_domain_search and args.multi_domain_mode in ("exhaustive_cosine", "database_cosine")
+    database_md = args.multi_domain_search and args.multi_domain_mode == "database_cosine"
     if args.multi_domain_search:
         if not cosine_md and not hip and tm.find_tmalign() is None:
             logging.error("--multi_domain_search aligns every query domain with every candidate target domain and needs a "
@@ -165,11 +170,21 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
     if cosine_md:       # the multi-domain step re-embeds the query domains with the encoder the search runs with
         from .foldclass import dbsearch as _ds
         network, _device = _ds.network_setup(threads=args.threads, device=args.device, weights_path=args.weights)
+    target_db = None
+    if database_md:     # ONE open (and one upload) of the database for the search and for the multi-domain step's scan of all rows
+        target_db = _ds.read_database(db_name=args.db_name, device=args.device, engine=network.engine)
     results, all_results = run_dbsearch(
-        network=network, inputs=inputs, db_name=args.db_name, tmp=tmp, device=args.device, topk=args.topk, fastmode=args.fastmode,
+        target_db=target_db, network=network, inputs=inputs, db_name=args.db_name, tmp=tmp, device=args.device, topk=args.topk, fastmode=args.fastmode,
         threads=args.threads, mincos=args.mincos, mintm=args.mintm, mincov=args.mincov, inputs_are_ca=inputs_are_ca,
         pdb_chain=pdb_chain, search_batchsize=args.search_batchsize, search_type=args.search_metric,
         skip_tmalign=skip, weights_path=args.weights, tmalign_backend=args.tmalign_backend)
+    md_kwargs = dict(queries=inputs, db_name=args.db_name, tmp_root=tmp, device=args.device, fastmode=args.fastmode, threads=args.threads,
+                     mintm=args.mintm, inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain,
+                     tmalign_backend=args.tmalign_backend, mincos=args.mincos, mincov=args.mincov, network=network)
+    mda = None
+    if database_md:     # every rank scans its shard of the database and takes part in the gather; the mode reads no search_results
+        from .foldclass.multidomain import multi_domain_search
+        mda = multi_domain_search(search_results=None, target_db=target_db, search_batchsize=args.search_batchsize, **md_kwargs)
     if sharded.rank_world()[0] != 0:
         return                                            # every rank searched its shard; rank 0 reports
     fields = _embedding_only_format(fields, skip)
@@ -183,10 +198,8 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         # passes inputs_from_easy_search=True here, which fails on file names; its stated intent is one chain 'A').
         from .foldclass.multidomain import multi_domain_search
         from .foldclass.results import write_all_dom_search_results
-        mda = multi_domain_search(queries=inputs, search_results=results, db_name=args.db_name, tmp_root=tmp, device=args.device,
-                                  fastmode=args.fastmode, threads=args.threads, mintm=args.mintm,
-                                  inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain,
-                                  tmalign_backend=args.tmalign_backend, mincos=args.mincos, mincov=args.mincov, network=network)
+        if not database_md:
+            mda = multi_domain_search(search_results=results, **md_kwargs)
         write_all_dom_search_results(mda, multi_output, args.output_headers)
 
 

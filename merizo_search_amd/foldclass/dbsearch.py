@@ -495,8 +495,10 @@ def _resident_shard(target_dict: dict, engine, dbmm, lo: int, hi: int, nq: int, 
 def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bool, threads: int, mincos: float,
                  mintm: float, mincov: float, inputs_are_ca: bool = False, search_batchsize: int = 262144,
                  search_type: str = "IP", pdb_chain: Optional[str] = None, skip_tmalign: bool = False,
-                 network=None, weights_path: Optional[str] = None, tmalign_backend: str = "auto"):
+                 network=None, weights_path: Optional[str] = None, tmalign_backend: str = "auto", target_db: Optional[dict] = None):
     """Set up the encoder, open the database, search every input (dbsearch.py:475-551).
+    target_db: the database opened already (read_database's dict, with the engine of `network`); None = opened here.  A caller
+    that goes on with the same dict (the multi-domain mode `database_cosine`) finds the rows this search made resident in it.
     Returns (search_results, all_search_results): one dict rank -> hit per input, twice.
     tmalign_backend: 'auto' = the TM-align binary if one is found, else an embedding-only search; 'hip' = the GPU
     aligner (needs a cuda device).  skip_tmalign wins over both."""
@@ -512,7 +514,8 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
         logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
                        "TM-align columns are unavailable")
         skip_tmalign = True
-    target_db = read_database(db_name=db_name, device=device, engine=network.engine)
+    if target_db is None:
+        target_db = read_database(db_name=db_name, device=device, engine=network.engine)
 
     if target_db["faiss"]:
         if search_batchsize < 1:

@@ -23,6 +23,9 @@ Engine interface (tensors are torch tensors on the engine's device):
                                                                the rows [lo[q], hi[q]) and without scores below min_score (db-search)
     md_chain_scores(db, q, mode, cand, trows, mat_off, min_score, lengths, qlen, mincov) -> (scores [total], match int32 [ncand,2]):
                                                                the multi-domain search's score matrices in the search's own arithmetic
+    md_chain_scan(db, chain_start, q, mode, qchain, min_score, lengths, qlen, mincov) -> (pairs int64 [m,2] sorted, qstatus int32 [nqc]),
+                                                               numpy: the (query chain, target chain) pairs of ALL rows that pass the
+                                                               mapping step's two early exits (mode `database_cosine`)
     upload_rows(matrix, lo, hi)                             -> rows [lo,hi) of a host matrix as ONE device tensor
     device_blocks(blocks)                                   -> iterator of device tensors (out-of-core streaming)
     resident_budget(nq, k)                                  -> bytes a resident matrix may occupy
@@ -256,6 +259,15 @@ class HipEngine:
             out = (self.torch.empty((int(total),), dtype=self.torch.float32, device=self.device),
                    self.torch.empty((int(cand.shape[0]), 2), dtype=self.torch.int32, device=self.device))
         return ops.md_chain_scores(db, q, code, cand, trows, mat_off, min_score, lengths=lengths, qlen=qlen, mincov=mincov, out=out)
+
+    def md_chain_scan(self, db, chain_start, q, mode: str, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0):
+        """The pairs (query chain, target chain) of a whole matrix whose score matrix passes chain_mappings' two early exits
+        (ms_md_chain_scan; the cells are md_chain_scores' cells).  chain_start int64 [nchains + 1]: the runs of rows that are
+        the target chains; qchain int32 [nqc,2] = (first query row, query domains); mode as md_chain_scores takes it.
+        -> (pairs [m,2] sorted, qstatus [nqc]; -1 = a query chain this call does not serve, e.g. more than 64 domains)."""
+        ops = self._ops
+        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        return ops.md_chain_scan(db, chain_start, q, code, qchain, min_score, lengths=lengths, qlen=qlen, mincov=mincov)
 
     # -- database residency ----------------------------------------------------------
     STAGE_ROWS = 1 << 19          # 256 MiB pinned staging buffers

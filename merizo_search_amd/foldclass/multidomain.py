@@ -21,6 +21,11 @@ the per-domain search reports for that pair -- with entries below mincos set to 
 launch of ms_md_chain_scores (`cosine_step`), which also takes chain_mappings' two early exits on the device:
 names and metadata are fetched only for the (query chain, hit chain) pairs that survive them.  No coordinates, no files, no
 processes, no TM-align binary.
+
+mode='database_cosine'  asks the same question of the WHOLE database instead of the chains the top-k lists
+name: ms_md_chain_scan reads every row once and reports every (query chain, target chain) pair that passes chain_mappings' two
+early exits (`database_candidates`; the target chains are the runs of adjacent rows with one chain id, `chain_runs`), and the
+second half of `cosine_step` (`score_plans`) turns those pairs into the same result tuples.  Its answer does not depend on -k.
 """
 from __future__ import annotations
 
@@ -44,7 +49,8 @@ logger = logging.getLogger(__name__)
 FIELD_SET_SEPARATOR = ","       # between the per-domain entries of one mapping
 FIELD_SEPARATOR = ":"           # inside an entry: query domain : hit domain : TM score
 
-MODES = ("exhaustive_tmalign", "exhaustive_cosine")
+MODES = ("exhaustive_tmalign", "exhaustive_cosine", "database_cosine")
+SCAN_MAX_DOMAINS = 64           # database_cosine: query domains per query chain ms_md_chain_scan serves (include/merizo_search_amd.h)
 # exhaustive_cosine: chain_mappings enumerates a Cartesian product; a (query chain, hit chain) pair with more paths than
 # this is skipped with a warning (at database scale one pair of 12-domain chains could run for hours)
 MAX_MAPPING_PATHS = 1_000_000
@@ -61,6 +67,21 @@ def domid2chainid(domain_id: str) -> str:
     stem = os.path.basename(domain_id).rstrip(".pdb")
     stem = _TWO_DIGITS.sub("", stem).rstrip("_")
     return stem[: -len("_TED")] if stem.endswith("_TED") else stem
+
+
+def chain_runs(names: Sequence[str]) -> np.ndarray:
+    """int64 [nchains + 1]: the first row of every run of adjacent names with one domid2chainid (its rstrip('.pdb') quirk
+    included), closed by len(names) -- the target chains of mode `database_cosine`, where a chain IS a run of rows.  Two runs
+    with one chain id that are not adjacent are two chains here (`exhaustive_cosine` would merge them by name; the reference
+    assumes adjacency, :363-394).  A plain loop: about a microsecond-scale call of domid2chainid per name."""
+    starts, prev = [], None
+    for row, name in enumerate(names):
+        chain = domid2chainid(name)
+        if chain != prev:
+            starts.append(row)
+            prev = chain
+    starts.append(len(names))
+    return np.asarray(starts, dtype=np.int64)
 
 
 def chain_mappings(tm: np.ndarray, query_chain: str, hit_chain: str, query_domains: Sequence[str],
@@ -187,6 +208,20 @@ class _TargetStore:
         self.maps.append((mm, handle))
         return mm
 
+    def stored_names(self, lo: int = 0, hi: Optional[int] = None) -> List[str]:
+        """The names of rows [lo, hi) as stored (the `.pt` index keeps paths): what domid2chainid is applied to."""
+        hi = self.n if hi is None else hi
+        if self.faiss:
+            rec = np.frombuffer(self.names[lo * dbutil.NAME_RECORD: hi * dbutil.NAME_RECORD], dtype="S%d" % dbutil.NAME_RECORD)
+            return [r.decode().rstrip() for r in rec]
+        return [self.index[r][0] for r in range(lo, hi)]
+
+    def chain_starts(self) -> np.ndarray:
+        """chain_runs of all rows, computed once per open database."""
+        if getattr(self, "_chain_starts", None) is None:
+            self._chain_starts = chain_runs(self.stored_names())
+        return self._chain_starts
+
     def close(self):
         for mm, handle in self.maps:
             mm.close()
@@ -223,16 +258,25 @@ class _TargetStore:
 def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, device=None, fastmode: bool = False,
                         threads: int = -1, mintm: float = 0.5, inputs_from_easy_search: bool = False,
                         mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto",
-                        mincos: float = 0.5, mincov: float = 0.7, network=None, max_mapping_paths: int = MAX_MAPPING_PATHS):
+                        mincos: float = 0.5, mincov: float = 0.7, network=None, max_mapping_paths: int = MAX_MAPPING_PATHS,
+                        target_db: Optional[dict] = None, search_batchsize: int = 262144):
     """The reference's multi_domain_search (:183-574): same arguments, same result tuples (feed
     them to results.write_all_dom_search_results).  `queries`: PDB file names (search) or domain
     dicts with 'coords', 'seq', 'name' (easy-search).  tmalign_backend: 'auto' = the TM-align binary (required),
     'hip' = the GPU aligner on `device`.
     mode='exhaustive_cosine': step 3 scores with the search's own embedding score instead (entries below `mincos` -> 0; the
     `.pt` layout masks by `mincov` as its search does); needs no aligner.  `network`: the encoder the search ran with (set up
-    from `device` when absent) -- the query embeddings are recomputed with it, bit-identical to the search's."""
+    from `device` when absent) -- the query embeddings are recomputed with it, bit-identical to the search's.
+    mode='database_cosine': the lines `exhaustive_cosine` would write if every database row at or above mincos were a hit, from
+    one pass over all rows (ms_md_chain_scan); search_results is not read (the answer does not depend on -k).  target_db: the
+    dict the search opened this database into (dbsearch.read_database) -- its resident rows are then scanned in place; without
+    it, or when they did not fit, the rows are streamed from the files in blocks of search_batchsize.  Under a process group
+    EVERY rank must call it (each scans its shard); ranks other than 0 get None."""
     if mode not in MODES:
         raise ValueError("Unrecognised multi-domain search mode: " + mode)
+    if mode == "database_cosine":
+        return _multi_domain_embedding(queries, None, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
+                                       threads, max_mapping_paths, True, target_db, search_batchsize)
     if mode == "exhaustive_cosine":
         return _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov,
                                     network, threads, max_mapping_paths)
@@ -413,7 +457,15 @@ def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, s
     (matrix, lengths or None, local index per row).  ONE engine.md_chain_scores call scores every (query chain, hit chain)
     matrix; names and metadata are read for the pairs its match counts keep.  skipped: receives (qc, hc, paths) of the pairs
     above max_mapping_paths; times: dbsearch._DeviceTimes, which then receives the span of the scoring call ('md_scores')."""
-    plans = []                                                # (qc, hc, q0, nqd, global rows of the hit chain)
+    plans = hit_chain_plans(hits, q_first, store, own_rows, log)
+    return score_plans(plans, hits, q_emb, score_mode, engine, store, target_rows, mincos, qlen=qlen, mincov=mincov,
+                       max_mapping_paths=max_mapping_paths, skipped=skipped, times=times)
+
+
+def hit_chain_plans(hits, q_first: Dict[str, int], store: "_TargetStore", own_rows: Optional[dict] = None, log=logger.info) -> list:
+    """cosine_step's first half: (qc, hc, q0, nqd, global rows of the hit chain) for every chain the hits of a query chain name
+    (step 2), query chains in the order of `hits`, hit chains per query chain in np.unique order of their chain id."""
+    plans = []
     for qc, domains in hits.items():
         rows = chain_target_rows(qc, domains, store.n, store.name, own_rows.get(qc) if own_rows else None, log)
         if rows is None:
@@ -422,6 +474,14 @@ def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, s
         rows = np.asarray(rows, dtype=np.int64)
         for hc in np.unique(hit_chain):
             plans.append((qc, str(hc), int(q_first[qc]), len(domains), rows[hit_chain == hc]))
+    return plans
+
+
+def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable, mincos: float, qlen=None,
+                mincov: float = 0.0, max_mapping_paths: int = MAX_MAPPING_PATHS, skipped: Optional[list] = None, times=None) -> list:
+    """cosine_step's second half: plans (qc, hc, q0, nqd, global rows) -> result tuples.  ONE engine.md_chain_scores call for all
+    matrices, chain_mappings' two early exits from its match counts, the max_mapping_paths skip, names and metadata for the
+    pairs that remain, chain_mappings."""
     if not plans:
         return []
     needed = np.unique(np.concatenate([p[4] for p in plans]))
@@ -464,10 +524,117 @@ def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, s
     return results
 
 
+# ------------------------------------------------------------------ database_cosine ---
+def clip_chain_table(starts: np.ndarray, a: int, b: int):
+    """The chain table of rows [a, b) (a < b) of a database whose chains start at `starts` (chain_runs), local to a:
+    -> (int64 table [m + 1] from 0 to b - a, global number of its first chain, first chain cut by a?, last chain cut by b?)."""
+    first = int(np.searchsorted(starts, a, side="right")) - 1
+    last = int(np.searchsorted(starts, b, side="left"))
+    table = np.clip(starts[first: last + 1], a, b) - a
+    return np.ascontiguousarray(table, dtype=np.int64), first, bool(starts[first] < a), bool(starts[last] > b)
+
+
+def range_candidates(starts: np.ndarray, a: int, b: int, nqc: int, scan: Callable) -> np.ndarray:
+    """The candidates a process finds in rows [a, b) -- its shard, or one streamed block: int64 [m,2] = (query chain, GLOBAL
+    target chain).  scan(table) -> the qualifying (query chain, local chain) pairs of those rows under the clipped table.
+    The edge rule: the verdict on a chain that a or b cuts was formed on a part of its rows, so it is discarded and the chain
+    becomes a candidate of EVERY query chain (at most two chains per range; the scoring half decides them exactly, on all their
+    rows).  No state crosses ranges."""
+    if b <= a or nqc < 1:
+        return np.zeros((0, 2), np.int64)
+    table, first, cut_first, cut_last = clip_chain_table(starts, a, b)
+    pairs = np.asarray(scan(table), dtype=np.int64).reshape(-1, 2)
+    cut = sorted(({0} if cut_first else set()) | ({len(table) - 2} if cut_last else set()))
+    pairs = pairs[~np.isin(pairs[:, 1], cut)] + np.asarray([0, first], np.int64)
+    extra = np.asarray([(g, first + c) for c in cut for g in range(nqc)], dtype=np.int64).reshape(-1, 2)
+    return np.concatenate([pairs, extra], axis=0)
+
+
+def merge_candidates(parts: Sequence[np.ndarray]) -> np.ndarray:
+    """Candidate lists of several ranges -> one list without duplicates, sorted by (query chain, target chain)."""
+    parts = [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p in parts]
+    if not parts:
+        return np.zeros((0, 2), np.int64)
+    return np.unique(np.concatenate(parts, axis=0), axis=0)
+
+
+def database_candidates(engine, reader, target_db: Optional[dict], starts: np.ndarray, q_emb, score_mode: str, qchain: np.ndarray,
+                        mincos: float, qlen, mincov: float, search_batchsize: int = 262144) -> np.ndarray:
+    """ms_md_chain_scan over this process's rows of the database -> the candidates of ALL rows, identical on every rank (a
+    collective under a process group: sharded.gather_pairs).  The rows: the resident copy the search left in target_db (the
+    `.pt` rows as dbsearch._to_engine normalised them, the faiss shard of target_db['_resident']) read in place; else streamed
+    from the files once more, block by block (engine.device_blocks), each block a range of its own (range_candidates)."""
+    from . import sharded
+    rank, world = sharded.rank_world()
+    lo, hi = sharded.shard_bounds(reader.n, world, rank)
+    nqc = int(qchain.shape[0])
+    qchain_d = engine.to_device(np.ascontiguousarray(qchain, dtype=np.int32))
+    parts = []
+
+    def scan_block(block, a, lengths=None):
+        scan = lambda table: engine.md_chain_scan(block, engine.to_device(table), q_emb, score_mode, qchain_d, float(mincos),
+                                                  lengths=lengths, qlen=qlen, mincov=float(mincov))[0]
+        parts.append(range_candidates(starts, a, a + int(block.shape[0]), nqc, scan))
+
+    resident = None
+    if target_db is not None and reader.faiss:
+        cache = target_db.get("_resident") or {}
+        if cache.get("engine") is engine and cache.get("span") == (lo, hi):
+            resident = (cache["shard"], None)
+    elif target_db is not None and target_db.get("_engine") is engine and (target_db["row_lo"], target_db["row_hi"]) == (lo, hi):
+        resident = (target_db["database"], target_db["lengths"])
+    if hi > lo and resident is not None:
+        logger.info("multi-domain search: scanning the %d resident rows of this process for matching chains" % (hi - lo))
+        scan_block(resident[0], lo, resident[1])
+    elif hi > lo:
+        step = max(1, int(search_batchsize))
+        logger.info("multi-domain search: the database rows are not resident: streaming rows %d..%d once more for the chain scan, "
+                    "in blocks of %d" % (lo, hi - 1, step))
+        if reader.faiss:
+            a = lo
+            for block in engine.device_blocks(dbutil.db_iterator(reader.matrix[lo:hi], step)):
+                scan_block(block, a)
+                a += int(block.shape[0])
+        else:
+            for a in range(lo, hi, step):
+                b = min(hi, a + step)
+                rows = engine.cosine_rows(engine.to_device(reader.embeddings(a, b)))
+                scan_block(rows, a, engine.to_device(np.asarray([len(x) for x in reader.seqs(a, b)], dtype=np.float32)))
+    return merge_candidates([sharded.gather_pairs(merge_candidates(parts), engine.device)])
+
+
+def candidate_plans(pairs: np.ndarray, served: Sequence[str], hits, q_first: Dict[str, int], starts: np.ndarray,
+                    store: "_TargetStore") -> list:
+    """Candidates (index into `served`, target chain number) -> the plans score_plans takes, in `exhaustive_cosine`'s order: query
+    chains as `hits` has them, target chains per query chain by chain id (np.unique's order; two runs with one id: by row)."""
+    plans = []
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    for g, qc in enumerate(served):
+        nqd = len(hits[qc])
+        chains = []
+        for c in pairs[pairs[:, 0] == g, 1]:
+            a, b = int(starts[c]), int(starts[c + 1])
+            if b - a >= nqd:                                  # (a cut chain is everybody's candidate; fewer domains cannot match)
+                chains.append((domid2chainid(store.entry_name(a)), a, b))
+        for hc, a, b in sorted(chains):
+            plans.append((qc, hc, int(q_first[qc]), nqd, np.arange(a, b, dtype=np.int64)))
+    return plans
+
+
 def _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
                          threads, max_mapping_paths):
     """multi_domain_search(mode='exhaustive_cosine'): the query embeddings recomputed with the search's encoder (ragged
     embedding is bit-identical to one-by-one), the target rows read from the database files (compact_target_rows)."""
+    return _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
+                                   threads, max_mapping_paths, False, None, 0)
+
+
+def _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
+                            threads, max_mapping_paths, whole_database: bool, target_db, search_batchsize):
+    """Both embedding-score modes.  whole_database (`database_cosine`): the candidates are every (query chain, target chain) pair
+    of the database that passes the two early exits (database_candidates: EVERY rank of a process group scans its rows and
+    takes part in the gather; rank 0 alone goes on to the scoring half and returns results, the others return None); else
+    (`exhaustive_cosine`) the chains the hits of search_results name."""
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
         return None
@@ -475,7 +642,7 @@ def _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_e
     names, query_chains, structures = _query_structures(queries, inputs_from_easy_search, pdb_chain)
     if len(set(names)) != len(names):
         raise ValueError("multi-domain search: query domain names must be unique")
-    hits = group_hits(names, query_chains, search_results)
+    hits = group_hits(names, query_chains, [] if whole_database else search_results)
     if network is None:
         from . import dbsearch
         network, _device = dbsearch.network_setup(threads=threads, device=device)
@@ -489,8 +656,30 @@ def _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_e
     reader = QueryDB(db_name)
     try:
         qlen = None if reader.faiss else engine.to_device(np.asarray([len(structures[i]["seq"]) for i in order], dtype=np.float32))
-        return cosine_step(hits, q_first, q_emb, "ip" if reader.faiss else "cosine", engine, reader.store,
-                           lambda rows: compact_target_rows(engine, reader, rows), mincos, qlen=qlen,
-                           mincov=mincov if not reader.faiss else 0.0, max_mapping_paths=max_mapping_paths)
+        score_mode, cov = ("ip", 0.0) if reader.faiss else ("cosine", mincov)
+        target_rows = lambda rows: compact_target_rows(engine, reader, rows)
+        if not whole_database:
+            return cosine_step(hits, q_first, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+                               max_mapping_paths=max_mapping_paths)
+        served = []
+        for qc, domains in hits.items():
+            if len(domains) < 2:
+                logger.info("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+            elif len(domains) > SCAN_MAX_DOMAINS:
+                logger.warning("Query chain %s has %d domains, more than the %d the database scan serves per query chain: skipped"
+                               % (qc, len(domains), SCAN_MAX_DOMAINS))
+            else:
+                served.append(qc)
+        if not served:
+            return []
+        starts = reader.store.chain_starts()
+        qchain = np.asarray([(q_first[qc], len(hits[qc])) for qc in served], dtype=np.int32)
+        pairs = database_candidates(engine, reader, target_db, starts, q_emb, score_mode, qchain, mincos, qlen, cov, search_batchsize)
+        from . import sharded
+        if sharded.rank_world()[0] != 0:
+            return None
+        plans = candidate_plans(pairs, served, hits, q_first, starts, reader.store)
+        return score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+                           max_mapping_paths=max_mapping_paths)
     finally:
         reader.close()

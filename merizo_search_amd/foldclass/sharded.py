@@ -186,6 +186,34 @@ def exchange_and_merge(scores, idx, engine, group=None):
     return engine.merge_gathered(ex)
 
 
+def gather_pairs(pairs, device, group=None) -> np.ndarray:
+    """Every rank's int64 [m_r,2] list (a numpy array; m_r differs by rank) -> all of them concatenated in rank order, on every
+    rank: an all-gather of the counts, then ONE all-gather of the lists padded to the longest.  `device`: where the
+    collective's buffers live (the rank's GPU under nccl = RCCL; gloo takes them there too).  Identity at world size 1."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
+    _rank, world = rank_world(group)
+    if world == 1:
+        return pairs
+    import torch
+    import torch.distributed as dist
+
+    def all_gather(mine):
+        out = torch.empty((world,) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(out, mine, group=group)
+        else:
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine, group=group)
+            out.copy_(torch.stack(parts))
+        return out
+
+    counts = all_gather(torch.tensor([pairs.shape[0]], dtype=torch.int64, device=device)).reshape(-1).cpu().numpy()
+    block = torch.zeros((max(int(counts.max()), 1), 2), dtype=torch.int64, device=device)
+    block[: pairs.shape[0]] = torch.from_numpy(pairs).to(device)
+    gathered = all_gather(block).cpu().numpy()
+    return np.concatenate([gathered[r, : int(counts[r])] for r in range(world)], axis=0)
+
+
 def balance_by_cost(costs: Sequence[float], world: int) -> List[List[int]]:
     """Deterministic longest-processing-time split of item numbers over `world` ranks (every rank
     computes the same answer).  Items of a rank are in ascending order."""

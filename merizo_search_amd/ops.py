@@ -558,6 +558,80 @@ def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, le
     return scores, match
 
 
+def md_chain_scan_launch(db, chain_start, q, mode: int, qchain, min_score: float, out_pairs, out_count, out_qstatus, cap: Optional[int] = None,
+                         lengths=None, qlen=None, mincov: float = 0.0, workspace=None):
+    """ONE ms_md_chain_scan call into preallocated outputs (the definition is the header's): db float32 [n,128], chain_start int64
+    [nchains + 1], q float32 [nq,128] (raw, as the search of `mode` takes them), qchain int32 [nqc,2] = (q0, nqd), out_pairs int64
+    [>= cap,2], out_count int64 [1], out_qstatus int32 [nqc] -- all device tensors.  cap: slots the call may write (default:
+    all of out_pairs).  Asynchronous; -> the workspace used (reusable by the next call as it is)."""
+    torch = _lib.require_gpu()
+    _f32_cuda(db, "db", DIM)
+    _f32_cuda(q, "q", DIM)
+    n, nq = db.shape[0], q.shape[0]
+    for name, t, size in (("lengths", lengths, n), ("qlen", qlen, nq)):
+        if t is not None:
+            _f32_cuda(t, name)
+            if t.numel() != size:
+                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+    for name, t, dtype in (("chain_start", chain_start, torch.int64), ("qchain", qchain, torch.int32), ("out_pairs", out_pairs, torch.int64),
+                           ("out_count", out_count, torch.int64), ("out_qstatus", out_qstatus, torch.int32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+            raise MerizoHipError(f"md_chain_scan: {name}: expected a contiguous {dtype} CUDA/HIP tensor")
+    nchains = max(int(chain_start.numel()) - 1, 0)
+    nqc = int(qchain.numel()) // 2
+    cap = int(out_pairs.numel()) // 2 if cap is None else int(cap)
+    if qchain.numel() != 2 * nqc or out_qstatus.numel() < nqc or out_count.numel() < 1 or cap < 0 or 2 * cap > out_pairs.numel():
+        raise MerizoHipError("md_chain_scan: qchain [nqc,2], out_qstatus [nqc], out_count [1] and out_pairs [>= cap,2] do not fit together")
+    lib = _lib.load()
+    need = int(lib.ms_md_chain_scan_workspace_bytes(n, nq))
+    if need == 0:
+        raise MerizoHipError(f"ms_md_chain_scan_workspace_bytes rejected n={n} nq={nq}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise MerizoHipError("md_chain_scan: workspace must be a contiguous uint8 tensor")
+    with _on(db, q, lengths, qlen, chain_start, qchain, out_pairs, out_count, out_qstatus, workspace) as d:
+        check(lib.ms_md_chain_scan(ptr(db), n, ptr(chain_start), nchains, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov),
+                                   ptr(qchain), nqc, float(min_score), ptr(out_pairs), cap, ptr(out_count), ptr(out_qstatus),
+                                   ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scan")
+    return workspace
+
+
+def md_chain_scan(db, chain_start, q, mode: int, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0, cap: int = 4096):
+    """Every (query chain, target chain) pair of a whole matrix that passes the mapping step's two early exits (ms_md_chain_scan).
+    chain_start int64 [nchains + 1] and qchain int32 [nqc,2]: tensors, or host arrays that are uploaded.
+    -> (pairs int64 [count,2] SORTED by (query chain, target chain), qstatus int32 [nqc]), numpy arrays: a function of the inputs
+    alone.  Synchronises (it reads the count back); runs a second time with the exact count when more than `cap` pairs qualify.
+    A chain table that breaks the header's rules raises."""
+    torch = _lib.require_gpu()
+
+    def dev(x, dtype, cols=None):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
+        if t.is_floating_point():
+            raise MerizoHipError(f"md_chain_scan: expected integers, got {t.dtype}")
+        t = t.to(device=db.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+        return t.reshape(-1, cols) if cols else t.reshape(-1)
+
+    cs, qc = dev(chain_start, np.int64), dev(qchain, np.int32, 2)
+    nqc = qc.shape[0]
+    count = torch.zeros(1, dtype=torch.int64, device=db.device)
+    status = torch.zeros(max(nqc, 1), dtype=torch.int32, device=db.device)[:nqc]
+    cap = max(int(cap), 0)
+    pairs = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=db.device)
+    ws = md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, lengths=lengths, qlen=qlen, mincov=mincov)
+    found = int(count.item())
+    if found > cap:
+        cap = found
+        pairs = torch.empty((cap, 2), dtype=torch.int64, device=db.device)
+        md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, lengths=lengths, qlen=qlen, mincov=mincov,
+                             workspace=ws)
+        found = int(count.item())
+    if found < 0:
+        raise MerizoHipError("md_chain_scan: chain_start must rise strictly from 0 to the number of rows")
+    out = pairs[:found].cpu().numpy()
+    return out[np.lexsort((out[:, 1], out[:, 0]))], status.cpu().numpy()
+
+
 class EgnnEncoder:
     """The Foldclass structure encoder on one GPU: prepared weights + positional table.
 

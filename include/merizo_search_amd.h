@@ -319,6 +319,34 @@ int ms_md_chain_scan(const float *db, int64_t n, const int64_t *chain_start, int
                      int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, void *workspace,
                      size_t workspace_bytes, ms_stream_t stream);
 
+/* ms_md_chain_scan for MANY queries: the same definition, served by the 16-bit matrix pipe in front of the exact cell.
+ * For every input ms_md_chain_scan accepts, the qualifying pairs are the same SET (their order in out_pairs is unspecified in
+ * both), *out_count is the same and out_qstatus is the same; the table is validated the same way (*out_count = -1, no row
+ * read); the cap rule is the same (counted, never written at or behind cap; cap == 0 only counts); the return codes are the
+ * same; nqd > 64 is still status -1; a target chain may have any number of rows; nq and nqc are not limited.
+ * How: an approximate score a from fp16 operands (the operands and scalings of MS_PF_F16X1: row * 2^sr and query * 2^sq
+ * rounded to nearest even, fp32 accumulation) obeys |a - s| <= E |row| |q| with E = ms_pf_err_coef(MS_PF_F16X1), s the exact
+ * cell's chain of 128 fmaf.  The scan's threshold is FIXED, so a cell with a < min_score - E * row_norm_bound * |q| is proved
+ * zero; every other cell is re-scored with the exact chain, mask and cut.  Nothing can fail to be proved: the verdicts are
+ * those of ms_md_chain_scan bit for bit.  In MS_MODE_COSINE_UNIT the filter works on the unmasked score (the mask multiplies
+ * by 0 or 1) and the mask is applied in the exact cell.
+ *   row_norm_bound   as in ms_pf_build_image: an upper bound on the L2 norm of the rows (1.0 + 1e-6 for unit rows).  NaN, <= 0
+ *                    or outside [2^-40, 2^40]: MS_ERR_RANGE.  It need not hold: a row whose fp32 sum of squares exceeds
+ *                    row_norm_bound^2 (1 + 1e-5) or is not finite has ALL its cells re-scored exactly, as has a query with a
+ *                    non-finite element, a zero norm or a norm outside [2^-40, 2^40].  min_score = -inf proves nothing and is
+ *                    served correctly at the speed of one lane per cell.
+ *   out_stats        int64 [1], device, may be NULL: out_stats[0] = the number of (query, row) cells this call sent to the exact
+ *                    re-score; written by the call's last launch, its counter reset by the call itself.
+ * Asynchronous on `stream`, never allocates; the workspace (ms_md_chain_scan_mq_workspace_bytes(n, nq) bytes; 0 for nq < 1 or
+ * n < 0; MS_ERR_WORKSPACE below that) serves the next call without clean-up.  Vector stores only (LDS atomics; at most one
+ * global atomic per wave and emission, one per wave for out_stats); no scratch memory.
+ * Backward compatible additions: ms_version() stays 210. */
+size_t ms_md_chain_scan_mq_workspace_bytes(int64_t n, int nq);
+int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *chain_start, int64_t nchains, const float *q, int nq, int mode,
+                        const float *lengths, const float *qlen, float mincov, const int32_t *qchain, int nqc, float min_score,
+                        int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, float row_norm_bound,
+                        int64_t *out_stats, void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

@@ -1,4 +1,4 @@
-"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments, `db-search` and `cluster`.
+"""Command line: `search`, `easy-search`, `createdb` with the reference's arguments, `db-search`, `chain-search` and `cluster`.
 
 Mirror of merizo_search/merizo.py for the Foldclass path (search :126-226, easy_search :229-407,
 createdb :102-123).  `segment` (the Merizo IPA network) is out of scope: easy-search takes the
@@ -8,6 +8,7 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli createdb <input_dir> <out_db> [-d cuda] [--layout pt|faiss|both]
     python -m merizo_search_amd.cli easy-search <pdb...> <db_name> <output> <tmp> --chopping "71-189,190-290"
     python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
+    python -m merizo_search_amd.cli chain-search <query_db> <target_db> <output> <tmp> [-s 0.5] [--exclude_same_chain] ...
     python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] ...
 
 `--multi_domain_search` (search, easy-search, db-search) also writes `<output>_search_multi_dom.tsv`: the target chains that match
@@ -20,6 +21,10 @@ the chains the top-k lists name -- from one more pass over the rows on the GPU: 
 
 `db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
 against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
+`chain-search` is `database_cosine` with a whole database as the query side: for every multi-domain chain of query_db (the runs of
+adjacent rows with one chain id) every chain of target_db that matches all its domains, whatever -k would have been -- the file
+`db-search --multi_domain_search` writes when -k covers the whole target -- with thousands of query domains per pass over the
+target's rows on the 16-bit matrix pipe (foldclass/chainsearch.py).
 `cluster` has none either: it makes a database non-redundant from the neighbour lists of that self-search (foldclass/cluster.py).
 
 Several GPUs of one node: start one process per GPU with torchrun,
@@ -334,6 +339,42 @@ def db_search(argv) -> None:
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def chain_search_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="chain-search", description="Every multi-domain match between two Foldclass databases: for each "
+                                "chain of query_db with 2-64 domains (adjacent rows with one chain id), every chain of target_db that "
+                                "matches ALL its domains at or above --mincos, from passes over all target rows on the GPU.",
+                                formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument("query_db", type=str, help="Database prefix whose chains are the queries (either layout).")
+    p.add_argument("target_db", type=str, help="Database prefix to search (either layout; may be query_db itself).")
+    p.add_argument("output", type=str, help="Writes <output>_search_multi_dom.tsv.")
+    p.add_argument("tmp", type=str)
+    p.add_argument("-d", "--device", type=str, default="cuda", help="'cuda' / 'cuda:N' = the MI355X. 'cpu' is refused by this build.")
+    p.add_argument("-s", "--mincos", type=float, default=0.5, help="Minimum cosine similarity of a matching domain pair.")
+    p.add_argument("-c", "--mincov", type=float, default=0.7, help="Minimum coverage of database matches (the `.pt` layout's mask).")
+    p.add_argument("--query_batchsize", type=int, default=4096, help="Query rows (whole query chains) per pass over the target.")
+    p.add_argument("--search_batchsize", type=int, default=262144, help="Target rows per block when the target is streamed.")
+    p.add_argument("--query_rows", type=str, default=None, metavar="LO:HI", help="Rows of query_db to take the query chains from.")
+    p.add_argument("--exclude_same_chain", action="store_true", default=False,
+                   help="query_db and target_db are the same database: a query chain is never its own match.")
+    p.add_argument("--output_headers", action="store_true", default=False)
+    return p
+
+
+def chain_search(argv) -> None:
+    args = chain_search_parser().parse_args(argv)
+    _join_process_group(args)
+    tmp = munge_tmp_with_uuid(args.tmp)
+    _log_command("chain-search")
+    from .foldclass.chainsearch import run_chain_search
+    t0 = time.time()
+    n = run_chain_search(query_db=args.query_db, db_name=args.target_db, output=args.output, tmp=tmp, device=args.device,
+                         mincos=args.mincos, mincov=args.mincov, query_batchsize=args.query_batchsize,
+                         search_batchsize=args.search_batchsize, query_rows=args.query_rows,
+                         exclude_same_chain=args.exclude_same_chain, output_headers=args.output_headers)
+    logging.info(f"Finished chain-search of {n} query chains in {time.time() - t0:.3f} seconds.")
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def cluster(argv) -> None:
     p = argparse.ArgumentParser(prog="cluster", description="Make a Foldclass database non-redundant on the GPU: search it against "
                                 "itself, pick representatives greedily (the longer domain first) and assign every other domain "
@@ -380,9 +421,10 @@ def createdb(argv) -> None:
 
 def main(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
-    modes = {"search": search, "easy-search": easy_search, "createdb": createdb, "db-search": db_search, "cluster": cluster}
+    modes = {"search": search, "easy-search": easy_search, "createdb": createdb, "db-search": db_search, "chain-search": chain_search,
+             "cluster": cluster}
     if not argv or argv[0] not in modes:
-        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb,db-search,cluster} ...  "
+        print("usage: python -m merizo_search_amd.cli {search,easy-search,createdb,db-search,chain-search,cluster} ...  "
               "(segment: out of scope, use the reference)", file=sys.stderr)
         sys.exit(2)
     modes[argv[0]](argv[1:])

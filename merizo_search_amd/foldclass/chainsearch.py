@@ -1,0 +1,176 @@
+"""`chain-search`: every multi-domain match between two databases.
+
+The query side is a whole database: its query chains are the runs of adjacent query rows with one chain id (multidomain.chain_runs,
+as `db-search --multi_domain_search` forms them), and for each of them EVERY chain of the target database is decided -- not only the
+chains a top-k list names.  Per batch of whole query chains: multidomain.database_candidates (ms_md_chain_scan / ms_md_chain_scan_mq
+over the resident target, this rank's shard under torchrun, or streamed blocks), then on rank 0 candidate_plans and score_plans,
+unchanged, and the lines appended to `<output>_search_multi_dom.tsv`.
+
+The file is the one `db-search query_db target_db --multi_domain_search --multi_domain_mode exhaustive_cosine --skip_tmalign -s S -c C
+-k K` writes when K is at least the target's row count (every row at or above S is then a hit), on databases whose chains are
+adjacent runs, with the same --query_rows and --exclude_same_chain."""
+from __future__ import annotations
+
+import logging
+import os
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import sharded
+from .multidomain import MAX_MAPPING_PATHS, SCAN_MAX_DOMAINS
+
+logger = logging.getLogger(__name__)
+
+
+def served_runs(starts: np.ndarray, ids: Sequence[str], offset: int = 0, log=logger) -> List[Tuple[int, int, str]]:
+    """The query chains a chain-search serves: (first row, one past the last row, chain id) of every run of chain_runs' table
+    `starts` (local rows; `offset` makes them global) with 2..SCAN_MAX_DOMAINS domains.  ids: the chain id of every local row.
+    Runs of one domain and runs of more than SCAN_MAX_DOMAINS are logged and skipped."""
+    out = []
+    for a, b in zip(starts[:-1].tolist(), starts[1:].tolist()):
+        qc = ids[a]
+        if b - a < 2:
+            log.debug("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+        elif b - a > SCAN_MAX_DOMAINS:
+            log.warning("Query chain %s has %d domains, more than the %d the database scan serves per query chain: skipped"
+                        % (qc, b - a, SCAN_MAX_DOMAINS))
+        else:
+            out.append((offset + a, offset + b, qc))
+    return out
+
+
+def chain_batches(runs: Sequence[Tuple[int, int, str]], batch_rows: int) -> List[List[Tuple[int, int, str]]]:
+    """Whole query chains, in order, up to batch_rows query rows per batch (a batch always takes at least one chain); a chain id
+    that comes back starts a new batch, as a batch's chains are keyed by their id."""
+    batches, cur, rows, seen = [], [], 0, set()
+    for run in runs:
+        n = run[1] - run[0]
+        if cur and (rows + n > batch_rows or run[2] in seen):
+            batches.append(cur)
+            cur, rows, seen = [], 0, set()
+        cur.append(run)
+        rows += n
+        seen.add(run[2])
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def drop_own_chain(pairs: np.ndarray, first_rows: Sequence[int], target_starts: np.ndarray) -> np.ndarray:
+    """The candidates (query chain of the batch, target chain) without the pairs whose target run holds the query chain's own first
+    row: in a search of a database against itself a query chain is never its own candidate."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if not len(pairs):
+        return pairs
+    own = np.searchsorted(np.asarray(target_starts, np.int64), np.asarray(first_rows, np.int64), side="right") - 1
+    return pairs[own[pairs[:, 0]] != pairs[:, 1]]
+
+
+def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device="cuda", mincos: float = 0.5, mincov: float = 0.7,
+                     query_batchsize: int = 4096, search_batchsize: int = 262144, query_rows: Optional[str] = None,
+                     exclude_same_chain: bool = False, output_headers: bool = False, max_mapping_paths: Optional[int] = None,
+                     route: str = "auto", engine=None) -> int:
+    """-> the number of query chains served.  route: multidomain.database_candidates' ("auto": the matrix route from
+    ops.MD_SCAN_MATRIX_MIN_NQ query rows per batch on; the file does not depend on it).  Under a process group every rank calls it;
+    rank 0 writes."""
+    from . import dbsearch
+    from . import multidomain as md
+    from .dbquery import QueryDB, parse_row_slice, same_database
+    from .results import write_all_dom_search_results
+
+    if engine is None:
+        from .engine import resolve_device
+        device = resolve_device(device)                                   # ('cpu' is refused here, before anything else)
+    if not 0.0 <= float(mincov) <= 1.0:
+        dbsearch._refuse("--mincov must lie in [0, 1], got %r." % (mincov,))
+    if query_batchsize < 1 or search_batchsize < 1:
+        dbsearch._refuse("--query_batchsize and --search_batchsize must be >= 1.")
+    same = same_database(query_db, db_name)
+    if exclude_same_chain and not same:
+        dbsearch._refuse("--exclude_same_chain removes the query chain itself from its candidates: it needs the query database and "
+                         "the target database to be the same, got %s and %s." % (query_db, db_name))
+    for prefix in (query_db, db_name):
+        if not (os.path.exists(prefix + ".json") or (os.path.exists(prefix + ".pt") and os.path.exists(prefix + ".index"))):
+            dbsearch._refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
+                             % (prefix, prefix, prefix))
+    target_db = dbsearch.read_database(db_name=db_name)                   # (host side only: nothing is uploaded yet)
+    qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
+    try:
+        q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
+    except ValueError as exc:
+        dbsearch._refuse("--query_rows: %s" % exc)
+    rank, world = sharded.rank_world()
+    os.makedirs(tmp, exist_ok=True)
+    multi_output = output + "_search_multi_dom.tsv"
+    if rank == 0:
+        if os.path.exists(multi_output):
+            logger.warning(f"Search output file '{multi_output}' already exists. Results will be overwritten!")
+        open(multi_output, "w").close()
+
+    engine = engine or dbsearch.engine_setup(device)
+    ids = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
+    runs = served_runs(md.chain_runs(qdb.store_names(q_lo, q_hi)), ids, q_lo)
+    batches = chain_batches(runs, int(query_batchsize))
+    # the target: made resident once by db-search's loader (streamed per batch beyond the HBM budget)
+    nq_batch = max([sum(b - a for a, b, _qc in batch) for batch in batches] or [1])
+    scan = dbsearch._BatchScan(target_db, qdb, engine, same, nq_batch, 1, search_batchsize, dbsearch._DeviceTimes(engine, None))
+    reader = qdb if same else QueryDB(db_name)
+    starts = reader.store.chain_starts()
+    if target_db["faiss"]:
+        score_mode, cov = ("ip_prenorm" if qdb.normalized else "ip"), 0.0
+    else:
+        score_mode, cov = "cosine", float(mincov)
+    resident = bool(world == 1 and not scan.streamed)
+    logger.info("chain-search: %d query chains of %s (rows %d..%d) against the %d chains of %s in %d batches%s"
+                % (len(runs), query_db, q_lo, q_hi - 1, len(starts) - 1, db_name, len(batches),
+                   "; the target is streamed in blocks of %d rows" % int(search_batchsize) if scan.streamed else ""))
+
+    def target_rows(rows):
+        if not resident:
+            return md.compact_target_rows(engine, reader, rows)
+        if target_db["faiss"]:
+            return scan.shard, None, rows - scan.lo
+        return target_db["database"], target_db["lengths"], rows - target_db["row_lo"]
+
+    max_paths = MAX_MAPPING_PATHS if max_mapping_paths is None else int(max_mapping_paths)
+    part = os.path.join(tmp, "chain_search_batch.tsv")
+    try:
+        for number, batch in enumerate(batches):
+            # the batch's query rows, chain after chain (the served chains need not be adjacent)
+            emb, names, seqlen, q_first, qchain, at = [], [], [], {}, [], 0
+            for a, b, qc in batch:
+                emb.append(qdb.embeddings(a, b))
+                names.extend(dbsearch._query_name(qd) for qd in qdb.records(a, b, with_coords=False))
+                if score_mode == "cosine":
+                    seqlen.extend(len(s) for s in qdb.seqs(a, b))
+                q_first[qc] = at
+                qchain.append((at, b - a))
+                at += b - a
+            chain_of = [qc for a, b, qc in batch for _ in range(b - a)]
+            hits = md.group_hits(names, chain_of, [])
+            q_emb = engine.to_device(np.concatenate(emb, axis=0))
+            qlen = engine.to_device(np.asarray(seqlen, dtype=np.float32)) if score_mode == "cosine" else None
+            pairs = md.database_candidates(engine, reader, target_db, starts, q_emb, score_mode, np.asarray(qchain, dtype=np.int32),
+                                           mincos, qlen, cov, search_batchsize, route=route)
+            if rank != 0:
+                continue
+            if exclude_same_chain:
+                pairs = drop_own_chain(pairs, [a for a, _b, _qc in batch], starts)
+            served = [qc for _a, _b, qc in batch]
+            plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader.store)
+            results = md.score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+                                     max_mapping_paths=max_paths)
+            write_all_dom_search_results(results, part, output_headers and number == 0)
+            with open(part, "rb") as src, open(multi_output, "ab") as dst:
+                dst.write(src.read())
+            os.remove(part)
+            logger.info("chain-search: batch %d of %d done (%d query chains, %d candidate pairs)"
+                        % (number + 1, len(batches), len(batch), len(pairs)))
+        if rank == 0 and output_headers and not batches:
+            write_all_dom_search_results([], multi_output, True)
+    finally:
+        if reader is not qdb:
+            reader.close()
+        qdb.close()
+    return len(runs)

@@ -260,14 +260,20 @@ class HipEngine:
                    self.torch.empty((int(cand.shape[0]), 2), dtype=self.torch.int32, device=self.device))
         return ops.md_chain_scores(db, q, code, cand, trows, mat_off, min_score, lengths=lengths, qlen=qlen, mincov=mincov, out=out)
 
-    def md_chain_scan(self, db, chain_start, q, mode: str, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0):
+    def md_chain_scan(self, db, chain_start, q, mode: str, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
+                      route: str = "lane", row_norm_bound=None, stats=None):
         """The pairs (query chain, target chain) of a whole matrix whose score matrix passes chain_mappings' two early exits
         (ms_md_chain_scan; the cells are md_chain_scores' cells).  chain_start int64 [nchains + 1]: the runs of rows that are
         the target chains; qchain int32 [nqc,2] = (first query row, query domains); mode as md_chain_scores takes it.
+        route: ops.md_chain_scan's ("lane", "matrix", "auto": the same pairs either way); the matrix route takes the unit rows the
+        drivers hold at their bound of 1 + 1e-6 unless row_norm_bound says otherwise (a longer row is re-scored exactly, never wrong).
         -> (pairs [m,2] sorted, qstatus [nqc]; -1 = a query chain this call does not serve, e.g. more than 64 domains)."""
         ops = self._ops
         code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
-        return ops.md_chain_scan(db, chain_start, q, code, qchain, min_score, lengths=lengths, qlen=qlen, mincov=mincov)
+        if route != "lane" and row_norm_bound is None:
+            row_norm_bound = 1.0 + 1e-6
+        return ops.md_chain_scan(db, chain_start, q, code, qchain, min_score, lengths=lengths, qlen=qlen, mincov=mincov, route=route,
+                                 row_norm_bound=row_norm_bound, stats=stats)
 
     # -- database residency ----------------------------------------------------------
     STAGE_ROWS = 1 << 19          # 256 MiB pinned staging buffers

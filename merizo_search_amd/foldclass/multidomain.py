@@ -559,11 +559,12 @@ def merge_candidates(parts: Sequence[np.ndarray]) -> np.ndarray:
 
 
 def database_candidates(engine, reader, target_db: Optional[dict], starts: np.ndarray, q_emb, score_mode: str, qchain: np.ndarray,
-                        mincos: float, qlen, mincov: float, search_batchsize: int = 262144) -> np.ndarray:
+                        mincos: float, qlen, mincov: float, search_batchsize: int = 262144, route: str = "lane") -> np.ndarray:
     """ms_md_chain_scan over this process's rows of the database -> the candidates of ALL rows, identical on every rank (a
     collective under a process group: sharded.gather_pairs).  The rows: the resident copy the search left in target_db (the
     `.pt` rows as dbsearch._to_engine normalised them, the faiss shard of target_db['_resident']) read in place; else streamed
-    from the files once more, block by block (engine.device_blocks), each block a range of its own (range_candidates)."""
+    from the files once more, block by block (engine.device_blocks), each block a range of its own (range_candidates).
+    route: engine.md_chain_scan's (the pairs do not depend on it)."""
     from . import sharded
     rank, world = sharded.rank_world()
     lo, hi = sharded.shard_bounds(reader.n, world, rank)
@@ -572,8 +573,9 @@ def database_candidates(engine, reader, target_db: Optional[dict], starts: np.nd
     parts = []
 
     def scan_block(block, a, lengths=None):
+        kw = {} if route == "lane" else {"route": route}          # (engines without a matrix route keep their signature)
         scan = lambda table: engine.md_chain_scan(block, engine.to_device(table), q_emb, score_mode, qchain_d, float(mincos),
-                                                  lengths=lengths, qlen=qlen, mincov=float(mincov))[0]
+                                                  lengths=lengths, qlen=qlen, mincov=float(mincov), **kw)[0]
         parts.append(range_candidates(starts, a, a + int(block.shape[0]), nqc, scan))
 
     resident = None

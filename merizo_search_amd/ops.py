@@ -558,16 +558,41 @@ def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, le
     return scores, match
 
 
+# Query rows from which md_chain_scan's route "auto" takes the matrix route: the smallest nq of tools/chain_search_bench.py's sweep from
+# which ms_md_chain_scan_mq is faster than ms_md_chain_scan on both of its shapes (profiles/chain_search_bench.log).
+MD_SCAN_MATRIX_MIN_NQ = 64
+MD_SCAN_ROUTES = ("lane", "matrix", "auto")
+
+
+def md_scan_route(route: str, nq: int, row_norm_bound) -> str:
+    """The route one md_chain_scan call takes: "lane" (ms_md_chain_scan) or "matrix" (ms_md_chain_scan_mq; needs a row-norm bound).
+    "auto": the matrix route from MD_SCAN_MATRIX_MIN_NQ query rows on when a bound is given."""
+    if route not in MD_SCAN_ROUTES:
+        raise MerizoHipError(f"md_chain_scan: route must be one of {MD_SCAN_ROUTES}, got {route!r}")
+    if route == "matrix" and row_norm_bound is None:
+        raise MerizoHipError("md_chain_scan: route 'matrix' needs row_norm_bound (1 + 1e-6 for unit rows)")
+    if route == "auto":
+        return "matrix" if row_norm_bound is not None and int(nq) >= MD_SCAN_MATRIX_MIN_NQ else "lane"
+    return route
+
+
 def md_chain_scan_launch(db, chain_start, q, mode: int, qchain, min_score: float, out_pairs, out_count, out_qstatus, cap: Optional[int] = None,
-                         lengths=None, qlen=None, mincov: float = 0.0, workspace=None):
+                         lengths=None, qlen=None, mincov: float = 0.0, workspace=None, route: str = "lane", row_norm_bound=None,
+                         out_stats=None):
     """ONE ms_md_chain_scan call into preallocated outputs (the definition is the header's): db float32 [n,128], chain_start int64
     [nchains + 1], q float32 [nq,128] (raw, as the search of `mode` takes them), qchain int32 [nqc,2] = (q0, nqd), out_pairs int64
     [>= cap,2], out_count int64 [1], out_qstatus int32 [nqc] -- all device tensors.  cap: slots the call may write (default:
-    all of out_pairs).  Asynchronous; -> the workspace used (reusable by the next call as it is)."""
+    all of out_pairs).  route: md_scan_route's; the matrix route is ms_md_chain_scan_mq with row_norm_bound and out_stats (int64 [1]
+    device tensor or None: the cells it re-scored exactly).  A workspace serves one route.
+    Asynchronous; -> the workspace used (reusable by the next call as it is)."""
     torch = _lib.require_gpu()
     _f32_cuda(db, "db", DIM)
     _f32_cuda(q, "q", DIM)
     n, nq = db.shape[0], q.shape[0]
+    matrix = md_scan_route(route, nq, row_norm_bound) == "matrix"
+    if out_stats is not None and (not isinstance(out_stats, torch.Tensor) or not out_stats.is_cuda or out_stats.dtype != torch.int64
+                                  or out_stats.numel() < 1):
+        raise MerizoHipError("md_chain_scan: out_stats: expected an int64 CUDA/HIP tensor of one element")
     for name, t, size in (("lengths", lengths, n), ("qlen", qlen, nq)):
         if t is not None:
             _f32_cuda(t, name)
@@ -583,25 +608,32 @@ def md_chain_scan_launch(db, chain_start, q, mode: int, qchain, min_score: float
     if qchain.numel() != 2 * nqc or out_qstatus.numel() < nqc or out_count.numel() < 1 or cap < 0 or 2 * cap > out_pairs.numel():
         raise MerizoHipError("md_chain_scan: qchain [nqc,2], out_qstatus [nqc], out_count [1] and out_pairs [>= cap,2] do not fit together")
     lib = _lib.load()
-    need = int(lib.ms_md_chain_scan_workspace_bytes(n, nq))
+    need = int((lib.ms_md_chain_scan_mq_workspace_bytes if matrix else lib.ms_md_chain_scan_workspace_bytes)(n, nq))
     if need == 0:
         raise MerizoHipError(f"ms_md_chain_scan_workspace_bytes rejected n={n} nq={nq}")
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
     elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
         raise MerizoHipError("md_chain_scan: workspace must be a contiguous uint8 tensor")
-    with _on(db, q, lengths, qlen, chain_start, qchain, out_pairs, out_count, out_qstatus, workspace) as d:
-        check(lib.ms_md_chain_scan(ptr(db), n, ptr(chain_start), nchains, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov),
-                                   ptr(qchain), nqc, float(min_score), ptr(out_pairs), cap, ptr(out_count), ptr(out_qstatus),
-                                   ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scan")
+    with _on(db, q, lengths, qlen, chain_start, qchain, out_pairs, out_count, out_qstatus, out_stats, workspace) as d:
+        args = (ptr(db), n, ptr(chain_start), nchains, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov), ptr(qchain), nqc,
+                float(min_score), ptr(out_pairs), cap, ptr(out_count), ptr(out_qstatus))
+        if matrix:
+            check(lib.ms_md_chain_scan_mq(*args, float(row_norm_bound), ptr(out_stats), ptr(workspace), workspace.numel(), d.stream),
+                  "ms_md_chain_scan_mq")
+        else:
+            check(lib.ms_md_chain_scan(*args, ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scan")
     return workspace
 
 
-def md_chain_scan(db, chain_start, q, mode: int, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0, cap: int = 4096):
+def md_chain_scan(db, chain_start, q, mode: int, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0, cap: int = 4096,
+                  route: str = "lane", row_norm_bound=None, stats=None):
     """Every (query chain, target chain) pair of a whole matrix that passes the mapping step's two early exits (ms_md_chain_scan).
     chain_start int64 [nchains + 1] and qchain int32 [nqc,2]: tensors, or host arrays that are uploaded.
     -> (pairs int64 [count,2] SORTED by (query chain, target chain), qstatus int32 [nqc]), numpy arrays: a function of the inputs
     alone.  Synchronises (it reads the count back); runs a second time with the exact count when more than `cap` pairs qualify.
+    route, row_norm_bound: md_scan_route's -- the answer does not depend on them.  stats: a dict that receives 'route' and, on the
+    matrix route, 'rescored' (cells of the last call that went to the exact chain).
     A chain table that breaks the header's rules raises."""
     torch = _lib.require_gpu()
 
@@ -618,14 +650,20 @@ def md_chain_scan(db, chain_start, q, mode: int, qchain, min_score: float, lengt
     status = torch.zeros(max(nqc, 1), dtype=torch.int32, device=db.device)[:nqc]
     cap = max(int(cap), 0)
     pairs = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=db.device)
-    ws = md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, lengths=lengths, qlen=qlen, mincov=mincov)
+    taken = md_scan_route(route, q.shape[0], row_norm_bound)
+    st = torch.zeros(1, dtype=torch.int64, device=db.device) if taken == "matrix" else None
+    kw = dict(lengths=lengths, qlen=qlen, mincov=mincov, route=taken, row_norm_bound=row_norm_bound, out_stats=st)
+    ws = md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, **kw)
     found = int(count.item())
     if found > cap:
         cap = found
         pairs = torch.empty((cap, 2), dtype=torch.int64, device=db.device)
-        md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, lengths=lengths, qlen=qlen, mincov=mincov,
-                             workspace=ws)
+        md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, workspace=ws, **kw)
         found = int(count.item())
+    if stats is not None:
+        stats["route"] = taken
+        if st is not None:
+            stats["rescored"] = int(st.item())
     if found < 0:
         raise MerizoHipError("md_chain_scan: chain_start must rise strictly from 0 to the number of rows")
     out = pairs[:found].cpu().numpy()

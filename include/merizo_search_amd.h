@@ -198,6 +198,31 @@ int ms_debug_prefilter_poison(void *workspace, unsigned int slot_counter, unsign
  * (approximate scores float32 [nq][kp], rows int64 [nq][kp]); image: 0 = no image, 1 = the split-bf16 image, 2 = the fp16 image; -1 when the shape is
  * not served by the prefilter. */
 int ms_debug_prefilter_lists(void *workspace, int64_t n, int nq, int k, int image, float *as_host, int64_t *ai_host, int *kp_out);
+/* Test hook (tests/merge_case.py): the final merge of a search on lists the CALLER wrote -- P lists of k slots for each of nq queries,
+ * every list sorted best first (score descending, row ascending), empty slots (-inf, 0xFFFFFFFF) last, rows distinct across the lists
+ * of a query.  The launch is the one a search makes for this (P, k): the workgroup merge for P <= 256, the head-advance merge or the
+ * pool merge beyond (MS_BLOCK_MERGE / MS_HEAD_MERGE as in a search).  All pointers are device memory, 16-byte aligned lists.
+ *   part_s / part_i  sm_nq_pad == 0: rank-major, entry (rank r, list l) of query q at (q * k + r) * P + l;
+ *                    sm_nq_pad >= nq: stream-major, at (l * sm_nq_pad + q) * k + r
+ *   sparse           != 0: the pool form the prefiltered search uses on its mostly empty lists (ignored when ub_s is given)
+ *   out_s / out_i    rank r of query q at q * out_stride + col0 + r: float32 score, int64 row + row_offset, (-inf, -1) padding
+ *   ub_s / ub_i      both NULL, or [nq]: the k-th entry (score, row without the offset; (-inf, 0xFFFFFFFF) when there are fewer)
+ *   dp_scratch       NULL, or 64 bytes the hook fills on `stream` with a device plan of dp_nq <= nq queries and dp_P <= P lists (the
+ *                    exact pass behind a prefiltered search): the lists are then laid out rank-major with dp_P, only the first dp_nq
+ *                    queries are merged and query q is written to output row qmap[q] (qmap: NULL or int32 [dp_nq]; only with a plan)
+ * MS_ERR_ARG: NULL or misaligned lists, k outside 1..64, nq < 1, P < 1, out_stride < col0 + k, a plan outside its launch;
+ * MS_ERR_RANGE: what the search's own merge launch declines (more than 1024 lists; a plan or stream-major lists that the workgroup
+ * merge does not take).  Nothing is launched on an error. */
+int ms_debug_merge_lists(const float *part_s, const unsigned int *part_i, int P, int nq, int k, int sm_nq_pad, int sparse, int64_t row_offset,
+                         float *out_s, int64_t *out_i, int out_stride, int col0, float *ub_s, unsigned int *ub_i, int dp_nq, int dp_P,
+                         const int *qmap, void *dp_scratch, ms_stream_t stream);
+/* Test hook: the lower bound a sampled search takes from its sample pass -- lb[q] = the k-th largest (with multiplicity) of the first
+ * `ranks` entries of the P lists of query q (part_s laid out as above; -inf = an empty slot), -inf when there are fewer than k.
+ * hist / hstep: both NULL, or uint32 [nq][16] counters (zeroed) and float [nq] bucket widths of the shared bound.
+ * MS_ERR_ARG: NULL pointers, k outside 1..64, nq < 1, P < 1, only one of hist / hstep; MS_ERR_RANGE: ranks < 1, ranks > k,
+ * ranks * P > 2048 (a search merges such lists instead). */
+int ms_debug_sample_bound(const float *part_s, int P, int nq, int k, int ranks, int sm_nq_pad, float *lb, unsigned int *hist, float *hstep,
+                          ms_stream_t stream);
 
 /* Merge S sorted result lists per query into the best k: faiss.ResultHeap(nq,k).add_result /
  * finalize (dbsearch.py:224,240,245) and the cross-shard merge after the RCCL all-gather.

@@ -72,6 +72,8 @@ SIGNATURES = {
     "ms_debug_prefilter_state": (_int, [_vp, _vp, _vp, _vp]),
     "ms_debug_prefilter_poison": (_int, [_vp, ctypes.c_uint, ctypes.c_uint]),
     "ms_debug_prefilter_lists": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    "ms_debug_merge_lists": (_int, [_vp, _vp, _int, _int, _int, _int, _int, _i64, _vp, _vp, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "ms_debug_sample_bound": (_int, [_vp, _int, _int, _int, _int, _int, _vp, _vp, _vp, _vp]),
     "ms_topk_merge": (_int, [_vp, _vp, _int, _int, _int, _vp, _vp, _vp]),
     "ms_topk_merge_strided": (_int, [_vp, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "ms_topk_drop_ranges": (_int, [_vp, _vp, _int, _int, _vp, _vp, _f, _int, _vp, _vp, _vp, _vp]),

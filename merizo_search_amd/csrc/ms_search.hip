@@ -978,6 +978,21 @@ int zero_hist_unless_clean(const ScanPlan &pl, const ScanParams &sp, const void 
     return MS_OK;
 }
 
+// The bound selection over ranks * P <= 2048 values per query: the kernel whose lanes hold them all (run_prepass, and the test
+// hook ms_debug_sample_bound)
+int launch_sample_bound(const float *part_s, int P, int nq, int k, int ranks, float *lb, uint32_t *hist, float *hstep, const uint32_t *gate,
+                        uint32_t gate_epoch, size_t sm_stride, hipStream_t st) {
+    const int vpl = (ranks * P + 63) / 64;
+#define MS_BOUND(V) hipLaunchKernelGGL(ms_sample_bound_kernel<V>, dim3(nq), dim3(64), 0, st, part_s, P, k, ranks, lb, hist, hstep, gate, gate_epoch, sm_stride)
+    if (vpl <= 4) { MS_BOUND(4); }
+    else if (vpl <= 8) { MS_BOUND(8); }
+    else if (vpl <= 16) { MS_BOUND(16); }
+    else { MS_BOUND(32); }
+#undef MS_BOUND
+    MS_LAUNCH_CHECK("ms_sample_bound_kernel");
+    return MS_OK;
+}
+
 // Sample pass: scan the first prepass_tiles tiles of every stream, merge, and leave the k-th
 // best score per query in the workspace as the lower bound of the full pass (attach_prepass_results).
 int run_prepass(const ScanPlan &pl, ScanParams *sp, int nq, char *ws, hipStream_t st) {
@@ -1012,13 +1027,8 @@ int run_prepass(const ScanPlan &pl, ScanParams *sp, int nq, char *ws, hipStream_
         return MS_OK;
     }
     uint32_t *hist = pl.hist_on ? pl.hist(ws) : nullptr;
-#define MS_BOUND(V) hipLaunchKernelGGL(ms_sample_bound_kernel<V>, dim3(nq), dim3(64), 0, st, s0.part_s, P, s0.k, ranks, pl.lb_s(ws), hist, pl.hstep(ws), s0.gate, s0.gate_epoch, sm_stride)
-    if (vpl <= 4) { MS_BOUND(4); }
-    else if (vpl <= 8) { MS_BOUND(8); }
-    else if (vpl <= 16) { MS_BOUND(16); }
-    else { MS_BOUND(32); }
-#undef MS_BOUND
-    MS_LAUNCH_CHECK("ms_sample_bound_kernel");
+    rc = launch_sample_bound(s0.part_s, P, nq, s0.k, ranks, pl.lb_s(ws), hist, pl.hstep(ws), s0.gate, s0.gate_epoch, sm_stride, st);
+    if (rc) return rc;
     attach_prepass_results(pl, ws, sp, pl.hist_on);
     return MS_OK;
 }
@@ -1403,6 +1413,49 @@ int ms_debug_prefilter_lists(void *workspace, int64_t n, int nq, int k, int imag
     if (hipMemcpy(as_host, L.as(workspace), (size_t)nq * L.kp * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     if (hipMemcpy(ai_host, L.ai(workspace), (size_t)nq * L.kp * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
+}
+
+// Test hook: launch_merge on lists the caller wrote (include/merizo_search_amd.h; tests/merge_case.py).  The plan and the parameters
+// carry what launch_merge reads of them -- the list count, the lists, no gate -- so the form launched is the one a search of that
+// (P, k) gets.
+int ms_debug_merge_lists(const float *part_s, const unsigned int *part_i, int P, int nq, int k, int sm_nq_pad, int sparse, int64_t row_offset,
+                         float *out_s, int64_t *out_i, int out_stride, int col0, float *ub_s, unsigned int *ub_i, int dp_nq, int dp_P,
+                         const int *qmap, void *dp_scratch, ms_stream_t stream) {
+    if (part_s == nullptr || part_i == nullptr || out_s == nullptr || out_i == nullptr || (ub_s == nullptr) != (ub_i == nullptr))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_merge_lists: NULL lists or outputs, or only one of ub_s / ub_i");
+    if ((((uintptr_t)part_s | (uintptr_t)part_i) & 15) != 0) MS_FAIL(MS_ERR_ARG, "ms_debug_merge_lists: the lists must be 16-byte aligned");
+    if (k < 1 || k > 64 || nq < 1 || P < 1 || col0 < 0 || out_stride < col0 + k || sm_nq_pad < 0 || (sm_nq_pad > 0 && sm_nq_pad < nq))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_merge_lists: need 1 <= k <= 64, nq >= 1, P >= 1, out_stride >= col0 + k, sm_nq_pad 0 or >= nq (P=%d nq=%d k=%d)", P, nq, k);
+    if (dp_scratch == nullptr ? qmap != nullptr : (dp_nq < 1 || dp_nq > nq || dp_P < 1 || dp_P > P || sm_nq_pad != 0))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_merge_lists: qmap without a device plan, or a plan outside its launch (dp_nq=%d nq=%d dp_P=%d P=%d)", dp_nq, nq, dp_P, P);
+    const hipStream_t st = (hipStream_t)stream;
+    ScanPlan pl{};
+    ScanParams sp{};
+    pl.d.P = P;
+    sp.part_s = const_cast<float *>(part_s); sp.part_i = const_cast<uint32_t *>(part_i);      // (the merges only read them)
+    if (dp_scratch != nullptr) {
+        if (!block_merge_takes(k, P))       // (what launch_merge answers: nothing is written to the scratch for a launch that does not happen)
+            return launch_merge(pl, sp, nq, k, row_offset, out_s, out_i, out_stride, col0, ub_s, ub_i, st, static_cast<const ScanDevPlan *>(dp_scratch), qmap);
+        static_assert(sizeof(ScanDevPlan) == 64, "the hook's scratch is 64 bytes");
+        char *d = static_cast<char *>(dp_scratch);
+        MS_HIP_CHECK(hipMemsetAsync(d, 0, sizeof(ScanDevPlan), st));
+        MS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d + offsetof(ScanDevPlan, nq)), dp_nq, 1, st));
+        MS_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d + offsetof(ScanDevPlan, P)), dp_P, 1, st));
+    }
+    return launch_merge(pl, sp, nq, k, row_offset, out_s, out_i, out_stride, col0, ub_s, ub_i, st, static_cast<const ScanDevPlan *>(dp_scratch), qmap,
+                        sparse != 0 ? 1 : 0, sm_nq_pad > 0 ? (size_t)sm_nq_pad * k : 0);
+}
+
+// Test hook: the bound selection of a sample pass on lists the caller wrote (run_prepass launches the same function)
+int ms_debug_sample_bound(const float *part_s, int P, int nq, int k, int ranks, int sm_nq_pad, float *lb, unsigned int *hist, float *hstep,
+                          ms_stream_t stream) {
+    if (part_s == nullptr || lb == nullptr || (hist == nullptr) != (hstep == nullptr))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_sample_bound: NULL lists or bound, or only one of hist / hstep");
+    if (k < 1 || k > 64 || nq < 1 || P < 1 || sm_nq_pad < 0 || (sm_nq_pad > 0 && sm_nq_pad < nq))
+        MS_FAIL(MS_ERR_ARG, "ms_debug_sample_bound: need 1 <= k <= 64, nq >= 1, P >= 1, sm_nq_pad 0 or >= nq (P=%d nq=%d k=%d)", P, nq, k);
+    if (ranks < 1 || ranks > k || (int64_t)ranks * P > 2048)
+        MS_FAIL(MS_ERR_RANGE, "ms_debug_sample_bound: need 1 <= ranks <= k and ranks * P <= 2048 (ranks=%d P=%d k=%d)", ranks, P, k);
+    return launch_sample_bound(part_s, P, nq, k, ranks, lb, hist, hstep, nullptr, 0u, sm_nq_pad > 0 ? (size_t)sm_nq_pad * k : 0, (hipStream_t)stream);
 }
 
 // S sorted lists per query, list s of each array s * stride BYTES behind list 0 -> the best k (both merge entry points)

@@ -77,7 +77,8 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
     from . import dbsearch
     from . import multidomain as md
     from .dbquery import QueryDB, parse_row_slice, same_database
-    from .results import write_all_dom_search_results
+    from .results import append_written, write_all_dom_search_results
+    from .target import Target, score_mode as target_score_mode
 
     if engine is None:
         from .engine import resolve_device
@@ -91,16 +92,14 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
         dbsearch._refuse("--exclude_same_chain removes the query chain itself from its candidates: it needs the query database and "
                          "the target database to be the same, got %s and %s." % (query_db, db_name))
     for prefix in (query_db, db_name):
-        if not (os.path.exists(prefix + ".json") or (os.path.exists(prefix + ".pt") and os.path.exists(prefix + ".index"))):
-            dbsearch._refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
-                             % (prefix, prefix, prefix))
+        dbsearch._require_database(prefix)
     target_db = dbsearch.read_database(db_name=db_name)                   # (host side only: nothing is uploaded yet)
     qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
     try:
         q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
     except ValueError as exc:
         dbsearch._refuse("--query_rows: %s" % exc)
-    rank, world = sharded.rank_world()
+    rank = sharded.rank_world()[0]
     os.makedirs(tmp, exist_ok=True)
     multi_output = output + "_search_multi_dom.tsv"
     if rank == 0:
@@ -112,27 +111,17 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
     ids = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
     runs = served_runs(md.chain_runs(qdb.store_names(q_lo, q_hi)), ids, q_lo)
     batches = chain_batches(runs, int(query_batchsize))
-    # the target: made resident once by db-search's loader (streamed per batch beyond the HBM budget)
+    # the target: made resident once (streamed per batch beyond the HBM budget)
     nq_batch = max([sum(b - a for a, b, _qc in batch) for batch in batches] or [1])
-    scan = dbsearch._BatchScan(target_db, qdb, engine, same, nq_batch, 1, search_batchsize, dbsearch._DeviceTimes(engine, None))
+    target = Target.of(target_db, engine, nq_batch, 1)
     reader = qdb if same else QueryDB(db_name)
     starts = reader.store.chain_starts()
-    if target_db["faiss"]:
-        score_mode, cov = ("ip_prenorm" if qdb.normalized else "ip"), 0.0
-    else:
-        score_mode, cov = "cosine", float(mincov)
-    resident = bool(world == 1 and not scan.streamed)
+    score_mode, masked = target_score_mode(target.faiss, qdb.normalized)
+    cov = float(mincov) if masked else 0.0
     logger.info("chain-search: %d query chains of %s (rows %d..%d) against the %d chains of %s in %d batches%s"
                 % (len(runs), query_db, q_lo, q_hi - 1, len(starts) - 1, db_name, len(batches),
-                   "; the target is streamed in blocks of %d rows" % int(search_batchsize) if scan.streamed else ""))
-
-    def target_rows(rows):
-        if not resident:
-            return md.compact_target_rows(engine, reader, rows)
-        if target_db["faiss"]:
-            return scan.shard, None, rows - scan.lo
-        return target_db["database"], target_db["lengths"], rows - target_db["row_lo"]
-
+                   "; the target is streamed in blocks of %d rows" % int(search_batchsize) if target.streamed else ""))
+    target_rows = lambda rows: target.rows_for(rows, reader)
     max_paths = MAX_MAPPING_PATHS if max_mapping_paths is None else int(max_mapping_paths)
     part = os.path.join(tmp, "chain_search_batch.tsv")
     try:
@@ -161,10 +150,7 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
             plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader.store)
             results = md.score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
                                      max_mapping_paths=max_paths)
-            write_all_dom_search_results(results, part, output_headers and number == 0)
-            with open(part, "rb") as src, open(multi_output, "ab") as dst:
-                dst.write(src.read())
-            os.remove(part)
+            append_written(multi_output, part, lambda f: write_all_dom_search_results(results, f, output_headers and number == 0))
             logger.info("chain-search: batch %d of %d done (%d query chains, %d candidate pairs)"
                         % (number + 1, len(batches), len(batch), len(pairs)))
         if rank == 0 and output_headers and not batches:

@@ -21,14 +21,15 @@ import numpy as np
 
 from . import dbsearch as ds
 from . import sharded
-from .dbsearch import _BatchScan, _DeviceTimes, _refuse, read_database
+from .dbsearch import _BatchScan, _DeviceTimes, _refuse, _require_database, read_database
+from .target import Target
 
 logger = logging.getLogger(__name__)
 
 
 def database_lengths(target_db: dict, qdb) -> np.ndarray:
-    """Domain lengths int32 [n] of an opened database: the `.pt` layout's `lengths` (read_database, before the rows go to an
-    engine), the faiss layout's sequence offsets (end - start of the int64 pairs of `sif`, one view of the mapped file)."""
+    """Domain lengths int32 [n] of an opened database: the `.pt` layout's `lengths` (read_database), the faiss layout's
+    sequence offsets (end - start of the int64 pairs of `sif`, one view of the mapped file)."""
     if qdb.faiss:
         offsets = np.frombuffer(qdb.store.seq[0], dtype=np.int64).reshape(-1, 2)
         return (offsets[:, 1] - offsets[:, 0]).astype(np.int32)
@@ -67,9 +68,7 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         _refuse("-c/--mincov must lie in [0, 1], got %r." % (mincov,))
     if topk < 1 or query_batchsize < 1 or search_batchsize < 1:
         _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
-    if not (os.path.exists(db_name + ".json") or (os.path.exists(db_name + ".pt") and os.path.exists(db_name + ".index"))):
-        _refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
-                % (db_name, db_name, db_name))
+    _require_database(db_name)
     target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
     qdb = QueryDB(db_name, loaded=target_db if not target_db["faiss"] else None)
     n, k = int(qdb.n), int(topk)
@@ -86,7 +85,7 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     engine = engine or ds.engine_setup(device)
     torch = engine.torch
     times = _DeviceTimes(engine, timings)
-    scan = _BatchScan(target_db, qdb, engine, True, min(int(query_batchsize), n), k + 1, search_batchsize, times)
+    scan = _BatchScan(Target.of(target_db, engine, min(int(query_batchsize), n), k + 1), qdb, True, k + 1, search_batchsize, times)
     if timings is not None:
         timings["in_place"], timings["streamed"] = scan.in_place, scan.streamed
     logger.info("cluster: %d rows of %s, %d neighbours per row at cosine >= %s, coverage >= %s, batches of %d%s"

@@ -22,7 +22,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import dbutil
-from .multidomain import _TargetStore, domid2chainid
+from .multidomain import _TargetStore, domid2chainid, equal_runs
 
 
 def same_database(prefix_a: str, prefix_b: str) -> bool:
@@ -54,10 +54,10 @@ class QueryDB:
     """Stored embeddings, names, sequences and coordinates of a database's rows, for either layout."""
 
     def __init__(self, db_name: str, loaded=None):
-        """loaded: dbsearch.read_database's dict of this same `.pt` database, before it went to an engine -- its unpickled
-        index and its mapped tensor are used instead of reading both a second time (a database searched against itself)."""
+        """loaded: dbsearch.read_database's dict of this same `.pt` database -- its unpickled index and its mapped tensor are
+        used instead of reading both a second time (a database searched against itself)."""
         self.prefix = db_name
-        shared = loaded is not None and not loaded.get("faiss") and "_engine" not in loaded
+        shared = loaded is not None and not loaded.get("faiss")
         self.store = _TargetStore(db_name, index=loaded["index"] if shared else None)
         self.faiss = self.store.faiss
         self.n = self.store.n
@@ -127,13 +127,8 @@ class QueryDB:
             return rows, rows + 1
         chains = [domid2chainid(n) for n in self.store_names(lo, hi)]
         first, last = np.empty(hi - lo, np.int64), np.empty(hi - lo, np.int64)
-        a = 0
-        while a < hi - lo:
-            b = a + 1
-            while b < hi - lo and chains[b] == chains[a]:
-                b += 1
+        for a, b in equal_runs(chains):
             first[a:b], last[a:b] = lo + a, lo + b
-            a = b
         r = lo - 1                                  # the first and the last run may continue outside the slice
         while r >= 0 and domid2chainid(self.store.name(r)) == chains[0]:
             r -= 1

@@ -44,10 +44,10 @@ import numpy as np
 
 from . import sharded
 from . import tmalign as tm
-from .dbutil import (ascii_conv, coord_conv, db_iterator, db_memmap, read_dbinfo, retrieve_bytes,
-                     retrieve_names_by_idx, retrieve_start_end_by_idx)
+from .dbutil import ascii_conv, coord_conv, read_dbinfo, retrieve_bytes, retrieve_names_by_idx, retrieve_start_end_by_idx
 from .network import network_setup
 from .pdbio import read_pdb, write_pdb
+from .target import Target, score_mode
 
 logger = logging.getLogger(__name__)
 
@@ -56,15 +56,15 @@ logger = logging.getLogger(__name__)
 def read_database(db_name: str, device=None, engine=None) -> dict:
     """Open a database by prefix: `<db>.pt` first, else `<db>.json` (dbsearch.py:50,65).
 
-    pt layout -> {'database': float32 [N,128] on the device (RAW), 'index': list of
-    (path, coords, seq), 'lengths': float32 [N], 'faiss': False, 'mdfn', 'mifn'}; once resident on the
-    engine's device the rows are kept L2-normalised (engine.cosine_rows: the row half of cosine_similarity,
-    done once).  faiss layout -> {'database': json path, 'faiss': True}; the matrix is opened by dbsearch_faiss.
+    pt layout -> {'database': [N,128] on the host (RAW, memory-mapped), 'index': list of (path, coords, seq), 'lengths':
+    float32 [N], 'faiss': False, 'mdfn', 'mifn'}; with an engine this rank's rows are made resident on its device at once,
+    L2-normalised (engine.cosine_rows: the row half of cosine_similarity, done once) -- in the dict's Target (target.py), which
+    the searches ask for the rows.  faiss layout -> {'database': json path, 'faiss': True}; the matrix is opened by Target.of.
     """
     if os.path.exists(db_name + ".pt"):
         import torch
 
-        try:        # memory-mapped: under N ranks every rank then reads only the pages of ITS rows (_to_engine slices first)
+        try:        # memory-mapped: under N ranks every rank then reads only the pages of ITS rows (Target.of slices first)
             raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True, mmap=True)
         except (RuntimeError, TypeError, ValueError):       # (an archive written in the legacy, non-zip format)
             raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True)
@@ -79,32 +79,13 @@ def read_database(db_name: str, device=None, engine=None) -> dict:
         out = {"database": raw, "index": target_index, "lengths": torch.from_numpy(lengths),
                "faiss": False, "mdfn": mdfn, "mifn": mifn}
         if engine is not None:
-            _to_engine(out, engine)
+            Target.of(out, engine)
         return out
     if os.path.exists(db_name + ".json"):
         return {"database": db_name + ".json", "faiss": True}
     logger.error("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
                  % (db_name, db_name, db_name))
     sys.exit(1)
-
-
-def _to_engine(target_dict: dict, engine) -> None:
-    """Make this rank's rows of the `.pt` database resident on the engine's device, normalised once for the
-    cosine search.  'database' / 'lengths' then hold rows [row_lo, row_hi) only."""
-    if target_dict.get("_engine") is engine:
-        return
-    rank, world = sharded.rank_world()
-    n = int(target_dict["database"].shape[0])
-    lo, hi = sharded.shard_bounds(n, world, rank)
-    target_dict["n_rows"] = n
-    target_dict["row_lo"], target_dict["row_hi"] = lo, hi
-    target_dict["database"] = engine.cosine_rows(engine.to_device(target_dict["database"][lo:hi].float().contiguous()))
-    target_dict["lengths"] = engine.to_device(target_dict["lengths"][lo:hi])
-    # (large query batches: the prefiltered search over an image of the normalised rows -- built by the first batch of more than 64
-    #  queries, never by a run with a handful of query domains)
-    target_dict["pf_image"] = (engine.lazy_pf_image(target_dict["database"], engine.UNIT_ROW_BOUND)
-                               if hasattr(engine, "lazy_pf_image") else None)
-    target_dict["_engine"] = engine
 
 
 # ------------------------------------------------------------------ numeric kernels ----
@@ -115,19 +96,15 @@ def search_query_against_db(query_dict, target_dict, mincov, topk, score_correct
     [nq,128] with query_dict['seq'] a list of sequences; returns {'scores', 'indices'} of shape
     [k] or [nq,k] accordingly.  k > Ndb raises, as torch.topk does.
     """
-    engine = engine or target_dict.get("_engine")
-    _to_engine(target_dict, engine)
-    emb = query_dict["embedding"]
+    target = Target.of(target_dict, engine)
+    engine = target.engine
     seqs = query_dict["seq"]
     single = isinstance(seqs, str)
     qlen = np.asarray([len(seqs)] if single else [len(s) for s in seqs], dtype=np.float32)
-    if topk > target_dict["n_rows"]:
+    if topk > target.n:
         raise RuntimeError("selected index k out of range")
-    q = engine.to_device(emb).reshape(-1, 128)
-    extra = {"pf_image": target_dict["pf_image"]} if target_dict.get("pf_image") is not None else {}
-    scores, idx = engine.cosine_topk(target_dict["database"], q, int(topk), lengths=target_dict["lengths"],
-                                     qlen=engine.to_device(qlen), mincov=float(mincov), row_offset=target_dict["row_lo"], **extra)
-    scores, idx = sharded.exchange_and_merge(scores, idx, engine)        # no-op on one rank
+    scores, idx = target.topk(engine.to_device(query_dict["embedding"]).reshape(-1, 128), int(topk), qlen=engine.to_device(qlen),
+                              mincov=mincov)
     if single:
         return {"scores": scores[0], "indices": idx[0]}
     return {"scores": scores, "indices": idx}
@@ -367,43 +344,28 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
         sys.exit(1)
     engine = network.engine
     nq = len(queries)
-    dbinfofname = target_dict["database"]
-    dbinfo = read_dbinfo(dbinfofname)
-    db_dir = os.path.dirname(dbinfofname)
-
-    def path(key):
-        return os.path.join(db_dir, dbinfo[key])
-
-    dbmm = db_memmap(filename=path("dbfname_IP"), shape=(dbinfo["DB_SIZE"], dbinfo["DB_DIM"]))
+    dbinfo, path = _faiss_files(target_dict)
     logger.info("DB iterator using batchsize of " + str(search_batchsize))
 
     query_dicts = _load_queries(queries, inputs_are_ca, _chain_list(pdb_chain, nq))
     emb = sharded.embed_distributed(network, [qd["coords"] for qd in query_dicts])   # ragged launches, data-parallel over ranks
 
-    # this rank's rows of the matrix: [lo, hi) of DB_SIZE (all of them on one rank)
-    rank, world = sharded.rank_world()
-    lo, hi = sharded.shard_bounds(int(dbinfo["DB_SIZE"]), world, rank)
-    shard = _resident_shard(target_dict, engine, dbmm, lo, hi, nq, int(topk))
-    if shard is not None:
-        # resident shard: F.normalize (:303-304) + knn_exact_faiss (:213-248) as ONE call -- for the few queries of a CLI
-        # search that is one launch (normalisation in the scan's prologue, merge by its last workgroup)
-        # (more than 64 queries: the prefiltered search, with the shard's row-norm bound measured once when it became resident)
-        Ds, Is = knn_exact(emb, [shard], int(topk), engine, row_offset=lo, to_host=False, raw_queries=True,
-                           row_norm_bound=target_dict["_resident"].get("row_norm_bound"), pf_image=target_dict["_resident"].get("pf_image"))
-    else:
-        logger.info("database shard of %d rows exceeds the resident budget: streaming blocks of %d rows"
-                    % (hi - lo, int(search_batchsize)))
-        emb = engine.normalized(emb, 1e-12)                                 # F.normalize once, out of place; then block by block
-        Ds, Is = knn_exact(emb, db_iterator(dbmm[lo:hi], int(search_batchsize)), int(topk), engine, row_offset=lo,
-                           to_host=False)
-    Ds, Is = sharded.exchange_and_merge(Ds, Is, engine)                   # all-gather + merge; no-op on one rank
+    # this rank's rows of the matrix, resident (F.normalize, :303-304, + knn_exact_faiss, :213-248, as ONE launch for the few
+    # queries of a CLI search; more than 64 queries: the prefiltered search) or streamed block by block; then the exchange
+    Ds, Is = Target.of(target_dict, engine, nq, int(topk)).topk(emb, int(topk), raw_queries=True, search_batchsize=search_batchsize)
     D, I = Ds.cpu().numpy(), Is.cpu().numpy()
     results = [dict() for _ in range(nq)]
     all_results = [dict() for _ in range(nq)]
-    if rank != 0:
+    if sharded.rank_world()[0] != 0:
         return results, all_results                                       # rank 0 assembles the hit records
     return _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
                               _aligner_device(network, device))
+
+
+def _faiss_files(target_dict: dict):
+    """(the json's contents, key -> path of the file it names) of a faiss-layout database."""
+    dbinfo, db_dir = read_dbinfo(target_dict["database"]), os.path.dirname(target_dict["database"])
+    return dbinfo, lambda key: os.path.join(db_dir, dbinfo[key])
 
 
 def _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
@@ -473,22 +435,6 @@ def _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode,
     if n_tm_exclude > tm_excluded_before:
         logger.info("Excluded " + str(n_tm_exclude - int(tm_excluded_before)) + " hits (across all query domains) by TM-score threshold(>=" + str(mintm) + ")")
     return results, all_results
-
-
-def _resident_shard(target_dict: dict, engine, dbmm, lo: int, hi: int, nq: int, k: int):
-    """Rows [lo,hi) of the matrix as one device tensor, kept in `target_dict` across calls on the same
-    database; None when they do not fit the engine's resident budget (-> streaming)."""
-    cache = target_dict.setdefault("_resident", {})
-    if cache.get("engine") is engine and cache.get("span") == (lo, hi):
-        return cache["shard"]
-    cache.clear()
-    if (hi - lo) * dbmm.shape[1] * 4 > engine.resident_budget(nq, k):
-        return None
-    cache.update(engine=engine, span=(lo, hi), shard=engine.upload_rows(dbmm, lo, hi))
-    if hasattr(engine, "row_norm_bound"):           # (the CPU oracle engine of the tests has no prefiltered search)
-        cache["row_norm_bound"] = engine.row_norm_bound(cache["shard"])
-        cache["pf_image"] = engine.lazy_pf_image(cache["shard"], cache["row_norm_bound"])
-    return cache["shard"]
 
 
 # ------------------------------------------------------------------ dispatcher ---------
@@ -590,52 +536,28 @@ class _DeviceTimes:
 
 
 class _BatchScan:
-    """A database as the target of query batches taken from a database (run_dbsearch_db, cluster.run_cluster): this rank's rows
-    made resident once (streamed through engine.device_blocks beyond the HBM budget), then per batch of query rows [b0, b1)
-    the scan at k', the exchange + merge under several ranks, and the drop step down to kout entries at or above min_score."""
+    """The per-batch half of a search of query batches taken from a database (run_dbsearch_db, cluster.run_cluster) against a
+    Target: per batch of query rows [b0, b1) the scan at k' with its exchange + merge (Target.topk) and the drop step down to
+    kout entries at or above min_score, between timing marks."""
 
-    def __init__(self, target_db: dict, qdb, engine, same: bool, nq_batch: int, kk: int, search_batchsize: int, times):
-        self.target_db, self.qdb, self.engine, self.kk, self.times = target_db, qdb, engine, int(kk), times
-        self.search_batchsize = int(search_batchsize)
-        self.shard = self.dbmm = None
-        rank, world = sharded.rank_world()
-        if target_db["faiss"]:
-            dbinfo = read_dbinfo(target_db["database"])
-            n_target = int(dbinfo["DB_SIZE"])
-            self.dbmm = db_memmap(filename=os.path.join(os.path.dirname(target_db["database"]), dbinfo["dbfname_IP"]),
-                                  shape=(dbinfo["DB_SIZE"], dbinfo["DB_DIM"]))
-            self.lo, self.hi = sharded.shard_bounds(n_target, world, rank)
-            self.shard = _resident_shard(target_db, engine, self.dbmm, self.lo, self.hi, int(nq_batch), self.kk)
-            if self.shard is None:
-                logger.info("database shard of %d rows exceeds the resident budget: streaming blocks of %d rows per query batch"
-                            % (self.hi - self.lo, self.search_batchsize))
-        else:
-            _to_engine(target_db, engine)
+    def __init__(self, target: Target, qdb, same: bool, kk: int, search_batchsize: int, times):
+        self.target, self.qdb, self.kk, self.search_batchsize, self.times = target, qdb, int(kk), int(search_batchsize), times
         # the same faiss-layout database on one rank: the resident rows ARE the queries (normalised, 16-byte aligned at 512 B per
         # row), read in place by the scan.  (`.pt`: the resident rows were normalised in place, the raw queries come from the file.)
-        self.in_place = bool(same and qdb.faiss and world == 1 and self.shard is not None)
-        self.streamed = bool(target_db["faiss"] and self.shard is None)
+        self.in_place = bool(same and qdb.faiss and target.whole)
+        self.streamed = target.streamed
 
     def search(self, b0: int, b1: int, seqs, mincov: float, d_lo, d_hi, kout: int, min_score: float, out=None):
         """Query rows [b0, b1) of the query database -> (scores [nq,kout], rows [nq,kout], count [nq]) on the device, the rows
         [d_lo[q], d_hi[q]) of each query excluded; seqs: the queries' sequences (the `.pt` layout's length mask; unused in the
         faiss layout).  out: the preallocated triple the drop step writes into."""
-        target_db, engine, qdb, kk, times = self.target_db, self.engine, self.qdb, self.kk, self.times
-        q = self.shard[b0:b1] if self.in_place else engine.to_device(qdb.embeddings(b0, b1))
+        target, qdb, times = self.target, self.qdb, self.times
+        engine = target.engine
+        q = target.rows[b0:b1] if self.in_place else engine.to_device(qdb.embeddings(b0, b1))
         t0 = times.mark()
-        if not target_db["faiss"]:
-            top = search_query_against_db({"seq": seqs, "embedding": q}, target_db, mincov, kk, engine=engine)
-            Ds, Is = top["scores"], top["indices"]
-        else:
-            if self.shard is not None:
-                Ds, Is = knn_exact(q, [self.shard], kk, engine, log=_QUIET, row_offset=self.lo, to_host=False, raw_queries=not qdb.normalized,
-                                   row_norm_bound=target_db["_resident"].get("row_norm_bound"),
-                                   pf_image=target_db["_resident"].get("pf_image"))
-            else:
-                qn = q if qdb.normalized else engine.normalized(q, 1e-12)
-                Ds, Is = knn_exact(qn, db_iterator(self.dbmm[self.lo:self.hi], self.search_batchsize), kk, engine, log=_QUIET,
-                                   row_offset=self.lo, to_host=False)
-            Ds, Is = sharded.exchange_and_merge(Ds, Is, engine)
+        qlen = None if target.faiss else engine.to_device(np.asarray([len(s) for s in seqs], dtype=np.float32))
+        Ds, Is = target.topk(q, self.kk, qlen=qlen, mincov=mincov, raw_queries=not qdb.normalized,
+                             search_batchsize=self.search_batchsize, log=_QUIET)
         t1 = times.mark()
         times.add("scan", t0, t1)
         kw = {} if out is None else {"out": out}
@@ -650,32 +572,24 @@ class _ChainStep:
     results of a chain's earlier rows are carried over on the host.  Target rows: the resident matrix when this process
     holds all rows (one rank, not streamed), else the needed chain runs read from the database files (rank 0)."""
 
-    def __init__(self, qdb, q_lo: int, q_hi: int, target_db: dict, db_name: str, same: bool, exclude_self: bool, engine, scan,
+    def __init__(self, qdb, q_lo: int, q_hi: int, target: Target, db_name: str, same: bool, exclude_self: bool,
                  mincos: float, mincov: float, max_mapping_paths: int, times, timings):
         from . import multidomain as md
         from .dbquery import QueryDB
-        self.md, self.qdb, self.q_lo, self.engine, self.scan, self.target_db = md, qdb, q_lo, engine, scan, target_db
-        self.mincos, self.mincov, self.max_paths, self.times = float(mincos), float(mincov), int(max_mapping_paths), times
+        self.md, self.qdb, self.q_lo, self.engine, self.target = md, qdb, q_lo, target.engine, target
+        self.mincos, self.max_paths, self.times = float(mincos), int(max_mapping_paths), times
         self.exclude_self = exclude_self
         chains = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
         self.chains = chains
         self.run_end = np.empty(q_hi - q_lo, np.int64)          # one past the last row (global) of each query row's run
-        a = 0
-        while a < len(chains):
-            b = a + 1
-            while b < len(chains) and chains[b] == chains[a]:
-                b += 1
+        for a, b in md.equal_runs(chains):
             self.run_end[a:b] = q_lo + b
-            a = b
         self.reader = qdb if same else QueryDB(db_name)
         self.owns_reader = not same
-        self.resident = bool(sharded.rank_world()[1] == 1 and not scan.streamed)
-        if target_db["faiss"]:
-            self.score_mode = "ip_prenorm" if qdb.normalized else "ip"
-        else:
-            self.score_mode = "cosine"
+        self.score_mode, masked = score_mode(target.faiss, qdb.normalized)
+        self.mincov = float(mincov) if masked else 0.0
         if timings is not None:
-            timings["md_resident"] = self.resident
+            timings["md_resident"] = target.whole
             timings["md_candidates_skipped"] = 0
         self.timings = timings
         self.pending = []                                      # (global row, query name, its reported results) of the open chain
@@ -684,13 +598,6 @@ class _ChainStep:
     def close(self) -> None:
         if self.owns_reader:
             self.reader.close()
-
-    def _target_rows(self, rows):
-        if not self.resident:
-            return self.md.compact_target_rows(self.engine, self.reader, rows)
-        if self.target_db["faiss"]:
-            return self.scan.shard, None, rows - self.scan.lo
-        return self.target_db["database"], self.target_db["lengths"], rows - self.target_db["row_lo"]
 
     def batch(self, b0: int, b1: int, query_dicts, results) -> list:
         """The result tuples of the chains that end in query rows [b0, b1), in query-chain order."""
@@ -730,8 +637,9 @@ class _ChainStep:
         if self.score_mode == "cosine":
             qlen = engine.to_device(np.asarray([len(s) for s in self.qdb.seqs(r0, r1)], dtype=np.float32))
         skipped = []
-        res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader.store, self._target_rows, self.mincos,
-                             qlen=qlen, mincov=self.mincov if self.score_mode == "cosine" else 0.0, own_rows=own or None,
+        target_rows = lambda rows: self.target.rows_for(rows, self.reader)
+        res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader.store, target_rows, self.mincos,
+                             qlen=qlen, mincov=self.mincov, own_rows=own or None,
                              max_mapping_paths=self.max_paths, log=logger.debug, skipped=skipped, times=self.times)
         self.skipped.extend(skipped)
         if self.timings is not None:
@@ -739,13 +647,11 @@ class _ChainStep:
         return res
 
 
-def _append_tsv(results, path: str, part: str, fields, header: bool) -> None:
-    """One batch's rows behind what `path` holds already, written by results.write_search_results itself."""
-    from .results import write_search_results
-    write_search_results(results=results, output_file=part, format_list=fields, header=header)
-    with open(part, "rb") as src, open(path, "ab") as dst:
-        dst.write(src.read())
-    os.remove(part)
+def _require_database(prefix: str) -> None:
+    """Refuse a prefix that names no database of either layout (the `.pt` layout needs its `.index` too)."""
+    if not (os.path.exists(prefix + ".json") or (os.path.exists(prefix + ".pt") and os.path.exists(prefix + ".index"))):
+        _refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
+                % (prefix, prefix, prefix))
 
 
 def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="cuda", topk: int = 1, fastmode: bool = False,
@@ -777,7 +683,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     from types import SimpleNamespace
 
     from .dbquery import QueryDB, parse_row_slice, same_database
-    from .results import SEARCH_FIELDS, embedding_only_format
+    from .results import SEARCH_FIELDS, append_written, embedding_only_format, write_all_dom_search_results, write_search_results
 
     t_start = time.perf_counter()
     if engine is None:
@@ -795,9 +701,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         _refuse("--exclude_self / --exclude_same_chain remove the query's own rows from its hits: they need the query database "
                 "and the target database to be the same, got %s and %s." % (query_db, db_name))
     for prefix in (query_db, db_name):
-        if not (os.path.exists(prefix + ".json") or (os.path.exists(prefix + ".pt") and os.path.exists(prefix + ".index"))):
-            _refuse("%s is not a valid db or the path basename is incorrect; neither %s.pt nor %s.json were found."
-                    % (prefix, prefix, prefix))
+        _require_database(prefix)
     target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
     # (a `.pt` database searched against itself: ONE unpickled index and one mapped tensor serve both sides)
     qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
@@ -808,12 +712,8 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     if target_db["faiss"]:
         if search_type != "IP":
             _refuse("Invalid/unsupported faiss search type: " + search_type + "\n\tOnly 'IP' is currently supported.")
-        dbinfo = read_dbinfo(target_db["database"])
-        db_dir = os.path.dirname(target_db["database"])
+        dbinfo, path = _faiss_files(target_db)
         n_target = int(dbinfo["DB_SIZE"])
-
-        def path(key):
-            return os.path.join(db_dir, dbinfo[key])
     else:
         n_target = int(target_db["database"].shape[0])
     ex_lo = ex_hi = np.zeros(q_hi - q_lo, np.int64)                       # lo >= hi: nothing excluded
@@ -846,20 +746,19 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     times = _DeviceTimes(engine, timings)
     network = SimpleNamespace(engine=engine)
     aligner_device = _aligner_device(network, device)
-    nq_batch = min(int(query_batchsize), q_hi - q_lo)
-    scan = _BatchScan(target_db, qdb, engine, same, nq_batch, kk, search_batchsize, times)
-    in_place = scan.in_place
+    target = Target.of(target_db, engine, min(int(query_batchsize), q_hi - q_lo), kk)      # resident once, or streamed per batch
+    scan = _BatchScan(target, qdb, same, kk, search_batchsize, times)
     logger.info("db-search: %d queries of %s against %d rows of %s in batches of %d (k = %d%s)%s"
                 % (q_hi - q_lo, query_db, n_target, db_name, int(query_batchsize), int(topk),
                    ", %d fetched: up to %d rows excluded per query" % (kk, max_excluded) if exclude_self else "",
-                   "; queries read in place from the resident rows" if in_place else ""))
+                   "; queries read in place from the resident rows" if scan.in_place else ""))
     if timings is not None:
-        timings["in_place"], timings["streamed"] = bool(in_place), scan.streamed
+        timings["in_place"], timings["streamed"] = scan.in_place, scan.streamed
     d_lo, d_hi = engine.to_device(ex_lo), engine.to_device(ex_hi)        # once for the run: a batch's ranges are a slice
     chain_step = None
     if multi_domain_search and rank == 0:
         from .multidomain import MAX_MAPPING_PATHS
-        chain_step = _ChainStep(qdb, q_lo, q_hi, target_db, db_name, same, exclude_self, engine, scan, mincos, mincov,
+        chain_step = _ChainStep(qdb, q_lo, q_hi, target, db_name, same, exclude_self, mincos, mincov,
                                 MAX_MAPPING_PATHS if max_mapping_paths is None else max_mapping_paths, times, timings)
     md_all = {}
     tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
@@ -894,15 +793,12 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
                 results.append(res)
                 all_results.append(all_res)
         part = os.path.join(tmp, "db_search_batch.tsv")
-        _append_tsv(results, search_output, part, fields, header and b0 == q_lo)
-        if report_insignificant_hits:
-            _append_tsv(all_results, all_output, part, fields, header and b0 == q_lo)
+        first = header and b0 == q_lo
+        for out_path, per_batch in zip(written, (results, all_results)):
+            append_written(out_path, part, lambda f: write_search_results(results=per_batch, output_file=f, format_list=fields, header=first))
         if chain_step is not None:
-            from .results import write_all_dom_search_results
-            write_all_dom_search_results(chain_step.batch(b0, b1, query_dicts, results), part, header and b0 == q_lo)
-            with open(part, "rb") as src, open(multi_output, "ab") as dst:
-                dst.write(src.read())
-            os.remove(part)
+            lines = chain_step.batch(b0, b1, query_dicts, results)
+            append_written(multi_output, part, lambda f: write_all_dom_search_results(lines, f, first))
         if metadata_json:
             for out_path, per_batch in zip(written, (results, all_results)):
                 md_all.setdefault(out_path, []).extend(hit["metadata"] for per_query in per_batch for hit in per_query.values()

@@ -69,19 +69,24 @@ def domid2chainid(domain_id: str) -> str:
     return stem[: -len("_TED")] if stem.endswith("_TED") else stem
 
 
+def equal_runs(keys: Sequence) -> List[Tuple[int, int]]:
+    """(first, one past the last) position of every run of adjacent equal keys, in order; a key that comes back after another
+    one starts a new run."""
+    runs, a = [], 0
+    for b in range(1, len(keys) + 1):
+        if b == len(keys) or keys[b] != keys[a]:
+            runs.append((a, b))
+            a = b
+    return runs
+
+
 def chain_runs(names: Sequence[str]) -> np.ndarray:
     """int64 [nchains + 1]: the first row of every run of adjacent names with one domid2chainid (its rstrip('.pdb') quirk
     included), closed by len(names) -- the target chains of mode `database_cosine`, where a chain IS a run of rows.  Two runs
     with one chain id that are not adjacent are two chains here (`exhaustive_cosine` would merge them by name; the reference
     assumes adjacency, :363-394).  A plain loop: about a microsecond-scale call of domid2chainid per name."""
-    starts, prev = [], None
-    for row, name in enumerate(names):
-        chain = domid2chainid(name)
-        if chain != prev:
-            starts.append(row)
-            prev = chain
-    starts.append(len(names))
-    return np.asarray(starts, dtype=np.int64)
+    starts = [a for a, _b in equal_runs([domid2chainid(name) for name in names])]
+    return np.asarray(starts + [len(names)], dtype=np.int64)
 
 
 def chain_mappings(tm: np.ndarray, query_chain: str, hit_chain: str, query_domains: Sequence[str],
@@ -278,8 +283,8 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
         return _multi_domain_embedding(queries, None, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
                                        threads, max_mapping_paths, True, target_db, search_batchsize)
     if mode == "exhaustive_cosine":
-        return _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov,
-                                    network, threads, max_mapping_paths)
+        return _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov,
+                                       network, threads, max_mapping_paths, False, None, 0)
     check_backend(tmalign_backend, device)
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
@@ -287,56 +292,44 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
     if tmalign_backend == "auto" and find_tmalign() is None:
         raise FileNotFoundError("multi-domain search aligns every query domain with every candidate target domain: "
                                 "it needs a TM-align binary (set $MERIZO_TMALIGN)")
-    if not inputs_from_easy_search:
-        chains = pdb_chain.rstrip(",").split(",") if pdb_chain else ["A"] * len(queries)
-        queries = [read_pdb(pdbfile=q, pdb_chain=c) for q, c in zip(queries, chains)]
-    names = [os.path.basename(q["name"]) for q in queries]
-    names = [n[: -len(".pdb")] if n.endswith(".pdb") else n for n in names]
-    structures = {n: q for n, q in zip(names, queries)}
-    query_chains = [_MERIZO_SUFFIX.sub("", n) for n in names] if inputs_from_easy_search else ["A"] * len(names)
+    names, query_chains, queries = _query_structures(queries, inputs_from_easy_search, pdb_chain)
+    structures = dict(zip(names, queries))
     hits = group_hits(names, query_chains, search_results)
 
     store = _TargetStore(db_name)
-    if tmalign_backend == "hip":
-        try:
-            return _multi_domain_hip(hits, structures, store, fastmode, mintm, device)
-        finally:
-            store.close()
-    results = []
     try:
+        if tmalign_backend == "hip":
+            return _multi_domain_hip(hits, structures, store, fastmode, mintm, device)
+        results = []
         for qc, domains in hits.items():
-            nqd = len(domains)
-            if nqd < 2:
-                logger.info("Query chain %s: only one detected domain, multi-domain hits equal the per-domain hits." % qc)
+            entries = _chain_entries(qc, domains, store)
+            if entries is None:
                 continue
-            rows = set()
-            for per_domain in domains.values():
-                for hit in per_domain:
-                    chain_rows = sibling_rows(hit["hi"], hit["hc"], store.n, store.name)
-                    if len(chain_rows) >= nqd:                 # target chains with fewer domains cannot match
-                        rows.update(chain_rows)
-            if not rows:
-                logger.info("Query chain %s: every hit chain has fewer domains than the query; try a larger -k." % qc)
-                continue
-            entries = [store.entry(r) for r in sorted(rows)]
             tmp = os.path.join(tmp_root, "MD_search_structures_" + qc)
             os.makedirs(tmp, exist_ok=True)
             try:
                 qfiles = [write_pdb(tmp, structures[qd]["coords"], structures[qd]["seq"], name="FSQUERY-" + qd) for qd in domains]
                 tfiles = [write_pdb(tmp, e[1], e[2], name="FSTARGET-" + e[0]) for e in entries]
-                logger.info("TM-align %d query domains of chain %s against %d target domains" % (nqd, qc, len(tfiles)))
+                logger.info("TM-align %d query domains of chain %s against %d target domains" % (len(domains), qc, len(tfiles)))
                 scores = tm_matrix(qfiles, tfiles, threads=threads, mintm=mintm, options="-fast" if fastmode else None)
             finally:
                 shutil.rmtree(tmp, ignore_errors=True)
-            hit_chain = np.asarray([domid2chainid(e[0]) for e in entries])
-            info = [{"hd": e[0], "hc": hc, "hi": e[3], "hm": e[4]} for e, hc in zip(entries, hit_chain)]
-            qds = list(domains.keys())
-            for hc in np.unique(hit_chain):
-                cols = np.flatnonzero(hit_chain == hc)
-                results.extend(chain_mappings(scores[:, cols], qc, str(hc), qds, [info[c] for c in cols]))
-            logger.info("Finished multi-domain search for query chain %s." % qc)
+            results.extend(_entry_mappings(scores, qc, list(domains.keys()), entries))
+        return results
     finally:
         store.close()
+
+
+def _entry_mappings(scores: np.ndarray, qc: str, qds: List[str], entries) -> list:
+    """Step 4 for one query chain: its score matrix over `entries` (_chain_entries) split by the entries' chain id (np.unique
+    order), chain_mappings per target chain."""
+    hit_chain = np.asarray([domid2chainid(e[0]) for e in entries])
+    info = [{"hd": e[0], "hc": hc, "hi": e[3], "hm": e[4]} for e, hc in zip(entries, hit_chain)]
+    results = []
+    for hc in np.unique(hit_chain):
+        cols = np.flatnonzero(hit_chain == hc)
+        results.extend(chain_mappings(scores[:, cols], qc, str(hc), qds, [info[c] for c in cols]))
+    logger.info("Finished multi-domain search for query chain %s." % qc)
     return results
 
 
@@ -378,12 +371,7 @@ def _multi_domain_hip(hits, structures, store, fastmode: bool, mintm: float, dev
         at += n
         scores = scores.reshape(len(qds), len(entries))
         scores[scores < mintm] = 0.0
-        hit_chain = np.asarray([domid2chainid(e[0]) for e in entries])
-        info = [{"hd": e[0], "hc": hc, "hi": e[3], "hm": e[4]} for e, hc in zip(entries, hit_chain)]
-        for hc in np.unique(hit_chain):
-            cols = np.flatnonzero(hit_chain == hc)
-            results.extend(chain_mappings(scores[:, cols], qc, str(hc), qds, [info[c] for c in cols]))
-        logger.info("Finished multi-domain search for query chain %s." % qc)
+        results.extend(_entry_mappings(scores, qc, qds, entries))
     return results
 
 
@@ -431,16 +419,11 @@ def compact_target_rows(engine, reader, rows: np.ndarray):
     copy was made with, so the bits are the resident copy's."""
     rows = np.asarray(rows, dtype=np.int64)
     parts, lens = [], []
-    a = 0
-    while a < len(rows):                                      # one read per run of adjacent rows (a chain is one run)
-        b = a + 1
-        while b < len(rows) and rows[b] == rows[b - 1] + 1:
-            b += 1
+    for a, b in equal_runs((rows - np.arange(len(rows))).tolist()):       # one read per run of adjacent rows (a chain is one run)
         lo, hi = int(rows[a]), int(rows[b - 1]) + 1
         parts.append(reader.embeddings(lo, hi))
         if not reader.faiss:
             lens.extend(len(s) for s in reader.seqs(lo, hi))
-        a = b
     matrix = engine.to_device(np.concatenate(parts, axis=0) if parts else np.zeros((0, 128), np.float32))
     if reader.faiss:
         return matrix, None, np.arange(len(rows), dtype=np.int64)
@@ -561,47 +544,26 @@ def merge_candidates(parts: Sequence[np.ndarray]) -> np.ndarray:
 def database_candidates(engine, reader, target_db: Optional[dict], starts: np.ndarray, q_emb, score_mode: str, qchain: np.ndarray,
                         mincos: float, qlen, mincov: float, search_batchsize: int = 262144, route: str = "lane") -> np.ndarray:
     """ms_md_chain_scan over this process's rows of the database -> the candidates of ALL rows, identical on every rank (a
-    collective under a process group: sharded.gather_pairs).  The rows: the resident copy the search left in target_db (the
-    `.pt` rows as dbsearch._to_engine normalised them, the faiss shard of target_db['_resident']) read in place; else streamed
-    from the files once more, block by block (engine.device_blocks), each block a range of its own (range_candidates).
+    collective under a process group: sharded.gather_pairs).  The rows: the resident copy the search left in target_db
+    (target.Target.for_reader) read in place; else streamed from the files once more, block by block (Target.blocks), each
+    block a range of its own (range_candidates).
     route: engine.md_chain_scan's (the pairs do not depend on it)."""
     from . import sharded
-    rank, world = sharded.rank_world()
-    lo, hi = sharded.shard_bounds(reader.n, world, rank)
+    from .target import Target
     nqc = int(qchain.shape[0])
     qchain_d = engine.to_device(np.ascontiguousarray(qchain, dtype=np.int32))
+    kw = {} if route == "lane" else {"route": route}              # (engines without a matrix route keep their signature)
+    target = Target.for_reader(target_db, engine, reader)
+    if target.hi > target.lo:
+        logger.info("multi-domain search: scanning the %d resident rows of this process for matching chains" % (target.hi - target.lo)
+                    if not target.streamed else
+                    "multi-domain search: the database rows are not resident: streaming rows %d..%d once more for the chain scan, "
+                    "in blocks of %d" % (target.lo, target.hi - 1, max(1, int(search_batchsize))))
     parts = []
-
-    def scan_block(block, a, lengths=None):
-        kw = {} if route == "lane" else {"route": route}          # (engines without a matrix route keep their signature)
+    for block, a, lengths in target.blocks(reader, search_batchsize):
         scan = lambda table: engine.md_chain_scan(block, engine.to_device(table), q_emb, score_mode, qchain_d, float(mincos),
                                                   lengths=lengths, qlen=qlen, mincov=float(mincov), **kw)[0]
         parts.append(range_candidates(starts, a, a + int(block.shape[0]), nqc, scan))
-
-    resident = None
-    if target_db is not None and reader.faiss:
-        cache = target_db.get("_resident") or {}
-        if cache.get("engine") is engine and cache.get("span") == (lo, hi):
-            resident = (cache["shard"], None)
-    elif target_db is not None and target_db.get("_engine") is engine and (target_db["row_lo"], target_db["row_hi"]) == (lo, hi):
-        resident = (target_db["database"], target_db["lengths"])
-    if hi > lo and resident is not None:
-        logger.info("multi-domain search: scanning the %d resident rows of this process for matching chains" % (hi - lo))
-        scan_block(resident[0], lo, resident[1])
-    elif hi > lo:
-        step = max(1, int(search_batchsize))
-        logger.info("multi-domain search: the database rows are not resident: streaming rows %d..%d once more for the chain scan, "
-                    "in blocks of %d" % (lo, hi - 1, step))
-        if reader.faiss:
-            a = lo
-            for block in engine.device_blocks(dbutil.db_iterator(reader.matrix[lo:hi], step)):
-                scan_block(block, a)
-                a += int(block.shape[0])
-        else:
-            for a in range(lo, hi, step):
-                b = min(hi, a + step)
-                rows = engine.cosine_rows(engine.to_device(reader.embeddings(a, b)))
-                scan_block(rows, a, engine.to_device(np.asarray([len(x) for x in reader.seqs(a, b)], dtype=np.float32)))
     return merge_candidates([sharded.gather_pairs(merge_candidates(parts), engine.device)])
 
 
@@ -623,24 +585,19 @@ def candidate_plans(pairs: np.ndarray, served: Sequence[str], hits, q_first: Dic
     return plans
 
 
-def _multi_domain_cosine(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
-                         threads, max_mapping_paths):
-    """multi_domain_search(mode='exhaustive_cosine'): the query embeddings recomputed with the search's encoder (ragged
-    embedding is bit-identical to one-by-one), the target rows read from the database files (compact_target_rows)."""
-    return _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
-                                   threads, max_mapping_paths, False, None, 0)
-
-
 def _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
                             threads, max_mapping_paths, whole_database: bool, target_db, search_batchsize):
     """Both embedding-score modes.  whole_database (`database_cosine`): the candidates are every (query chain, target chain) pair
     of the database that passes the two early exits (database_candidates: EVERY rank of a process group scans its rows and
     takes part in the gather; rank 0 alone goes on to the scoring half and returns results, the others return None); else
-    (`exhaustive_cosine`) the chains the hits of search_results name."""
+    (`exhaustive_cosine`) the chains the hits of search_results name.  The query embeddings are recomputed with the search's
+    encoder (ragged embedding is bit-identical to one-by-one); the scoring half reads its target rows from the database files
+    (compact_target_rows)."""
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
         return None
     from .dbquery import QueryDB
+    from .target import score_mode as target_score_mode
     names, query_chains, structures = _query_structures(queries, inputs_from_easy_search, pdb_chain)
     if len(set(names)) != len(names):
         raise ValueError("multi-domain search: query domain names must be unique")
@@ -658,7 +615,8 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
     reader = QueryDB(db_name)
     try:
         qlen = None if reader.faiss else engine.to_device(np.asarray([len(structures[i]["seq"]) for i in order], dtype=np.float32))
-        score_mode, cov = ("ip", 0.0) if reader.faiss else ("cosine", mincov)
+        score_mode, masked = target_score_mode(reader.faiss, False)
+        cov = mincov if masked else 0.0
         target_rows = lambda rows: compact_target_rows(engine, reader, rows)
         if not whole_database:
             return cosine_step(hits, q_first, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,

@@ -140,3 +140,12 @@ def write_all_dom_search_results(results, output_file: str, header: bool) -> Non
             out.write("query_chain\tnqd\thit_chain\tnhd\tmatch_category\tmatch_info\thit_metadata\n")
         for res in results:
             out.write("\t".join(str(a) for a in res) + "\n")
+
+
+def append_written(path: str, part: str, write) -> None:
+    """One batch's rows behind what `path` holds already: write(part) writes the part file with a writer of this module,
+    its bytes are appended to `path`, the part file is removed."""
+    write(part)
+    with open(part, "rb") as src, open(path, "ab") as dst:
+        dst.write(src.read())
+    os.remove(part)

@@ -128,7 +128,7 @@ def test_planted_database_equals_the_restated_driver_with_complete_hit_lists(pla
     driver_ref fed with every row at or above mincos; inorder -> 3, reversed -> 0, inserted -> 1, nearmiss absent, five_copy -> 3,
     and the query's own chain in category 3 (nothing excludes it)."""
     from merizo_search_amd.foldclass import dbsearch as ds
-    from merizo_search_amd.foldclass.dbutil import db_memmap, read_dbinfo
+    from merizo_search_amd.foldclass.target import Target
     engine = ds.engine_setup("cuda:0")
     prefix = os.path.join(planted[0], layout)
     n = len(planted[1])
@@ -136,9 +136,8 @@ def test_planted_database_equals_the_restated_driver_with_complete_hit_lists(pla
         target = ds.read_database(prefix, engine=engine)
     else:
         target = ds.read_database(prefix)
-        info = read_dbinfo(target["database"])
-        dbmm = db_memmap(os.path.join(os.path.dirname(target["database"]), info["dbfname_IP"]), (info["DB_SIZE"], info["DB_DIM"]))
-        assert ds._resident_shard(target, engine, dbmm, 0, n, 8, 10) is not None
+        resident = Target.of(target, engine, 8, 10)
+        assert resident.rows is not None and (resident.lo, resident.hi) == (0, n)
     got, want, pairs = _planted_run(planted, layout, engine, target)
     assert got == want and len(got) > 5
     fam = mc.FAMILY

@@ -179,7 +179,9 @@ def test_run_dbsearch_target_db_none_takes_the_old_path(planted, tmp_path, monke
     assert run(target_db=None) == old and len(opened) == 2
     target = real(prefix, engine=net.engine)
     assert run(target_db=target) == old and len(opened) == 2
+    from merizo_search_amd.foldclass.target import Target
+    resident = Target.cached(target, net.engine)
     if layout == "pt":
-        assert target["_engine"] is net.engine and (target["row_lo"], target["row_hi"]) == (0, len(planted[1]))
+        assert resident.engine is net.engine and (resident.lo, resident.hi) == (0, len(planted[1]))
     else:
-        assert target["_resident"]["span"] == (0, len(planted[1])) and target["_resident"]["shard"].shape == (len(planted[1]), 128)
+        assert (resident.lo, resident.hi) == (0, len(planted[1])) and resident.rows.shape == (len(planted[1]), 128)

@@ -372,6 +372,44 @@ int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *chain_start, 
                         int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, float row_norm_bound,
                         int64_t *out_stats, void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* The best mapping of every (query chain, target chain) candidate: the step behind ms_md_chain_scores, on its buffers.
+ * Candidate c has a matrix M [nqd,nhd], row-major, at scores + mat_off[c] (scores float32 [total_cells]) -- what
+ * ms_md_chain_scores wrote: cut cells are +0.0f.  cand is the [ncand][4] array that call takes; only nqd = cand[c][1] and
+ * nhd = cand[c][3] are read.
+ *   cell (i, j) is ALLOWED iff M[i][j] != 0 and it is not NaN (-0.0 is zero).  Its weight is the integer
+ *        w = llrint(clamp((double) M[i][j], -2^20, 2^20) * 2^32), rounded to nearest even: exact for 2^-9 <= |M[i][j]| <= 2^20.
+ *        Totals are int64 sums of w: "maximum" carries no rounding, no summation order and no floating-point ties.
+ *   kind 0, any order: a mapping gives every query domain i a distinct column path[i] with every cell (i, path[i]) allowed;
+ *        one mapping of maximum total is reported.  Which one: rows are inserted in order 0..nqd-1 by shortest augmenting
+ *        path with row and column potentials on the costs -w (the classic O(nqd^2 nhd) form: the search stands on a column,
+ *        relaxes the slack of every unvisited column from that column's row, moves to the unvisited column of smallest
+ *        slack, shifts the potentials by that slack, until it reaches an unmatched column); every argmin over columns
+ *        takes the smallest column.
+ *   kind 1, order-preserving: the same with path strictly increasing.  D[0][j] = w[0][j]; D[i][j] = w[i][j] + max over
+ *        j' < j of D[i-1][j'], over allowed cells with a finite prefix.  The last column is the smallest argmax of D[nqd-1];
+ *        each earlier column is the smallest argmax of D[i] over the columns below the one chosen after it.
+ * Outputs (device); EVERY entry of every candidate is written, so the result is a function of the inputs alone:
+ *   out_status int32 [ncand][2], per kind: 1 = mapping found, 0 = none exists, -1 = bad descriptor (nqd < 1, nhd < 1,
+ *        mat_off[c] < 0 or mat_off[c] + nqd * nhd > total_cells), -2 = beyond this entry point's limits (nqd > 64 or
+ *        nhd > MS_MD_BEST_MAX_HD; tested before the offset);
+ *   out_total  int64 [ncand][2]: the sum of w over the path; 0 unless the status is 1;
+ *   out_path   int32 [ncand][2][64]: path[i] for i < nqd when the status is 1; -1 everywhere else;
+ *   out_cell   float32 [ncand][2][64]: M[i][path[i]], bit for bit; +0.0f everywhere else.
+ * Descriptors are data, not trusted: no address outside scores [0, total_cells), the outputs and the workspace is formed.
+ * Limits: nqd <= 64 as in ms_md_chain_scan; nhd <= MS_MD_BEST_MAX_HD.
+ * workspace: ms_md_best_mappings_workspace_bytes(ncand, total_cells) bytes (0 for a negative argument; never 0 otherwise),
+ * 16-byte aligned: kind 1's table D, one int64 per cell at the matrix's offset.  Every cell read was written by the same
+ * call: a workspace serves the next call without clean-up.  (Matrices that overlap share their D cells: lay them out apart.)
+ * ncand == 0 succeeds without a launch.  MS_ERR_ARG: NULL pointers, negative counts, a workspace that is not 16-byte
+ * aligned; MS_ERR_WORKSPACE: a workspace below the size the function reports.
+ * Asynchronous on `stream`, never allocates.  One wave per candidate; vector stores only, no atomics, no scratch memory.
+ * Backward compatible additions: ms_version() stays 210. */
+#define MS_MD_BEST_MAX_HD 1024
+size_t ms_md_best_mappings_workspace_bytes(int ncand, int64_t total_cells);
+int ms_md_best_mappings(const float *scores, int64_t total_cells, const int32_t *cand, int ncand, const int64_t *mat_off,
+                        int32_t *out_status, int64_t *out_total, int32_t *out_path, float *out_cell, void *workspace,
+                        size_t workspace_bytes, ms_stream_t stream);
+
 /* ------------------------------------------------------------------ encoder --------- */
 
 /* Floats in the canonical weight blob of the whole encoder (2 EGNN layers, state_dict order:

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ms_md_chain_scan_mq_workspace_bytes": (_sz, [_i64, _int]),
     "ms_md_chain_scan_mq": (_int, [_vp, _i64, _vp, _i64, _vp, _int, _int, _vp, _vp, _f, _vp, _int, _f, _vp, _i64, _vp, _vp, _f, _vp, _vp, _sz,
                                    _vp]),
+    "ms_md_best_mappings_workspace_bytes": (_sz, [_int, _i64]),
+    "ms_md_best_mappings": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ms_egnn_weight_floats": (_sz, []),
     "ms_egnn_prepared_bytes": (_sz, []),
     "ms_egnn_prepare_weights": (_int, [_vp, _vp, _vp]),

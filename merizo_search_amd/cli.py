@@ -19,6 +19,10 @@ scores those pairs with the search's own embedding score on the GPU and needs ne
 `database_cosine` (search and easy-search) gives exhaustive_cosine's answer for the WHOLE database -- every target chain, not only
 the chains the top-k lists name -- from one more pass over the rows on the GPU: it needs no aligner and does not depend on -k.
 
+`--multi_domain_report best` (all four commands; the two embedding-score modes) writes per (query chain, hit chain) pair the best
+any-order mapping with its score and, when that one breaks the domain order, the best order-preserving one -- solved on the GPU
+(ms_md_best_mappings), pairs ranked per query chain, no pair skipped for having too many mappings; the default `all` lists every mapping.
+
 `db-search` has no counterpart in the reference: it searches the stored embeddings of one database against another (or
 against itself), in batches of thousands of queries, without parsing or embedding a structure (foldclass/dbquery.py).
 `chain-search` is `database_cosine` with a whole database as the query side: for every multi-domain chain of query_db (the runs of
@@ -59,6 +63,25 @@ def munge_tmp_with_uuid(tmp: str) -> str:
     return os.path.join(tmp, str(uuid.uuid4()))
 
 
+def _add_report_flag(p: argparse.ArgumentParser) -> None:
+    p.add_argument("--multi_domain_report", type=str, default="all", choices=["all", "best"],
+                   help="What <output>_search_multi_dom.tsv holds. 'all': every one-to-one mapping of a (query chain, hit chain) pair "
+                        "(pairs with more than a million candidate mappings are skipped). 'best': per pair the best any-order mapping "
+                        "with its score and, when that one breaks the domain order, the best order-preserving one -- solved on the GPU, "
+                        "no pair is skipped; needs one of the embedding-score modes (exhaustive_cosine, database_cosine).")
+
+
+def _check_report(args) -> None:
+    """A report the multi-domain mode cannot serve is refused here, before any work (no database is opened, no GPU call made)."""
+    if args.multi_domain_search:
+        from .foldclass.multidomain import check_report
+        try:
+            check_report(args.multi_domain_report, args.multi_domain_mode)
+        except ValueError as exc:
+            logging.error(str(exc))
+            sys.exit(1)
+
+
 def _add_search_flags(p: argparse.ArgumentParser, default_format: str) -> None:
     p.add_argument("-d", "--device", type=str, default="cuda", help="'cuda' / 'cuda:N' = the MI355X. 'cpu' is refused by this build.")
     p.add_argument("-k", "--topk", type=int, default=1, help="Max number of domain matches to return per query domain.")
@@ -85,6 +108,7 @@ def _add_search_flags(p: argparse.ArgumentParser, default_format: str) -> None:
                         "the search's own embedding score on the GPU instead (entries below --mincos count as no match); needs "
                         "no TM-align binary. 'database_cosine': exhaustive_cosine's scores and output for EVERY chain of the database, "
                         "found by one pass over all its rows on the GPU; needs no aligner and does not depend on -k.")
+    _add_report_flag(p)
     p.add_argument("--skip_tmalign", action="store_true", default=False,
                    help="Embedding-only search (automatic when no TM-align binary is found and --tmalign_backend is auto).")
     p.add_argument("--tmalign_backend", type=str, default="auto", choices=["auto", "hip"],
@@ -185,7 +209,8 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         skip_tmalign=skip, weights_path=args.weights, tmalign_backend=args.tmalign_backend)
     md_kwargs = dict(queries=inputs, db_name=args.db_name, tmp_root=tmp, device=args.device, fastmode=args.fastmode, threads=args.threads,
                      mintm=args.mintm, inputs_from_easy_search=inputs_are_ca, mode=args.multi_domain_mode, pdb_chain=pdb_chain,
-                     tmalign_backend=args.tmalign_backend, mincos=args.mincos, mincov=args.mincov, network=network)
+                     tmalign_backend=args.tmalign_backend, mincos=args.mincos, mincov=args.mincov, network=network,
+                     report=args.multi_domain_report)
     mda = None
     if database_md:     # every rank scans its shard of the database and takes part in the gather; the mode reads no search_results
         from .foldclass.multidomain import multi_domain_search
@@ -202,10 +227,10 @@ def _search_and_write(args, inputs, inputs_are_ca, pdb_chain, fields, tmp):
         # merizo.py:207-222 / :396-411.  `search`: the inputs are single-domain files of ONE chain (the reference
         # passes inputs_from_easy_search=True here, which fails on file names; its stated intent is one chain 'A').
         from .foldclass.multidomain import multi_domain_search
-        from .foldclass.results import write_all_dom_search_results
+        from .foldclass.results import multi_dom_writer
         if not database_md:
             mda = multi_domain_search(search_results=results, **md_kwargs)
-        write_all_dom_search_results(mda, multi_output, args.output_headers)
+        multi_dom_writer(args.multi_domain_report)(mda, multi_output, args.output_headers)
 
 
 def search(argv) -> None:
@@ -217,6 +242,7 @@ def search(argv) -> None:
     p.add_argument("tmp", type=str)
     _add_search_flags(p, SEARCH_FIELDS)
     args = p.parse_args(argv)
+    _check_report(args)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
     _log_command("search")
@@ -243,6 +269,7 @@ def easy_search(argv) -> None:
     p.add_argument("--segment_tsv", type=str, default=None, help="A reference `_segment.tsv` to take the choppings from.")
     _add_segmenter_flags(p)
     args = p.parse_args(argv)
+    _check_report(args)
     _warn_ignored_segmenter_flags(args)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
@@ -320,6 +347,7 @@ def db_search(argv) -> None:
     p.add_argument("--multi_domain_mode", type=str, default="exhaustive_cosine", choices=["exhaustive_cosine"],
                    help="The multi-domain search mode: every query domain against every domain of every hit chain, scored with "
                         "the search's own embedding score on the GPU (entries below --mincos count as no match).")
+    _add_report_flag(p)
     args = p.parse_args(argv)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
@@ -334,7 +362,7 @@ def db_search(argv) -> None:
                         exclude_same_chain=args.exclude_same_chain, format_list=fields,
                         header=args.output_headers, metadata_json=args.metadata_json,
                         report_insignificant_hits=args.report_insignificant_hits, multi_domain_search=args.multi_domain_search,
-                        multi_domain_mode=args.multi_domain_mode)
+                        multi_domain_mode=args.multi_domain_mode, multi_domain_report=args.multi_domain_report)
     logging.info(f"Finished db-search of {n} queries in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 
@@ -357,6 +385,7 @@ def chain_search_parser() -> argparse.ArgumentParser:
     p.add_argument("--exclude_same_chain", action="store_true", default=False,
                    help="query_db and target_db are the same database: a query chain is never its own match.")
     p.add_argument("--output_headers", action="store_true", default=False)
+    _add_report_flag(p)
     return p
 
 
@@ -370,7 +399,8 @@ def chain_search(argv) -> None:
     n = run_chain_search(query_db=args.query_db, db_name=args.target_db, output=args.output, tmp=tmp, device=args.device,
                          mincos=args.mincos, mincov=args.mincov, query_batchsize=args.query_batchsize,
                          search_batchsize=args.search_batchsize, query_rows=args.query_rows,
-                         exclude_same_chain=args.exclude_same_chain, output_headers=args.output_headers)
+                         exclude_same_chain=args.exclude_same_chain, output_headers=args.output_headers,
+                         report=args.multi_domain_report)
     logging.info(f"Finished chain-search of {n} query chains in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 

@@ -70,14 +70,15 @@ def drop_own_chain(pairs: np.ndarray, first_rows: Sequence[int], target_starts: 
 def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device="cuda", mincos: float = 0.5, mincov: float = 0.7,
                      query_batchsize: int = 4096, search_batchsize: int = 262144, query_rows: Optional[str] = None,
                      exclude_same_chain: bool = False, output_headers: bool = False, max_mapping_paths: Optional[int] = None,
-                     route: str = "auto", engine=None) -> int:
-    """-> the number of query chains served.  route: multidomain.database_candidates' ("auto": the matrix route from
+                     route: str = "auto", engine=None, report: str = "all") -> int:
+    """-> the number of query chains served.  report: 'all' = every mapping of a pair (capped by max_mapping_paths), 'best' = the
+    best one(s) per pair with their score (multidomain.best_lines; no cap).  route: multidomain.database_candidates' ("auto": the matrix route from
     ops.MD_SCAN_MATRIX_MIN_NQ query rows per batch on; the file does not depend on it).  Under a process group every rank calls it;
     rank 0 writes."""
     from . import dbsearch
     from . import multidomain as md
     from .dbquery import QueryDB, parse_row_slice, same_database
-    from .results import append_written, write_all_dom_search_results
+    from .results import append_written, multi_dom_writer
     from .target import Target, score_mode as target_score_mode
 
     if engine is None:
@@ -87,6 +88,9 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
         dbsearch._refuse("--mincov must lie in [0, 1], got %r." % (mincov,))
     if query_batchsize < 1 or search_batchsize < 1:
         dbsearch._refuse("--query_batchsize and --search_batchsize must be >= 1.")
+    if report not in md.REPORTS:
+        dbsearch._refuse("--multi_domain_report must be one of %s, got %r." % (", ".join(md.REPORTS), report))
+    write_multi_dom = multi_dom_writer(report)
     same = same_database(query_db, db_name)
     if exclude_same_chain and not same:
         dbsearch._refuse("--exclude_same_chain removes the query chain itself from its candidates: it needs the query database and "
@@ -149,12 +153,12 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
             served = [qc for _a, _b, qc in batch]
             plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader.store)
             results = md.score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
-                                     max_mapping_paths=max_paths)
-            append_written(multi_output, part, lambda f: write_all_dom_search_results(results, f, output_headers and number == 0))
+                                     max_mapping_paths=max_paths, report=report)
+            append_written(multi_output, part, lambda f: write_multi_dom(results, f, output_headers and number == 0))
             logger.info("chain-search: batch %d of %d done (%d query chains, %d candidate pairs)"
                         % (number + 1, len(batches), len(batch), len(pairs)))
         if rank == 0 and output_headers and not batches:
-            write_all_dom_search_results([], multi_output, True)
+            write_multi_dom([], multi_output, True)
     finally:
         if reader is not qdb:
             reader.close()

@@ -573,12 +573,12 @@ class _ChainStep:
     holds all rows (one rank, not streamed), else the needed chain runs read from the database files (rank 0)."""
 
     def __init__(self, qdb, q_lo: int, q_hi: int, target: Target, db_name: str, same: bool, exclude_self: bool,
-                 mincos: float, mincov: float, max_mapping_paths: int, times, timings):
+                 mincos: float, mincov: float, max_mapping_paths: int, times, timings, report: str = "all"):
         from . import multidomain as md
         from .dbquery import QueryDB
         self.md, self.qdb, self.q_lo, self.engine, self.target = md, qdb, q_lo, target.engine, target
         self.mincos, self.max_paths, self.times = float(mincos), int(max_mapping_paths), times
-        self.exclude_self = exclude_self
+        self.exclude_self, self.report = exclude_self, report
         chains = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
         self.chains = chains
         self.run_end = np.empty(q_hi - q_lo, np.int64)          # one past the last row (global) of each query row's run
@@ -640,7 +640,8 @@ class _ChainStep:
         target_rows = lambda rows: self.target.rows_for(rows, self.reader)
         res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader.store, target_rows, self.mincos,
                              qlen=qlen, mincov=self.mincov, own_rows=own or None,
-                             max_mapping_paths=self.max_paths, log=logger.debug, skipped=skipped, times=self.times)
+                             max_mapping_paths=self.max_paths, log=logger.debug, skipped=skipped, times=self.times,
+                             report=self.report)
         self.skipped.extend(skipped)
         if self.timings is not None:
             self.timings["md_candidates_skipped"] = len(self.skipped)
@@ -661,7 +662,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
                     exclude_same_chain: bool = False, format_list=None, header: bool = False, metadata_json: bool = False,
                     report_insignificant_hits: bool = False, engine=None, timings: Optional[dict] = None,
                     multi_domain_search: bool = False, multi_domain_mode: str = "exhaustive_cosine",
-                    max_mapping_paths: Optional[int] = None) -> int:
+                    max_mapping_paths: Optional[int] = None, multi_domain_report: str = "all") -> int:
     """Search the rows of database `query_db` (all, or the slice query_rows = 'LO:HI') against database `db_name` and write
     `<output>_search.tsv` (+ `_search_insignificant.tsv`), in query-row order: `search` with a database in the place of the
     PDB files.  No structure is parsed or embedded -- the stored embeddings are the queries (dbquery.QueryDB), so the
@@ -675,7 +676,8 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     multi_domain_search: also write `<output>_search_multi_dom.tsv`, the multi-domain search in mode `exhaustive_cosine` (the only
     one here; multidomain.cosine_step): the query chains are the runs of adjacent query rows with one chain id, the hits that
     seed the candidates are each batch's reported results, and with exclude_self a query chain is never its own candidate
-    (_ChainStep).  max_mapping_paths: multidomain.MAX_MAPPING_PATHS unless given.
+    (_ChainStep).  max_mapping_paths: multidomain.MAX_MAPPING_PATHS unless given.  multi_domain_report: 'all' = every mapping of a
+    pair, 'best' = the best one(s) per pair with their score (multidomain.best_lines; no path cap).
     Everything else -- thresholds, hit records, columns -- is the code of dbsearch / dbsearch_faiss.  Returns the number of
     queries searched.  `timings`: a dict that receives which path ran ('in_place': the queries were row ranges of the resident
     matrix; 'streamed': the target went through engine.device_blocks) and HIP-event totals of the scan calls and the drop step."""
@@ -683,7 +685,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     from types import SimpleNamespace
 
     from .dbquery import QueryDB, parse_row_slice, same_database
-    from .results import SEARCH_FIELDS, append_written, embedding_only_format, write_all_dom_search_results, write_search_results
+    from .results import SEARCH_FIELDS, append_written, embedding_only_format, multi_dom_writer, write_search_results
 
     t_start = time.perf_counter()
     if engine is None:
@@ -695,6 +697,9 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
     if multi_domain_search and multi_domain_mode != "exhaustive_cosine":
         _refuse("db-search --multi_domain_mode: only 'exhaustive_cosine' is available here, got %r." % (multi_domain_mode,))
+    if multi_domain_report not in ("all", "best"):
+        _refuse("--multi_domain_report must be 'all' or 'best', got %r." % (multi_domain_report,))
+    write_multi_dom = multi_dom_writer(multi_domain_report)
     exclude_self = exclude_self or exclude_same_chain
     same = same_database(query_db, db_name)
     if exclude_self and not same:
@@ -759,7 +764,8 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     if multi_domain_search and rank == 0:
         from .multidomain import MAX_MAPPING_PATHS
         chain_step = _ChainStep(qdb, q_lo, q_hi, target, db_name, same, exclude_self, mincos, mincov,
-                                MAX_MAPPING_PATHS if max_mapping_paths is None else max_mapping_paths, times, timings)
+                                MAX_MAPPING_PATHS if max_mapping_paths is None else max_mapping_paths, times, timings,
+                                report=multi_domain_report)
     md_all = {}
     tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
     t_loop = time.perf_counter()
@@ -798,7 +804,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
             append_written(out_path, part, lambda f: write_search_results(results=per_batch, output_file=f, format_list=fields, header=first))
         if chain_step is not None:
             lines = chain_step.batch(b0, b1, query_dicts, results)
-            append_written(multi_output, part, lambda f: write_all_dom_search_results(lines, f, first))
+            append_written(multi_output, part, lambda f: write_multi_dom(lines, f, first))
         if metadata_json:
             for out_path, per_batch in zip(written, (results, all_results)):
                 md_all.setdefault(out_path, []).extend(hit["metadata"] for per_query in per_batch for hit in per_query.values()

@@ -23,6 +23,8 @@ Engine interface (tensors are torch tensors on the engine's device):
                                                                the rows [lo[q], hi[q]) and without scores below min_score (db-search)
     md_chain_scores(db, q, mode, cand, trows, mat_off, min_score, lengths, qlen, mincov) -> (scores [total], match int32 [ncand,2]):
                                                                the multi-domain search's score matrices in the search's own arithmetic
+    md_best_mappings(scores, cand, mat_off)                 -> (status [ncand,2], total int64 [ncand,2], path [ncand,2,64], cell [ncand,2,64]):
+                                                               the best any-order / order-preserving mapping of each of those matrices
     md_chain_scan(db, chain_start, q, mode, qchain, min_score, lengths, qlen, mincov) -> (pairs int64 [m,2] sorted, qstatus int32 [nqc]),
                                                                numpy: the (query chain, target chain) pairs of ALL rows that pass the
                                                                mapping step's two early exits (mode `database_cosine`)
@@ -259,6 +261,12 @@ class HipEngine:
             out = (self.torch.empty((int(total),), dtype=self.torch.float32, device=self.device),
                    self.torch.empty((int(cand.shape[0]), 2), dtype=self.torch.int32, device=self.device))
         return ops.md_chain_scores(db, q, code, cand, trows, mat_off, min_score, lengths=lengths, qlen=qlen, mincov=mincov, out=out)
+
+    def md_best_mappings(self, scores, cand, mat_off):
+        """The best any-order and the best order-preserving mapping of every matrix md_chain_scores wrote (ms_md_best_mappings), on
+        its device buffers -> (status int32 [ncand,2], total int64 [ncand,2], path int32 [ncand,2,64], cell float32 [ncand,2,64]),
+        device tensors; status 1 = found, 0 = none exists, -1 = bad descriptor, -2 = more than 64 x ops.MD_BEST_MAX_HD domains."""
+        return self._ops.md_best_mappings(scores, cand, mat_off)
 
     def md_chain_scan(self, db, chain_start, q, mode: str, qchain, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
                       route: str = "lane", row_norm_bound=None, stats=None):

@@ -26,6 +26,9 @@ mode='database_cosine'  asks the same question of the WHOLE data
 name: ms_md_chain_scan reads every row once and reports every (query chain, target chain) pair that passes chain_mappings' two
 early exits (`database_candidates`; the target chains are the runs of adjacent rows with one chain id, `chain_runs`), and the
 second half of `cosine_step` (`score_plans`) turns those pairs into the same result tuples.  Its answer does not depend on -k.
+
+report='best' (both embedding-score modes) replaces step 4's enumeration: ms_md_best_mappings solves, on the device
+buffers ms_md_chain_scores wrote, the best any-order and the best order-preserving mapping of every pair (`best_lines`).
 """
 from __future__ import annotations
 
@@ -54,6 +57,11 @@ SCAN_MAX_DOMAINS = 64           # database_cosine: query domains per query chain
 # exhaustive_cosine: chain_mappings enumerates a Cartesian product; a (query chain, hit chain) pair with more paths than
 # this is skipped with a warning (at database scale one pair of 12-domain chains could run for hours)
 MAX_MAPPING_PATHS = 1_000_000
+# what `<output>_search_multi_dom.tsv` holds: 'all' = every valid mapping of a pair (chain_mappings' enumeration, capped by
+# MAX_MAPPING_PATHS); 'best' = per pair the best any-order mapping and, when that one breaks the order, the best order-preserving
+# one, solved on the GPU (ms_md_best_mappings) -- no cap; the embedding-score modes only
+REPORTS = ("all", "best")
+BEST_MAX_HIT_DOMAINS = 1024     # report 'best': target domains per chain ms_md_best_mappings serves (MS_MD_BEST_MAX_HD)
 
 _TWO_DIGITS = re.compile(r"[0-9]{2}$")
 _MERIZO_SUFFIX = re.compile(r"_merizo_[0-9]*$")
@@ -89,6 +97,30 @@ def chain_runs(names: Sequence[str]) -> np.ndarray:
     return np.asarray(starts + [len(names)], dtype=np.int64)
 
 
+def mapping_category(path: Sequence[int], nhd: int) -> int:
+    """The category of one one-to-one mapping (path[i] = the target domain of query domain i) onto a chain of nhd domains
+    (:140-160): 3 = same number of domains, same order; 2 = order kept, contiguous target domains; 1 = order kept with gaps;
+    0 = any order."""
+    nqd = len(path)
+    steps = np.diff(path)
+    if nqd > 1 and not (steps > 0).all():
+        return 0
+    if nqd == nhd:
+        return 3
+    if (steps == 1).all():
+        return 2
+    return 1
+
+
+def check_report(report: str, mode: str) -> None:
+    """Refuse a report / mode combination before any work is done."""
+    if report not in REPORTS:
+        raise ValueError("Unrecognised multi-domain report: %s (expected one of: %s)" % (report, ", ".join(REPORTS)))
+    if report == "best" and mode not in ("exhaustive_cosine", "database_cosine"):
+        raise ValueError("--multi_domain_report best is served by the multi-domain modes exhaustive_cosine and database_cosine "
+                         "(the embedding-score matrices on the GPU), not by %s" % mode)
+
+
 def chain_mappings(tm: np.ndarray, query_chain: str, hit_chain: str, query_domains: Sequence[str],
                    hit_domains: Sequence[dict]) -> List[tuple]:
     """All one-to-one assignments of a chain's query domains (rows of `tm`) to the domains of one
@@ -110,15 +142,7 @@ def chain_mappings(tm: np.ndarray, query_chain: str, hit_chain: str, query_domai
     for path in itertools.product(*choices):
         if len(set(path)) != nqd:                     # two query domains on the same target domain
             continue
-        steps = np.diff(path)
-        if nqd > 1 and not (steps > 0).all():
-            category = 0
-        elif nqd == nhd:
-            category = 3
-        elif (steps == 1).all():
-            category = 2
-        else:
-            category = 1
+        category = mapping_category(path, nhd)
         info = [FIELD_SEPARATOR.join([query_domains[q], hit_domains[c]["hd"], str(tm[q, c])]) for q, c in enumerate(path)]
         meta = [hit_domains[c]["hm"] for c in path]
         out.append((query_chain, nqd, hit_chain, nhd, category, FIELD_SET_SEPARATOR.join(info),
@@ -264,7 +288,7 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
                         threads: int = -1, mintm: float = 0.5, inputs_from_easy_search: bool = False,
                         mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto",
                         mincos: float = 0.5, mincov: float = 0.7, network=None, max_mapping_paths: int = MAX_MAPPING_PATHS,
-                        target_db: Optional[dict] = None, search_batchsize: int = 262144):
+                        target_db: Optional[dict] = None, search_batchsize: int = 262144, report: str = "all"):
     """The reference's multi_domain_search (:183-574): same arguments, same result tuples (feed
     them to results.write_all_dom_search_results).  `queries`: PDB file names (search) or domain
     dicts with 'coords', 'seq', 'name' (easy-search).  tmalign_backend: 'auto' = the TM-align binary (required),
@@ -276,15 +300,18 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
     one pass over all rows (ms_md_chain_scan); search_results is not read (the answer does not depend on -k).  target_db: the
     dict the search opened this database into (dbsearch.read_database) -- its resident rows are then scanned in place; without
     it, or when they did not fit, the rows are streamed from the files in blocks of search_batchsize.  Under a process group
-    EVERY rank must call it (each scans its shard); ranks other than 0 get None."""
+    EVERY rank must call it (each scans its shard); ranks other than 0 get None.
+    report='best' (the two embedding-score modes): per (query chain, hit chain) pair the best mapping instead of every mapping --
+    the eight-column tuples of best_lines, for results.write_best_dom_search_results; MAX_MAPPING_PATHS does not apply."""
     if mode not in MODES:
         raise ValueError("Unrecognised multi-domain search mode: " + mode)
+    check_report(report, mode)
     if mode == "database_cosine":
         return _multi_domain_embedding(queries, None, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
-                                       threads, max_mapping_paths, True, target_db, search_batchsize)
+                                       threads, max_mapping_paths, True, target_db, search_batchsize, report)
     if mode == "exhaustive_cosine":
         return _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov,
-                                       network, threads, max_mapping_paths, False, None, 0)
+                                       network, threads, max_mapping_paths, False, None, 0, report)
     check_backend(tmalign_backend, device)
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
@@ -432,17 +459,19 @@ def compact_target_rows(engine, reader, rows: np.ndarray):
 
 def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable,
                 mincos: float, qlen=None, mincov: float = 0.0, own_rows: Optional[dict] = None,
-                max_mapping_paths: int = MAX_MAPPING_PATHS, log=logger.info, skipped: Optional[list] = None, times=None) -> list:
+                max_mapping_paths: int = MAX_MAPPING_PATHS, log=logger.info, skipped: Optional[list] = None, times=None,
+                report: str = "all") -> list:
     """Steps 2-4 of `exhaustive_cosine` for the query chains of `hits` (group_hits' dictionary) -> result tuples.
     q_emb [nq,128] on the engine's device holds the query embeddings as the search took them, the domains of chain qc in
     rows [q_first[qc], q_first[qc] + nqd) in the order of hits[qc]; score_mode: 'ip' (raw queries, faiss layout), 'ip_prenorm'
     (stored faiss rows as queries) or 'cosine' (`.pt` layout, with qlen / mincov).  target_rows(sorted unique global rows) ->
     (matrix, lengths or None, local index per row).  ONE engine.md_chain_scores call scores every (query chain, hit chain)
     matrix; names and metadata are read for the pairs its match counts keep.  skipped: receives (qc, hc, paths) of the pairs
-    above max_mapping_paths; times: dbsearch._DeviceTimes, which then receives the span of the scoring call ('md_scores')."""
+    above max_mapping_paths; times: dbsearch._DeviceTimes, which then receives the span of the scoring call ('md_scores').
+    report: score_plans'."""
     plans = hit_chain_plans(hits, q_first, store, own_rows, log)
     return score_plans(plans, hits, q_emb, score_mode, engine, store, target_rows, mincos, qlen=qlen, mincov=mincov,
-                       max_mapping_paths=max_mapping_paths, skipped=skipped, times=times)
+                       max_mapping_paths=max_mapping_paths, skipped=skipped, times=times, report=report)
 
 
 def hit_chain_plans(hits, q_first: Dict[str, int], store: "_TargetStore", own_rows: Optional[dict] = None, log=logger.info) -> list:
@@ -461,10 +490,16 @@ def hit_chain_plans(hits, q_first: Dict[str, int], store: "_TargetStore", own_ro
 
 
 def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable, mincos: float, qlen=None,
-                mincov: float = 0.0, max_mapping_paths: int = MAX_MAPPING_PATHS, skipped: Optional[list] = None, times=None) -> list:
+                mincov: float = 0.0, max_mapping_paths: int = MAX_MAPPING_PATHS, skipped: Optional[list] = None, times=None,
+                report: str = "all") -> list:
     """cosine_step's second half: plans (qc, hc, q0, nqd, global rows) -> result tuples.  ONE engine.md_chain_scores call for all
     matrices, chain_mappings' two early exits from its match counts, the max_mapping_paths skip, names and metadata for the
-    pairs that remain, chain_mappings."""
+    pairs that remain, chain_mappings.
+    report='best': the matrices stay on the device and go straight into ONE engine.md_best_mappings call; status, total, path and
+    chosen cells come back, not the matrices, and best_lines forms the eight-column tuples.  No path cap applies; skipped receives
+    (qc, hc, -2) for a pair beyond that call's limits (more than BEST_MAX_HIT_DOMAINS target domains)."""
+    if report not in REPORTS:
+        raise ValueError("Unrecognised multi-domain report: %s" % (report,))
     if not plans:
         return []
     needed = np.unique(np.concatenate([p[4] for p in plans]))
@@ -484,6 +519,12 @@ def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStor
                                            lengths=lengths, qlen=qlen, mincov=float(mincov), total=m_off)
     if times is not None:
         times.add("md_scores", t0)
+    if report == "best":
+        t0 = times.mark() if times is not None else None
+        best = engine.md_best_mappings(scores, cand_d, off_d)
+        if times is not None:
+            times.add("md_best", t0)
+        return best_lines(plans, hits, store, *(t.cpu().numpy() for t in best), skipped=skipped)
     scores, match = scores.cpu().numpy(), match.cpu().numpy()
     results = []
     for c, (qc, hc, _q0, nqd, grows) in enumerate(plans):
@@ -504,6 +545,46 @@ def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStor
             hd, hm = store.name_meta(int(r))
             info.append({"hd": hd, "hc": hc, "hi": int(r), "hm": hm})
         results.extend(chain_mappings(tm, qc, hc, list(hits[qc].keys()), info))
+    return results
+
+
+def best_lines(plans, hits, store: "_TargetStore", status, total, path, cell, skipped: Optional[list] = None) -> list:
+    """Report 'best': md_best_mappings' outputs for `plans` -> tuples (query_chain, nqd, hit_chain, nhd, category, 'score',
+    'qd:hd:score,...', '[metadata,...]').  Per pair with an any-order mapping (kind-0 status 1) one line for it and, when its
+    category is 0 and an order-preserving mapping exists (kind-1 status 1), a second line for that one.  score: the float64 sum
+    of the path's cells in row order, '%.6f'.  Within a query chain the pairs are ordered by the kind-0 integer total,
+    descending, ties in plan order; query chains keep the order of `plans`.  Names and metadata are read for reported pairs only."""
+    chain_rank, order = {}, []
+    for c, (qc, hc, _q0, nqd, grows) in enumerate(plans):
+        chain_rank.setdefault(qc, len(chain_rank))
+        if status[c, 0] == -2:
+            logger.warning("multi-domain search: query chain %s x hit chain %s has %d x %d domains (the best-mapping step serves "
+                           "up to %d x %d): skipped" % (qc, hc, nqd, len(grows), SCAN_MAX_DOMAINS, BEST_MAX_HIT_DOMAINS))
+            if skipped is not None:
+                skipped.append((qc, hc, -2))
+        elif status[c, 0] < 0:
+            raise RuntimeError("multi-domain search: ms_md_best_mappings refused the descriptor of %s x %s" % (qc, hc))
+        elif status[c, 0] == 1:
+            order.append(c)
+    order.sort(key=lambda c: (chain_rank[plans[c][0]], -int(total[c, 0])))           # (stable: ties stay in plan order)
+    results = []
+    for c in order:
+        qc, hc, _q0, nqd, grows = plans[c]
+        qds = list(hits[qc].keys())
+        info = {}
+        kinds = [0]
+        if mapping_category(path[c, 0, :nqd], len(grows)) == 0 and status[c, 1] == 1:
+            kinds.append(1)
+        for kind in kinds:
+            cols = [int(j) for j in path[c, kind, :nqd]]
+            for j in cols:
+                if j not in info:
+                    info[j] = store.name_meta(int(grows[j]))
+            cells = cell[c, kind, :nqd]
+            score = float(np.sum(cells.astype(np.float64)))
+            fields = [FIELD_SEPARATOR.join([qds[i], info[j][0], str(cells[i])]) for i, j in enumerate(cols)]
+            results.append((qc, nqd, hc, len(grows), mapping_category(cols, len(grows)), "%.6f" % score,
+                            FIELD_SET_SEPARATOR.join(fields), "[" + FIELD_SET_SEPARATOR.join(info[j][1] for j in cols) + "]"))
     return results
 
 
@@ -586,7 +667,7 @@ def candidate_plans(pairs: np.ndarray, served: Sequence[str], hits, q_first: Dic
 
 
 def _multi_domain_embedding(queries, search_results, db_name, device, inputs_from_easy_search, pdb_chain, mincos, mincov, network,
-                            threads, max_mapping_paths, whole_database: bool, target_db, search_batchsize):
+                            threads, max_mapping_paths, whole_database: bool, target_db, search_batchsize, report: str = "all"):
     """Both embedding-score modes.  whole_database (`database_cosine`): the candidates are every (query chain, target chain) pair
     of the database that passes the two early exits (database_candidates: EVERY rank of a process group scans its rows and
     takes part in the gather; rank 0 alone goes on to the scoring half and returns results, the others return None); else
@@ -620,7 +701,7 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
         target_rows = lambda rows: compact_target_rows(engine, reader, rows)
         if not whole_database:
             return cosine_step(hits, q_first, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
-                               max_mapping_paths=max_mapping_paths)
+                               max_mapping_paths=max_mapping_paths, report=report)
         served = []
         for qc, domains in hits.items():
             if len(domains) < 2:
@@ -640,6 +721,6 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
             return None
         plans = candidate_plans(pairs, served, hits, q_first, starts, reader.store)
         return score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
-                           max_mapping_paths=max_mapping_paths)
+                           max_mapping_paths=max_mapping_paths, report=report)
     finally:
         reader.close()

@@ -142,6 +142,23 @@ def write_all_dom_search_results(results, output_file: str, header: bool) -> Non
             out.write("\t".join(str(a) for a in res) + "\n")
 
 
+def write_best_dom_search_results(results, output_file: str, header: bool) -> None:
+    """`--multi_domain_report best`: multidomain.best_lines' eight-column tuples (match_score between the category and the
+    mapping), one or two lines per (query chain, hit chain) pair."""
+    if results is None:
+        return
+    with open(output_file, "w+") as out:
+        if header:
+            out.write("query_chain\tnqd\thit_chain\tnhd\tmatch_category\tmatch_score\tmatch_info\thit_metadata\n")
+        for res in results:
+            out.write("\t".join(str(a) for a in res) + "\n")
+
+
+def multi_dom_writer(report: str):
+    """The writer of `<output>_search_multi_dom.tsv` for a multi-domain report ('all' or 'best')."""
+    return write_best_dom_search_results if report == "best" else write_all_dom_search_results
+
+
 def append_written(path: str, part: str, write) -> None:
     """One batch's rows behind what `path` holds already: write(part) writes the part file with a writer of this module,
     its bytes are appended to `path`, the part file is removed."""

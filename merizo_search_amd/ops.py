@@ -558,6 +558,59 @@ def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, le
     return scores, match
 
 
+MD_BEST_MAX_QD, MD_BEST_MAX_HD = 64, 1024      # ms_md_best_mappings' limits (include/merizo_search_amd.h: 64, MS_MD_BEST_MAX_HD)
+
+
+def md_best_mappings(scores, cand, mat_off, out=None, workspace=None):
+    """The best any-order and the best order-preserving mapping of every candidate matrix (ms_md_best_mappings: the definition
+    is the header's).  scores float32 [total_cells]: the CUDA/HIP tensor md_chain_scores returned; cand int32 [ncand,4] and
+    mat_off int64 [ncand] as that call took them: tensors, or host arrays that are uploaded.
+    -> (status int32 [ncand,2], total int64 [ncand,2], path int32 [ncand,2,64], cell float32 [ncand,2,64]) on the device, every
+    entry written.  Asynchronous.  out: optional preallocated (status, total, path, cell); workspace: optional uint8 tensor of
+    ms_md_best_mappings_workspace_bytes(ncand, total_cells) bytes, reusable as it is."""
+    torch = _lib.require_gpu()
+    _f32_cuda(scores, "scores")
+    if scores.dim() != 1:
+        raise MerizoHipError(f"md_best_mappings: scores: expected float32 [total_cells], got shape {tuple(scores.shape)}")
+
+    def dev(x, dtype, name, cols=None):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
+        if t.is_floating_point():
+            raise MerizoHipError(f"md_best_mappings: {name}: expected integers, got {t.dtype}")
+        t = t.to(device=scores.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+        if (cols is None and t.dim() != 1) or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
+            raise MerizoHipError(f"md_best_mappings: {name}: unexpected shape {tuple(t.shape)}")
+        return t
+
+    cand_t, off_t = dev(cand, np.int32, "cand", 4), dev(mat_off, np.int64, "mat_off")
+    ncand, total_cells = cand_t.shape[0], int(scores.numel())
+    if off_t.numel() != ncand:
+        raise MerizoHipError(f"md_best_mappings: mat_off: expected {ncand} entries, got {off_t.numel()}")
+    shapes = ((torch.int32, (ncand, 2)), (torch.int64, (ncand, 2)), (torch.int32, (ncand, 2, MD_BEST_MAX_QD)),
+              (torch.float32, (ncand, 2, MD_BEST_MAX_QD)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtype, device=scores.device) for dtype, shape in shapes)
+    elif len(out) != 4 or any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape
+                              or not t.is_contiguous() for t, (dtype, shape) in zip(out, shapes)):
+        raise MerizoHipError("md_best_mappings: out must be contiguous CUDA tensors (int32 [ncand,2], int64 [ncand,2], "
+                             "int32 [ncand,2,64], float32 [ncand,2,64])")
+    status, total, path, cell = out
+    if ncand == 0:                      # (nothing to solve: the library would not launch either)
+        return status, total, path, cell
+    lib = _lib.load()
+    need = int(lib.ms_md_best_mappings_workspace_bytes(ncand, total_cells))
+    if need == 0:
+        raise MerizoHipError(f"ms_md_best_mappings_workspace_bytes rejected ncand={ncand} total_cells={total_cells}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=scores.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise MerizoHipError("md_best_mappings: workspace must be a contiguous uint8 tensor")
+    with _on(scores, cand_t, off_t, status, total, path, cell, workspace) as d:
+        check(lib.ms_md_best_mappings(ptr(scores), total_cells, ptr(cand_t), ncand, ptr(off_t), ptr(status), ptr(total), ptr(path),
+                                      ptr(cell), ptr(workspace), workspace.numel(), d.stream), "ms_md_best_mappings")
+    return status, total, path, cell
+
+
 # Query rows from which md_chain_scan's route "auto" takes the matrix route: the smallest nq of tools/chain_search_bench.py's sweep from
 # which ms_md_chain_scan_mq is faster than ms_md_chain_scan on both of its shapes (profiles/chain_search_bench.log).
 MD_SCAN_MATRIX_MIN_NQ = 64

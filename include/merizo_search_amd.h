@@ -284,6 +284,21 @@ int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n,
                       int64_t *out_n_reps, int32_t *out_rounds, int64_t *out_saturated,
                       void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* ms_cluster_greedy over the UNION of the lists' entries and m extra directed entries edge_src[e] -> edge_dst[e] with score
+ * edge_score[e] (int64 [m], int64 [m], float32 [m], device): what `cluster --complete` runs on the lists plus the output of
+ * ms_threshold_edges.  An extra entry is valid under the rule above with i = edge_src[e]; an edge_src outside [0, n) makes it
+ * invalid, and such a row is never dereferenced (nor is an edge_dst outside [0, n)).  Duplicates -- of list entries or of each
+ * other -- change nothing: the weight of i ~ j is the larger of the directed scores.  Every output is defined as above on that
+ * union; the same entries split in any way between lists and extras give identical outputs, *out_rounds included.
+ * k == 0 with NULL lists is allowed (extra entries only), m == 0 with NULL edge arrays is allowed.  *out_saturated counts over
+ * the lists only (0 when k == 0).  The workspace is ms_cluster_workspace_bytes(n), unchanged.
+ * ms_cluster_greedy is this call with m == 0.  MS_ERR_ARG: k < 0, m < 0, a NULL pointer that the counts make necessary, and
+ * what ms_cluster_greedy refuses.  Synchronises like ms_cluster_greedy.  Backward compatible addition: ms_version() stays 210. */
+int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                            const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
+                            float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps, int32_t *out_rounds,
+                            int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
 /* The score matrices of the multi-domain search's `exhaustive_cosine` mode: step 3 of dbsearch_fulllength.py (:468-483) with
  * the search's own score in place of TM-align -- the "embscore mode" that file leaves as a TODO (:202-203, :558-571).
  * Candidate c = cand[c] = {q0, nqd, t_off, nhd} is one (query chain, target chain) pair: its query domains are rows
@@ -371,6 +386,36 @@ int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *chain_start, 
                         const float *lengths, const float *qlen, float mincov, const int32_t *qchain, int nqc, float min_score,
                         int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, float row_norm_bound,
                         int64_t *out_stats, void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
+/* Every (query, row) cell of db [n,128] x q [nq,128] whose score is at or above a fixed threshold, as a list: the range search
+ * behind `cluster --complete` (the rows whose neighbour lists came back full get ALL their neighbours from it).
+ *   Cell (qi, r), qi in [0, nq), r in [0, n), has score s = EXACTLY the score ms_ip_topk reports for that query and row in
+ *        `mode` (MS_MODE_IP_PRENORM, MS_MODE_IP_NORMQ or MS_MODE_COSINE_UNIT with no length mask; others: MS_ERR_ARG): the
+ *        queries prepared by the scan's own preparation launch into the workspace, the dot the chain of 128 fmaf that
+ *        ms_md_chain_scores documents (s = 0..63: element s, then element 64 + s).
+ *   The cell is EMITTED iff s >= min_score and the global row row_offset + r lies outside [lo[qi], hi[qi]).  NaN is never
+ *        emitted; -inf as min_score cuts nothing.  lo / hi: int64 [nq], device, they go together; NULL NULL = nothing excluded.
+ *        An emitted cell writes out_src = qi, out_dst = row_offset + r, out_score = s as computed (-0.0 stays -0.0).
+ *   *out_count (int64, device) = the number of emitted cells, exact even when it exceeds cap; the first min(count, cap) slots
+ *        of out_src / out_dst / out_score (int64, int64, float32 [cap], device) hold distinct emitted cells in unspecified
+ *        order; nothing is written at or behind slot cap; cap == 0 only counts (the three arrays may then be NULL).
+ *   row_norm_bound, out_stats: as in ms_md_chain_scan_mq -- the fp16 matrix pipe proves a cell below min_score when its
+ *        approximate score is below min_score - E * row_norm_bound * |q|, every other cell is computed exactly.  The bound need
+ *        not hold: a row above it, or a query the filter cannot serve, has all its cells scored exactly.  out_stats[0] = the
+ *        number of cells sent to the exact chain (NULL: not reported).
+ * n == 0 succeeds with *out_count = 0.  Error codes as ms_md_chain_scan_mq's, in its order: MS_ERR_ARG for another mode, nq < 1,
+ * n < 0, cap < 0, NULL pointers, only one of lo / hi, a NaN min_score, db or workspace not 16-byte aligned; MS_ERR_RANGE for a
+ * row_norm_bound that is NaN, <= 0 or outside [2^-40, 2^40] and for n >= 2^31; MS_ERR_WORKSPACE below
+ * ms_threshold_edges_workspace_bytes(n, nq) bytes (0 for nq < 1 or n < 0).
+ * Asynchronous on `stream`, never allocates; the slot counter lives in the workspace and is reset by the call: the workspace
+ * serves the next call without clean-up.  Vector stores and vector atomics only (one global atomic per wave and drain of its
+ * list of unproved cells, one per wave for out_stats); no scratch memory.  One route serves any nq >= 1 (padded to the 32-query
+ * tile; the results do not depend on it).  Backward compatible additions: ms_version() stays 210. */
+size_t ms_threshold_edges_workspace_bytes(int64_t n, int nq);
+int ms_threshold_edges(const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int mode, const int64_t *lo,
+                       const int64_t *hi, float min_score, float row_norm_bound, int64_t *out_src, int64_t *out_dst,
+                       float *out_score, int64_t cap, int64_t *out_count, int64_t *out_stats, void *workspace,
+                       size_t workspace_bytes, ms_stream_t stream);
 
 /* The best mapping of every (query chain, target chain) candidate: the step behind ms_md_chain_scores, on its buffers.
  * Candidate c has a matrix M [nqd,nhd], row-major, at scores + mat_off[c] (scores float32 [total_cells]) -- what

@@ -79,6 +79,9 @@ SIGNATURES = {
     "ms_topk_drop_ranges": (_int, [_vp, _vp, _int, _int, _vp, _vp, _f, _int, _vp, _vp, _vp, _vp]),
     "ms_cluster_workspace_bytes": (_sz, [_i64]),
     "ms_cluster_greedy": (_int, [_vp, _vp, _i64, _int, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ms_cluster_greedy_edges": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ms_threshold_edges_workspace_bytes": (_sz, [_i64, _int]),
+    "ms_threshold_edges": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ms_md_chain_scores_workspace_bytes": (_sz, [_int]),
     "ms_md_chain_scores": (_int, [_vp, _i64, _vp, _int, _int, _vp, _vp, _f, _vp, _int, _vp, _i64, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
     "ms_md_chain_scan_workspace_bytes": (_sz, [_i64, _int]),

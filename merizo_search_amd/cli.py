@@ -420,6 +420,11 @@ def cluster(argv) -> None:
     p.add_argument("--query_batchsize", type=int, default=4096, help="Rows per scan call.")
     p.add_argument("--search_batchsize", type=int, default=262144, help="Target rows per block when the database is streamed.")
     p.add_argument("--output_headers", action="store_true", default=False)
+    p.add_argument("--complete", action="store_true", default=False,
+                   help="Cluster the full threshold graph, whatever -k: domains whose -k neighbours all reach --mincos get ALL their "
+                        "neighbours from one more pass over the database.")
+    p.add_argument("--max_edges", type=int, default=2 ** 27,
+                   help="--complete: directed neighbour entries that pass may hold (20 bytes of device memory each); beyond it the run is refused.")
     args = p.parse_args(argv)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
@@ -428,7 +433,7 @@ def cluster(argv) -> None:
     t0 = time.time()
     run_cluster(db_name=args.db_name, output=args.output, tmp=tmp, device=args.device, topk=args.topk, mincos=args.mincos,
                 mincov=args.mincov, query_batchsize=args.query_batchsize, search_batchsize=args.search_batchsize,
-                header=args.output_headers)
+                header=args.output_headers, complete=args.complete, max_edges=args.max_edges)
     logging.info(f"Finished cluster in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 

@@ -17,6 +17,9 @@
 // representative reads its list once more, the round after it was chosen, to cover its neighbours).
 // Assignment runs once on the final set: 64-bit atomicMax on {order-preserving score bits, ~row}, pushed and pulled in the
 // same way, so the result depends on the set alone.  Vector stores and vector atomics only; no LDS, no scratch.
+// ms_cluster_greedy_edges adds m directed entries held as three arrays (row i, row j, score) to the lists: the mark and the
+// assign step get a second launch over them, with i read instead of derived from the entry's place; ms_cluster_greedy is that
+// call with m == 0 -- the launches it always made, in their order.
 #include "ms_common.h"
 
 #define MS_CL_THREADS 256
@@ -90,6 +93,28 @@ __device__ __forceinline__ int64_t ms_cl_entry_row(int64_t base, int k) {
     return row0 + (int64_t)(local / (uint32_t)k);
 }
 
+// The mark step of ONE directed entry i -> j with score s (i inside [0, n)): what the header comment calls push, pull and cover.
+__device__ __forceinline__ void ms_cl_mark_entry(int64_t i, const int64_t *__restrict__ jp, const float *__restrict__ sp, int64_t n,
+                                                 const int32_t *__restrict__ lengths, float min_score, float mincov,
+                                                 const uint8_t *__restrict__ status, uint8_t *blocked, uint8_t *covered) {
+    const uint8_t st = status[i];
+    if (st != MS_CL_UNDECIDED && st != MS_CL_REP_NEW) return;              // decided rows have nothing left to say
+    const int64_t j = *jp;
+    const float s = *sp;
+    const int32_t li = lengths[i];
+    int32_t lj;
+    if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) return;
+    if (st == MS_CL_REP_NEW) { covered[j] = 1; return; }
+    const uint8_t sj = status[j];
+    if (ms_cl_before(li, i, lj, j)) {
+        if (sj == MS_CL_UNDECIDED) blocked[j] = 1;                         // push: j must wait for i
+    } else if (sj == MS_CL_UNDECIDED) {
+        blocked[i] = 1;                                                    // pull: i must wait for j
+    } else if (ms_cl_is_rep(sj)) {
+        covered[i] = 1;
+    }
+}
+
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_kernel(
         const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
         const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
@@ -99,23 +124,25 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_kernel(
     MS_CL_FOR_ENTRIES(total) {
         const int64_t i = ms_cl_entry_row(base, k);
         if (i >= n) continue;
-        const uint8_t st = status[i];
-        if (st != MS_CL_UNDECIDED && st != MS_CL_REP_NEW) continue;        // decided rows have nothing left to say
         const int64_t e = base + threadIdx.x;
-        const int64_t j = nbr_idx[e];
-        const float s = nbr_score[e];
-        const int32_t li = lengths[i];
-        int32_t lj;
-        if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) continue;
-        if (st == MS_CL_REP_NEW) { covered[j] = 1; continue; }
-        const uint8_t sj = status[j];
-        if (ms_cl_before(li, i, lj, j)) {
-            if (sj == MS_CL_UNDECIDED) blocked[j] = 1;                     // push: j must wait for i
-        } else if (sj == MS_CL_UNDECIDED) {
-            blocked[i] = 1;                                                // pull: i must wait for j
-        } else if (ms_cl_is_rep(sj)) {
-            covered[i] = 1;
-        }
+        ms_cl_mark_entry(i, nbr_idx + e, nbr_score + e, n, lengths, min_score, mincov, status, blocked, covered);
+    }
+}
+
+// The same step over the m extra entries edge_src[e] -> edge_dst[e]: i is READ, and an entry whose i lies outside [0, n) is skipped
+// before anything is looked up with it.  (Launched between a round's list launch and its decide launch; with k == 0 it is the
+// round's only mark launch, so it resets the count too: the same value, whichever launch stores it.)
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_edges_kernel(
+        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
+        uint8_t *blocked, uint8_t *covered, uint32_t *remaining_slot) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *remaining_slot = 0u;
+    MS_CL_FOR_ENTRIES(m) {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) continue;
+        const int64_t i = edge_src[e];
+        if (i < 0 || i >= n) continue;
+        ms_cl_mark_entry(i, edge_dst + e, edge_score + e, n, lengths, min_score, mincov, status, blocked, covered);
     }
 }
 
@@ -141,6 +168,19 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_decide_kernel(int64_
     }
 }
 
+// The assignment step of ONE directed entry i -> j (i inside [0, n)); false: the entry is not valid.
+__device__ __forceinline__ bool ms_cl_assign_entry(int64_t i, int64_t j, float s, int64_t n, const int32_t *__restrict__ lengths,
+                                                   float min_score, float mincov, const uint8_t *__restrict__ status,
+                                                   unsigned long long *best) {
+    const int32_t li = lengths[i];
+    int32_t lj;
+    if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) return false;
+    const bool rep_i = ms_cl_is_rep(status[i]), rep_j = ms_cl_is_rep(status[j]);
+    if (rep_j && !rep_i) atomicMax(best + i, ms_cl_key(s, j));             // pull
+    if (rep_i && !rep_j) atomicMax(best + j, ms_cl_key(s, i));             // push
+    return true;
+}
+
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_kernel(
         const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
         const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
@@ -150,14 +190,20 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_kernel(
         const int64_t i = ms_cl_entry_row(base, k);
         if (i >= n) continue;
         const int64_t e = base + threadIdx.x;
-        const int64_t j = nbr_idx[e];
-        const float s = nbr_score[e];
-        const int32_t li = lengths[i];
-        int32_t lj;
-        if (!ms_cl_valid(i, j, s, n, lengths, li, min_score, mincov, &lj)) { cut[i] = 1; continue; }
-        const bool rep_i = ms_cl_is_rep(status[i]), rep_j = ms_cl_is_rep(status[j]);
-        if (rep_j && !rep_i) atomicMax(best + i, ms_cl_key(s, j));         // pull
-        if (rep_i && !rep_j) atomicMax(best + j, ms_cl_key(s, i));         // push
+        if (!ms_cl_assign_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, status, best)) cut[i] = 1;
+    }
+}
+
+// (An extra entry that is not valid says nothing about a LIST: `cut`, and with it out_saturated, is the lists' alone.)
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_edges_kernel(
+        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status, unsigned long long *best) {
+    MS_CL_FOR_ENTRIES(m) {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) continue;
+        const int64_t i = edge_src[e];
+        if (i < 0 || i >= n) continue;
+        ms_cl_assign_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, status, best);
     }
 }
 
@@ -200,33 +246,34 @@ static inline unsigned ms_cl_blocks(int64_t items) {
     return (unsigned)(b < MS_CL_MAX_BLOCKS ? b : MS_CL_MAX_BLOCKS);
 }
 
-extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int32_t *lengths,
-                                 float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
-                                 int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
-                                 ms_stream_t stream) {
-    if (!nbr_idx || !nbr_score || !lengths || !out_rep || !out_rep_score || !out_n_reps || !out_rounds || !out_saturated || !workspace)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: NULL pointer");
-    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
-    if (k < 1) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need k >= 1 (k=%d)", k);
-    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: min_score is NaN (-inf: no cut)");
-    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: mincov must lie in [0, 1]");
+// Both entry points: the lists ([n,k], k >= 0) and the extra entries (m >= 0), `who` in the messages.
+static int ms_cl_run(const char *who, const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                     const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score, float mincov,
+                     int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps, int32_t *out_rounds, int64_t *out_saturated,
+                     void *workspace, size_t workspace_bytes, ms_stream_t stream) {
     const size_t need = ms_cluster_workspace_bytes(n);
     if (workspace_bytes < need)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: workspace of %zu bytes, ms_cluster_workspace_bytes(%lld) = %zu", workspace_bytes,
-                (long long)n, need);
-    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: workspace must be 16-byte aligned");
+        MS_FAIL(MS_ERR_ARG, "%s: workspace of %zu bytes, ms_cluster_workspace_bytes(%lld) = %zu", who, workspace_bytes, (long long)n, need);
+    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
 
     hipStream_t st = (hipStream_t)stream;
     const ms_cl_view v = ms_cl_carve(workspace, n);
-    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), row_blocks = ms_cl_blocks(n);
+    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), edge_blocks = ms_cl_blocks(m), row_blocks = ms_cl_blocks(n);
     MS_HIP_CHECK(hipMemsetAsync(workspace, 0, need, st));                  // every row undecided, no flag, no key, counters 0
 
     int64_t rounds = 0;
     for (bool done = false; !done;) {
         for (int g = 0; g < MS_CL_GROUP; ++g) {
-            hipLaunchKernelGGL(ms_cluster_mark_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
-                               min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
-            MS_LAUNCH_CHECK("ms_cluster_mark_kernel");
+            if (k > 0) {
+                hipLaunchKernelGGL(ms_cluster_mark_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
+                                   min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
+                MS_LAUNCH_CHECK("ms_cluster_mark_kernel");
+            }
+            if (m > 0 || k == 0) {                                         // (k == 0 and m == 0: one workgroup that resets the count)
+                hipLaunchKernelGGL(ms_cluster_mark_edges_kernel, dim3(m > 0 ? edge_blocks : 1u), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst,
+                                   edge_score, m, n, lengths, min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
+                MS_LAUNCH_CHECK("ms_cluster_mark_edges_kernel");
+            }
             hipLaunchKernelGGL(ms_cluster_decide_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.blocked, v.covered,
                                v.head->remaining + g);
             MS_LAUNCH_CHECK("ms_cluster_decide_kernel");
@@ -239,13 +286,20 @@ extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score,
             done = remaining[g] == 0u;                                     // (the rounds behind it in the group changed nothing)
         }
         if (!done && rounds > n)                                           // every round decides a row: unreachable on sound memory
-            MS_FAIL(MS_ERR_HIP, "ms_cluster_greedy: %lld rows still undecided after %lld rounds", (long long)remaining[MS_CL_GROUP - 1],
+            MS_FAIL(MS_ERR_HIP, "%s: %lld rows still undecided after %lld rounds", who, (long long)remaining[MS_CL_GROUP - 1],
                     (long long)rounds);
     }
 
-    hipLaunchKernelGGL(ms_cluster_assign_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
-                       min_score, mincov, v.status, v.best, v.cut);
-    MS_LAUNCH_CHECK("ms_cluster_assign_kernel");
+    if (k > 0) {
+        hipLaunchKernelGGL(ms_cluster_assign_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
+                           min_score, mincov, v.status, v.best, v.cut);
+        MS_LAUNCH_CHECK("ms_cluster_assign_kernel");
+    }
+    if (m > 0) {
+        hipLaunchKernelGGL(ms_cluster_assign_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score, m, n,
+                           lengths, min_score, mincov, v.status, v.best);
+        MS_LAUNCH_CHECK("ms_cluster_assign_edges_kernel");
+    }
     hipLaunchKernelGGL(ms_cluster_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.best, v.cut, out_rep,
                        out_rep_score, v.head);
     MS_LAUNCH_CHECK("ms_cluster_finish_kernel");
@@ -253,7 +307,37 @@ extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score,
     MS_HIP_CHECK(hipMemcpyAsync(&head, v.head, sizeof(head), hipMemcpyDeviceToHost, st));
     MS_HIP_CHECK(hipStreamSynchronize(st));
     *out_n_reps = (int64_t)head.n_reps;
-    *out_saturated = (int64_t)head.saturated;
+    *out_saturated = k > 0 ? (int64_t)head.saturated : 0;                  // (no list, no full list)
     *out_rounds = (int32_t)rounds;
     return MS_OK;
+}
+
+extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int32_t *lengths,
+                                 float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
+                                 int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
+                                 ms_stream_t stream) {
+    if (!nbr_idx || !nbr_score || !lengths || !out_rep || !out_rep_score || !out_n_reps || !out_rounds || !out_saturated || !workspace)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: NULL pointer");
+    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
+    if (k < 1) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need k >= 1 (k=%d)", k);
+    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: min_score is NaN (-inf: no cut)");
+    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: mincov must lie in [0, 1]");
+    return ms_cl_run("ms_cluster_greedy", nbr_idx, nbr_score, n, k, nullptr, nullptr, nullptr, 0, lengths, min_score, mincov, out_rep,
+                     out_rep_score, out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                                       const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths,
+                                       float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
+                                       int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
+                                       ms_stream_t stream) {
+    if (k < 0 || m < 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: need k >= 0 and m >= 0 (k=%d m=%lld)", k, (long long)m);
+    if ((k > 0 && (!nbr_idx || !nbr_score)) || (m > 0 && (!edge_src || !edge_dst || !edge_score)) || !lengths || !out_rep || !out_rep_score ||
+        !out_n_reps || !out_rounds || !out_saturated || !workspace)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: NULL pointer");
+    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
+    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: min_score is NaN (-inf: no cut)");
+    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: mincov must lie in [0, 1]");
+    return ms_cl_run("ms_cluster_greedy_edges", nbr_idx, nbr_score, n, k, edge_src, edge_dst, edge_score, m, lengths, min_score, mincov,
+                     out_rep, out_rep_score, out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes, stream);
 }

@@ -5,6 +5,11 @@ ranks, the drop of the own row and of everything below --mincos) writes each bat
 [b0, b1) of two device tensors [n,k]; ms_cluster_greedy turns that graph into representatives and assignments.  The lists
 never reach the host.  Output `<output>_cluster.tsv`: representative, member, cosine -- one line per database row.
 
+`--complete` (run_cluster(complete=True)) makes the answer independent of -k: the rows whose lists came back FULL get all
+their neighbours at the threshold from one more pass (ms_threshold_edges: every cell of those rows against the whole database,
+decided against the fixed threshold), and ms_cluster_greedy_edges clusters the lists plus those entries -- the true threshold
+graph ("The complete graph").
+
 The clustering's definition is the header's (include/merizo_search_amd.h, ms_cluster_greedy): an edge needs a cosine at or
 above --mincos in either direction and the shorter domain to cover --mincov of the longer; the longer domain is the
 representative (cd-hit's greedy order), every other domain goes to its best-scoring adjacent representative.  Coverage is that
@@ -22,7 +27,7 @@ import numpy as np
 from . import dbsearch as ds
 from . import sharded
 from .dbsearch import _BatchScan, _DeviceTimes, _refuse, _require_database, read_database
-from .target import Target
+from .target import Target, score_mode
 
 logger = logging.getLogger(__name__)
 
@@ -48,15 +53,71 @@ def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, 
             handle.write("%s\t%s\t%s\n" % (names[int(rep[r])], names[int(r)], "{:.4f}".format(rep_score[r])))
 
 
+MAX_EDGES = 2 ** 27        # directed entries the edge pass of --complete may hold: a memory budget (20 B each: 2.7 GB), not a measurement
+
+
+def _edge_pass(engine, target: Target, qdb, in_place: bool, full_rows: np.ndarray, mincos: float, query_batchsize: int,
+               search_batchsize: int, edge_room: int, max_edges: int, times):
+    """Every neighbour at or above mincos of the rows `full_rows` (global, ascending) among THIS rank's rows of the database ->
+    (src, dst, score, found, rescored): directed entries src -> dst in global rows (device tensors of one length), the number
+    found -- larger than that length only when it exceeds max_edges: the scan then goes on counting without keeping -- and the
+    cells that went to the exact chain.  The queries are what the self-search used for those rows, in its mode; a query's own row
+    is excluded.  The buffer starts at min(max_edges, edge_room) entries and grows geometrically; a call whose exact count
+    exceeds the room left is repeated once after growing.  times: one 'edges' span per batch of query_batchsize full rows."""
+    torch = engine.torch
+    mode, _masked = score_mode(target.faiss, qdb.normalized)
+    bound = target.row_norm_bound if target.faiss else None             # (None: unit rows, the engine's default)
+    cap = max(1, min(int(max_edges), int(edge_room)))
+    buf = [torch.empty((cap,), dtype=dt, device=engine.device) for dt in (torch.int64, torch.int64, torch.float32)]
+    used = found = rescored = 0
+    for f0 in range(0, full_rows.shape[0], int(query_batchsize)):
+        t0 = times.mark()
+        rows = engine.to_device(full_rows[f0:f0 + int(query_batchsize)])
+        q = target.rows[rows] if in_place else engine.to_device(qdb.embeddings_of(full_rows[f0:f0 + int(query_batchsize)]))
+        for block, a, _lengths in target.blocks(qdb, search_batchsize):
+            stats = {}
+            scan = lambda keep: engine.threshold_edges(block, q, mode, mincos, lo=rows, hi=rows + 1, row_offset=a, row_norm_bound=bound,
+                                                       out=tuple(b[used:used + keep] for b in buf), stats=stats)
+            if found > max_edges:                                       # over the budget already: count on, keep nothing
+                found += scan(0)[3]
+                rescored += stats["rescored"]
+                continue
+            src, _dst, _score, count = scan(cap - used)
+            if used + count > max_edges:
+                found = used + count
+                rescored += stats["rescored"]
+                continue
+            if count > cap - used:
+                cap = min(int(max_edges), max(2 * cap, used + count))
+                grown = [torch.empty((cap,), dtype=b.dtype, device=engine.device) for b in buf]
+                for g, b in zip(grown, buf):
+                    g[:used] = b[:used]
+                buf = grown
+                src, _dst, _score, count = scan(cap - used)
+            rescored += stats["rescored"]
+            buf[0][used:used + count] = rows[src]                       # the query's number -> its global row
+            used += count
+            found = used
+        times.add("edges", t0)
+    return buf[0][:used], buf[1][:used], buf[2][:used], found, rescored
+
+
 def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 20, mincos: Optional[float] = None,
                 mincov: float = 0.7, query_batchsize: int = 4096, search_batchsize: int = 262144, header: bool = False,
-                engine=None, timings: Optional[dict] = None):
+                engine=None, timings: Optional[dict] = None, complete: bool = False, max_edges: int = MAX_EDGES,
+                edge_room: int = 2 ** 20):
     """Cluster the rows of database `db_name` and write `<output>_cluster.tsv`.  topk: neighbours kept per row (the search
     fetches topk + 1 and drops the row itself); a row whose topk entries all count as edges may have neighbours the clustering
     never sees (`saturated`: raise -k).  Under several ranks every rank scans its shard of the rows; rank 0 alone keeps the
     graph, clusters and writes.  -> (rep int64 [n], rep_score float32 [n], info) as numpy arrays on rank 0, (None, None, info)
-    elsewhere; info: n, n_reps, singletons, rounds, saturated.  `timings`: as run_dbsearch_db's, plus the HIP-event span of
-    ms_cluster_greedy ('cluster_ms')."""
+    elsewhere; info: n, n_reps, singletons, rounds, saturated, full_lists (rows whose list holds topk entries at or above
+    mincos, whether or not they pass mincov: the lists that may have been cut short).  `timings`: as run_dbsearch_db's, plus the
+    HIP-event span of ms_cluster_greedy ('cluster_ms').
+    complete: cluster the TRUE threshold graph, whatever topk -- the rows with a full list get all their neighbours from an
+    edge pass over this rank's rows (_edge_pass; gathered to rank 0 under several ranks) and ms_cluster_greedy_edges runs on the
+    lists plus those entries: the TSV a run at topk = n - 1 would write.  At most max_edges directed entries are held (beyond
+    that the run is refused and nothing is written); edge_room: the entries the buffer starts with.  info gains `complete`,
+    `edges` and `rescored`, timings 'edges_ms' (the edge pass: one span per batch of full rows, as 'scan_ms' has one per batch)."""
     from .dbquery import QueryDB
 
     if engine is None:
@@ -68,6 +129,8 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         _refuse("-c/--mincov must lie in [0, 1], got %r." % (mincov,))
     if topk < 1 or query_batchsize < 1 or search_batchsize < 1:
         _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
+    if int(max_edges) < 1 or int(edge_room) < 1:
+        _refuse("--max_edges must be >= 1, got %r." % (max_edges,))
     _require_database(db_name)
     target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
     qdb = QueryDB(db_name, loaded=target_db if not target_db["faiss"] else None)
@@ -88,27 +151,48 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     scan = _BatchScan(Target.of(target_db, engine, min(int(query_batchsize), n), k + 1), qdb, True, k + 1, search_batchsize, times)
     if timings is not None:
         timings["in_place"], timings["streamed"] = scan.in_place, scan.streamed
-    logger.info("cluster: %d rows of %s, %d neighbours per row at cosine >= %s, coverage >= %s, batches of %d%s"
+    logger.info("cluster: %d rows of %s, %d neighbours per row at cosine >= %s, coverage >= %s, batches of %d%s%s"
                 % (n, db_name, k, mincos, mincov, int(query_batchsize),
-                   "; queries read in place from the resident rows" if scan.in_place else ""))
+                   "; queries read in place from the resident rows" if scan.in_place else "",
+                   "; complete: rows with a full list get all their neighbours from an edge pass" if complete else ""))
     own = engine.to_device(np.arange(n + 1, dtype=np.int64))              # row q excludes [q, q + 1): slices of one array
     nbr_s = nbr_i = count = None
     if rank == 0:                                                         # the graph: rank 0's device, never the host
         nbr_s = torch.empty((n, k), dtype=torch.float32, device=engine.device)
         nbr_i = torch.empty((n, k), dtype=torch.int64, device=engine.device)
         count = torch.empty((n,), dtype=torch.int32, device=engine.device)
+    counts = []                                                           # every rank gets each batch's counts back from the drop step
     for b0 in range(0, n, int(query_batchsize)):
         b1 = min(n, b0 + int(query_batchsize))
         seqs = None if target_db["faiss"] else qdb.seqs(b0, b1)
         out = (nbr_s[b0:b1], nbr_i[b0:b1], count[b0:b1]) if rank == 0 else None
-        scan.search(b0, b1, seqs, 0.0, own[b0:b1], own[b0 + 1:b1 + 1], k, float(mincos), out=out)
-    info = {"n": n, "k": k}
+        counts.append(scan.search(b0, b1, seqs, 0.0, own[b0:b1], own[b0 + 1:b1 + 1], k, float(mincos), out=out)[2])
+    full_rows = np.nonzero(torch.cat(counts).cpu().numpy() == k)[0].astype(np.int64)      # the lists that k may have cut short
+    info = {"n": n, "k": k, "full_lists": int(full_rows.shape[0]), "complete": bool(complete)}
+    edges = None
+    if complete:
+        info.update(edges=0, rescored=0)
+    if complete and full_rows.shape[0] > 0:
+        src, dst, score, found, rescored = _edge_pass(engine, scan.target, qdb, scan.in_place, full_rows, float(mincos), query_batchsize,
+                                                      search_batchsize, edge_room, int(max_edges), times)
+        edges, info["edges"], info["rescored"] = sharded.gather_edges(src, dst, score, engine.device, total=found, rescored=rescored,
+                                                                      limit=int(max_edges))
+        if edges is None:                                                 # (every rank learns it from the same counts)
+            times.finish()
+            qdb.close()
+            _refuse("cluster --complete: the %d rows with a full list have %d neighbours at cosine >= %s, more than --max_edges %d "
+                    "directed entries. Raise -s/--mincos, or raise --max_edges (20 bytes of device memory per entry)."
+                    % (info["full_lists"], info["edges"], mincos, int(max_edges)))
     if rank != 0:
         times.finish()
         qdb.close()
         return None, None, info
     t0 = times.mark()
-    rep, rep_score, found = engine.cluster_greedy(nbr_i, nbr_s, lengths, float(mincos), float(mincov))
+    if complete:
+        e_src, e_dst, e_score = edges if edges is not None else (None, None, None)
+        rep, rep_score, found = engine.cluster_greedy_edges(nbr_i, nbr_s, e_src, e_dst, e_score, lengths, float(mincos), float(mincov))
+    else:
+        rep, rep_score, found = engine.cluster_greedy(nbr_i, nbr_s, lengths, float(mincos), float(mincov))
     times.add("cluster", t0)
     times.finish()
     rep, rep_score = rep.cpu().numpy(), rep_score.cpu().numpy()
@@ -118,7 +202,14 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     qdb.close()
     logger.info("cluster: %d clusters (%d singletons) of %d rows in %d rounds -> %s"
                 % (info["n_reps"], info["singletons"], n, info["rounds"], out_path))
+    if complete:
+        logger.info("cluster: complete: %d rows had a full list of %d; the edge pass added %d directed entries (%d cells re-scored "
+                    "exactly): the clustering is that of the full threshold graph" % (info["full_lists"], k, info["edges"], info["rescored"]))
+        return rep, rep_score, info
     if info["saturated"] > 0:
         logger.warning("cluster: %d rows have all %d kept neighbours above the thresholds: their lists may have been cut short "
                        "and neighbours beyond them are unknown to the clustering. Raise -k." % (info["saturated"], k))
+    if info["full_lists"] > info["saturated"]:
+        logger.warning("cluster: %d lists are full when the entries that fail --mincov are counted too: such a list may have been cut "
+                       "short as well. --complete clusters the full threshold graph, whatever -k." % info["full_lists"])
     return rep, rep_score, info

@@ -93,6 +93,14 @@ class QueryDB:
             return np.ascontiguousarray(self.matrix[lo:hi], dtype=np.float32)
         return np.ascontiguousarray(self.matrix[lo:hi].float().numpy())
 
+    def embeddings_of(self, rows) -> np.ndarray:
+        """embeddings() of the given rows (an int64 array, any order) instead of a range."""
+        rows = np.asarray(rows, dtype=np.int64)
+        if self.faiss:
+            return np.ascontiguousarray(self.matrix[rows], dtype=np.float32)
+        import torch
+        return np.ascontiguousarray(self.matrix[torch.from_numpy(rows)].float().numpy())
+
     def names(self, lo: int, hi: int) -> List[str]:
         if self.faiss:
             rec = np.frombuffer(self.store.names[lo * dbutil.NAME_RECORD: hi * dbutil.NAME_RECORD], dtype="S%d" % dbutil.NAME_RECORD)

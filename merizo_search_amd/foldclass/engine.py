@@ -248,6 +248,23 @@ class HipEngine:
         """Representatives and assignments from neighbour lists (ms_cluster_greedy) -> (rep, rep_score, info)."""
         return self._ops.cluster_greedy(nbr_idx, nbr_score, lengths, min_score, mincov)
 
+    def cluster_greedy_edges(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0):
+        """cluster_greedy over the lists plus extra directed entries (src, dst, score) (ms_cluster_greedy_edges)."""
+        return self._ops.cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
+
+    def threshold_edges(self, db, q, mode: str, min_score: float, lo=None, hi=None, row_offset: int = 0, row_norm_bound=None, out=None,
+                        stats=None):
+        """Every (query, row) cell of a block of rows at or above min_score, the global rows [lo[q], hi[q]) of each query left out
+        (ms_threshold_edges) -> (src [count'], dst [count'], score [count'], count): src = the query's number in q, dst = the global
+        row.  mode as md_chain_scores takes it: the scores are those of the search in that mode, bit for bit.  row_norm_bound: the
+        rows' bound when the caller measured one (default: unit rows; a longer row is scored exactly, never wrong).
+        out: a preallocated (src, dst, score) of one length -- the call then writes at most that many entries and reports the exact
+        count, which may be larger; stats receives 'rescored'."""
+        ops = self._ops
+        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        bound = self.UNIT_ROW_BOUND if row_norm_bound is None else float(row_norm_bound)
+        return ops.threshold_edges(db, q, code, min_score, bound, lo=lo, hi=hi, row_offset=row_offset, out=out, stats=stats)
+
     def md_chain_scores(self, db, q, mode: str, cand, trows, mat_off, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
                         total: Optional[int] = None):
         """Score matrices of (query chain, target chain) candidates in the search's own arithmetic (ms_md_chain_scores).

@@ -214,6 +214,43 @@ def gather_pairs(pairs, device, group=None) -> np.ndarray:
     return np.concatenate([gathered[r, : int(counts[r])] for r in range(world)], axis=0)
 
 
+def gather_edges(src, dst, score, device, total: Optional[int] = None, rescored: int = 0, limit: Optional[int] = None, group=None):
+    """Every rank's directed entries (src int64 [m_r], dst int64 [m_r], score float32 [m_r]: tensors; m_r differs by rank) -> all of
+    them concatenated in rank order, on every rank, shaped like gather_pairs: an all-gather of the counts, then ONE all-gather of
+    the entries padded to the longest, the score travelling as its bit pattern.  total: the entries this rank FOUND when it kept
+    fewer (it ran out of room); rescored: a second count that is summed along.  limit: when the ranks' totals add up to more, no
+    entries are exchanged -- every rank learns it from the counts and gets None.
+    -> ((src, dst, score) or None, the sum of the totals, the sum of `rescored`).  Identity at world size 1."""
+    import torch
+    m = int(src.numel())
+    total = m if total is None else int(total)
+    _rank, world = rank_world(group)
+    if world == 1:
+        return (None if limit is not None and total > limit else (src, dst, score)), total, int(rescored)
+    import torch.distributed as dist
+
+    def all_gather(mine):
+        out = torch.empty((world,) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
+        if dist.get_backend(group) == "nccl":
+            dist.all_gather_into_tensor(out, mine, group=group)
+        else:
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine, group=group)
+            out.copy_(torch.stack(parts))
+        return out
+
+    counts = all_gather(torch.tensor([m, total, int(rescored)], dtype=torch.int64, device=device)).cpu().numpy()
+    all_total, all_rescored = int(counts[:, 1].sum()), int(counts[:, 2].sum())
+    if limit is not None and all_total > limit:
+        return None, all_total, all_rescored
+    block = torch.zeros((max(int(counts[:, 0].max()), 1), 3), dtype=torch.int64, device=device)
+    block[:m, 0], block[:m, 1] = src.to(device), dst.to(device)
+    block[:m, 2] = score.to(device).contiguous().view(torch.int32).to(torch.int64)
+    gathered = all_gather(block)
+    cat = torch.cat([gathered[r, : int(counts[r, 0])] for r in range(world)], dim=0)
+    return (cat[:, 0].contiguous(), cat[:, 1].contiguous(), cat[:, 2].to(torch.int32).view(torch.float32).contiguous()), all_total, all_rescored
+
+
 def balance_by_cost(costs: Sequence[float], world: int) -> List[List[int]]:
     """Deterministic longest-processing-time split of item numbers over `world` ranks (every rank
     computes the same answer).  Items of a rank are in ascending order."""

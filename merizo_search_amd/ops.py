@@ -496,6 +496,129 @@ def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float 
     return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
 
 
+def cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
+                         workspace=None):
+    """cluster_greedy over the union of the lists and m extra directed entries edge_src[e] -> edge_dst[e] with score edge_score[e]
+    (ms_cluster_greedy_edges: the definition is the header's).  nbr_idx int64 [n,k] / nbr_score float32 [n,k], or None None (k = 0:
+    extra entries only); edge_src / edge_dst int64 [m], edge_score float32 [m] CUDA/HIP tensors, or None None None (m = 0);
+    lengths int32 [n] says what n is.  -> (rep, rep_score, info) as cluster_greedy; 'saturated' counts over the lists only."""
+    import ctypes
+    torch = _lib.require_gpu()
+    t = lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)))
+    if t.is_floating_point() or t.dim() != 1 or t.numel() < 1:
+        raise MerizoHipError(f"cluster_greedy_edges: lengths: expected n >= 1 integers, got {t.dtype} of shape {tuple(t.shape)}")
+    n = int(t.numel())
+    if (nbr_idx is None) != (nbr_score is None) or len({edge_src is None, edge_dst is None, edge_score is None}) != 1:
+        raise MerizoHipError("cluster_greedy_edges: the two list tensors go together, and so do the three edge tensors")
+    k = 0
+    if nbr_idx is not None:
+        if (not isinstance(nbr_idx, torch.Tensor) or not isinstance(nbr_score, torch.Tensor) or nbr_score.dim() != 2
+                or nbr_idx.shape != nbr_score.shape or nbr_score.dtype != torch.float32 or nbr_idx.dtype != torch.int64
+                or not nbr_score.is_cuda or not (nbr_idx.is_contiguous() and nbr_score.is_contiguous()) or nbr_score.shape[0] != n):
+            raise MerizoHipError("cluster_greedy_edges: expected contiguous int64 / float32 CUDA tensors of one shape [n,k]")
+        k = int(nbr_score.shape[1])
+    m = 0
+    if edge_src is not None:
+        for name, e, dtype in (("edge_src", edge_src, torch.int64), ("edge_dst", edge_dst, torch.int64), ("edge_score", edge_score, torch.float32)):
+            if not isinstance(e, torch.Tensor) or not e.is_cuda or e.dtype != dtype or e.dim() != 1 or not e.is_contiguous():
+                raise MerizoHipError(f"cluster_greedy_edges: {name}: expected a contiguous {dtype} CUDA/HIP tensor [m]")
+        m = int(edge_src.numel())
+        if edge_dst.numel() != m or edge_score.numel() != m:
+            raise MerizoHipError("cluster_greedy_edges: edge_src, edge_dst and edge_score must have one length")
+    some = nbr_score if nbr_score is not None else edge_score
+    device = some.device if some is not None else (t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    if out is None:
+        rep = torch.empty((n,), dtype=torch.int64, device=device)
+        rep_score = torch.empty((n,), dtype=torch.float32, device=device)
+    else:
+        rep, rep_score = out
+        if (tuple(rep.shape) != (n,) or tuple(rep_score.shape) != (n,) or rep.dtype != torch.int64 or rep_score.dtype != torch.float32
+                or not (rep.is_contiguous() and rep_score.is_contiguous())):
+            raise MerizoHipError("cluster_greedy_edges: out must be contiguous (int64 [n], float32 [n]) tensors")
+    lib = _lib.load()
+    need = int(lib.ms_cluster_workspace_bytes(n))
+    if need == 0:
+        raise MerizoHipError(f"ms_cluster_workspace_bytes rejected n={n}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise MerizoHipError(f"cluster_greedy_edges: workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    with _on(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, t, rep, rep_score, workspace) as dev:
+        check(lib.ms_cluster_greedy_edges(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, ptr(edge_src) if m else 0,
+                                          ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m, ptr(t), float(min_score), float(mincov),
+                                          ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
+                                          ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), "ms_cluster_greedy_edges")
+    return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+
+
+THRESHOLD_EDGES_CAP = 1 << 16      # slots of threshold_edges' first launch when the caller names none (it launches again beyond)
+
+
+def threshold_edges(db, q, mode: int, min_score: float, row_norm_bound: float, lo=None, hi=None, row_offset: int = 0,
+                    cap: int = THRESHOLD_EDGES_CAP, out=None, workspace=None, stats=None):
+    """Every (query, row) cell of db float32 [n,128] x q float32 [nq,128] (raw, as the search of `mode` takes them) that scores at or
+    above min_score and whose global row row_offset + r lies outside [lo[qi], hi[qi]) (ms_threshold_edges: the definition is the
+    header's; the score is ip_topk's for that query and row, bit for bit).  lo / hi: int64 [nq] tensors or host arrays, both or neither.
+    -> (src int64 [count], dst int64 [count], score float32 [count], count) in unspecified order; src = the query's number,
+    dst = the global row.  Synchronises (it reads the count back) and launches a second time with a buffer of `count` slots when
+    more than `cap` cells qualify -- unless out = (src, dst, score) preallocated tensors of one length (the cap) is given: then
+    count may exceed what was written (the first min(count, cap) slots) and the caller decides.
+    stats: a dict that receives 'rescored', the cells of the last launch that went to the exact chain."""
+    torch = _lib.require_gpu()
+    _f32_cuda(db, "db", DIM)
+    _f32_cuda(q, "q", DIM)
+    n, nq = db.shape[0], q.shape[0]
+    if (lo is None) != (hi is None):
+        raise MerizoHipError("threshold_edges: lo and hi go together")
+    if lo is not None:
+        lo, hi = _i64_rows(lo, nq, "lo", db.device), _i64_rows(hi, nq, "hi", db.device)
+    lib = _lib.load()
+    need = int(lib.ms_threshold_edges_workspace_bytes(n, nq))
+    if need == 0:
+        raise MerizoHipError(f"ms_threshold_edges_workspace_bytes rejected n={n} nq={nq}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise MerizoHipError("threshold_edges: workspace must be a contiguous uint8 tensor")
+    count = torch.zeros(1, dtype=torch.int64, device=db.device)
+    st = torch.zeros(1, dtype=torch.int64, device=db.device)
+
+    def launch(src, dst, score, slots):
+        with _on(db, q, lo, hi, src, dst, score, count, st, workspace) as d:
+            check(lib.ms_threshold_edges(ptr(db), n, int(row_offset), ptr(q), nq, int(mode), ptr(lo), ptr(hi), float(min_score),
+                                         float(row_norm_bound), ptr(src), ptr(dst), ptr(score), int(slots), ptr(count), ptr(st),
+                                         ptr(workspace), workspace.numel(), d.stream), "ms_threshold_edges")
+        return int(count.item())
+
+    def buffers(slots):
+        return (torch.empty((max(slots, 1),), dtype=torch.int64, device=db.device), torch.empty((max(slots, 1),), dtype=torch.int64, device=db.device),
+                torch.empty((max(slots, 1),), dtype=torch.float32, device=db.device))
+
+    if out is not None:
+        src, dst, score = out
+        for name, e, dtype in (("src", src, torch.int64), ("dst", dst, torch.int64), ("score", score, torch.float32)):
+            if not isinstance(e, torch.Tensor) or not e.is_cuda or e.dtype != dtype or e.dim() != 1 or not e.is_contiguous():
+                raise MerizoHipError(f"threshold_edges: out {name}: expected a contiguous {dtype} CUDA/HIP tensor [cap]")
+        cap = int(src.numel())
+        if dst.numel() != cap or score.numel() != cap:
+            raise MerizoHipError("threshold_edges: the three out tensors must have one length")
+        found = launch(src, dst, score, cap)
+    else:
+        cap = max(int(cap), 0)
+        src, dst, score = buffers(cap)
+        found = launch(src, dst, score, cap)
+        if found > cap:
+            cap = found
+            src, dst, score = buffers(cap)
+            found = launch(src, dst, score, cap)
+    if stats is not None:
+        stats["rescored"] = int(st.item())
+    kept = min(found, cap)
+    return src[:kept], dst[:kept], score[:kept], found
+
+
 def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, lengths=None, qlen=None, mincov: float = 0.0,
                     out=None, workspace=None):
     """Score matrices of (query chain, target chain) candidates (ms_md_chain_scores: the definition is the header's).

@@ -299,6 +299,32 @@ int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_score, int6
                             float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps, int32_t *out_rounds,
                             int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* Connected components (single linkage) of the SAME graph: what `cluster --cluster_mode connected` runs.  The inputs are those
+ * of ms_cluster_greedy_edges -- lists [n,k] (k == 0 with NULL lists: none), m extra directed entries (m == 0 with NULL arrays:
+ * none), lengths, min_score, mincov -- and a directed entry is valid under exactly the rule of ms_cluster_greedy (row inside
+ * [0, n), no self-loop, score not NaN and >= min_score, the fp32 coverage inequality; an edge_src or a row outside [0, n) is never
+ * dereferenced).  i ~ j when either direction is valid, with the larger of the directed scores as weight (-0.0 counts as +0.0).
+ * A component is a connected component of ~.  Its representative is its highest-priority row: the longest domain, the smaller
+ * row on equal length (the priority of ms_cluster_greedy).  out_rep[i] = the representative of i's component.
+ * out_link_score[i] = 1.0f for a representative (a row without a valid entry is one: a singleton); for every other row the
+ * largest weight among the row's OWN valid incident edges, in either direction: the strongest link that ties the row to its
+ * cluster.  (A member need not be adjacent to its representative: the graph holds no "score to the representative".)
+ * HOST pointers: *out_n_components = components, *out_saturated = rows whose k list entries are ALL valid (over the lists only, 0
+ * when k == 0), *out_rounds = hook / compress rounds it took (1..n), for information.
+ * out_rep, out_link_score and *out_n_components are functions of the set of entries alone: identical however the same entries
+ * are split between lists and extras, in whatever order, with whatever duplicates, run after run; *out_saturated is one of the
+ * lists alone.  *out_rounds is NOT promised: how many trees one round merges depends on what concurrent reads of the parent
+ * array return.
+ * workspace: ms_cluster_components_workspace_bytes(n) bytes (0 for n outside [1, 2^31 - 1]), 16-byte aligned, initialised by the
+ * call.  MS_ERR_ARG: what ms_cluster_greedy_edges refuses.  Synchronises like ms_cluster_greedy_edges: it reads the rounds'
+ * "changed" words back every few rounds and returns after all its work on `stream` has finished.
+ * Backward compatible addition: ms_version() stays 210. */
+size_t ms_cluster_components_workspace_bytes(int64_t n);
+int ms_cluster_components(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                          const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
+                          float mincov, int64_t *out_rep, float *out_link_score, int64_t *out_n_components, int32_t *out_rounds,
+                          int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
 /* The score matrices of the multi-domain search's `exhaustive_cosine` mode: step 3 of dbsearch_fulllength.py (:468-483) with
  * the search's own score in place of TM-align -- the "embscore mode" that file leaves as a TODO (:202-203, :558-571).
  * Candidate c = cand[c] = {q0, nqd, t_off, nhd} is one (query chain, target chain) pair: its query domains are rows

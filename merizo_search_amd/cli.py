@@ -9,7 +9,7 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli easy-search <pdb...> <db_name> <output> <tmp> --chopping "71-189,190-290"
     python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
     python -m merizo_search_amd.cli chain-search <query_db> <target_db> <output> <tmp> [-s 0.5] [--exclude_same_chain] ...
-    python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] ...
+    python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] [--complete] [--cluster_mode connected] ...
 
 `--multi_domain_search` (search, easy-search, db-search) also writes `<output>_search_multi_dom.tsv`: the target chains that match
 every domain of a query chain.  `--multi_domain_mode exhaustive_tmalign` (the reference's; search and easy-search) aligns every
@@ -423,6 +423,10 @@ def cluster(argv) -> None:
     p.add_argument("--complete", action="store_true", default=False,
                    help="Cluster the full threshold graph, whatever -k: domains whose -k neighbours all reach --mincos get ALL their "
                         "neighbours from one more pass over the database.")
+    p.add_argument("--cluster_mode", type=str, default="greedy", choices=("greedy", "connected"),
+                   help="greedy: representatives picked greedily, every other domain with its best adjacent representative. connected: "
+                        "the connected components of the same neighbour graph (single linkage), the longest domain of each as its "
+                        "representative; with --complete the true components, whatever -k.")
     p.add_argument("--max_edges", type=int, default=2 ** 27,
                    help="--complete: directed neighbour entries that pass may hold (20 bytes of device memory each); beyond it the run is refused.")
     args = p.parse_args(argv)
@@ -433,7 +437,7 @@ def cluster(argv) -> None:
     t0 = time.time()
     run_cluster(db_name=args.db_name, output=args.output, tmp=tmp, device=args.device, topk=args.topk, mincos=args.mincos,
                 mincov=args.mincov, query_batchsize=args.query_batchsize, search_batchsize=args.search_batchsize,
-                header=args.output_headers, complete=args.complete, max_edges=args.max_edges)
+                header=args.output_headers, complete=args.complete, max_edges=args.max_edges, mode=args.cluster_mode)
     logging.info(f"Finished cluster in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 

@@ -341,3 +341,268 @@ extern "C" int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_
     return ms_cl_run("ms_cluster_greedy_edges", nbr_idx, nbr_score, n, k, edge_src, edge_dst, edge_score, m, lengths, min_score, mincov,
                      out_rep, out_rep_score, out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ms_cluster_components: the connected components of the same graph (`cluster --cluster_mode connected`; DESIGN.md section 5.8,
+// "Connected components").  Same entries, same validity test (ms_cl_valid), same two entry sources, same kernel-boundary-only
+// hand-off; what differs is what is read off the graph.
+//
+// Every row has a 64-bit priority key {length, ~row}: the longer domain, then the smaller row, is the larger key (ms_cl_before).
+// parent[n] holds the KEY of each row's parent (its own key: a root; the row is the key's low half), a forest in which a parent's key
+// is at least its child's and every tree lies inside one component of the graph.  A round is
+//   hook      one thread per entry i -> j (lists, then extras): a valid entry looks up the root keys of its endpoints by following
+//             parent[]; when they differ it does a 64-bit atomicMax(parent[row of the lower key], higher key) and raises this round's
+//             `changed` word.  (Many entries at one root: the highest key wins.)
+//   compress  one thread per row: parent[i] = root key of i (no hook runs beside it: roots are fixed for the launch).
+// Parents only rise and stay inside the row's component, so every value a racing read returns is the key of a row of the component at
+// or above the reader, and following them ends, within n steps, at a row that read as its own parent.  A row that stopped being a
+// root never is one again.  A hook whose lower root has meanwhile been hooked by another thread may replace that link by a higher
+// one: nothing is lost for good, since every round looks at every entry again.  A round that raised `changed` saw the lower root as
+// a root during the launch and left it none: every such round takes a root away, so at most n - 1 of them exist (n rounds in all).
+// A round that did not raise it read every valid entry with both ends in one tree, on memory no one wrote: the trees are the
+// components.  Their roots are the components' highest-priority rows (such a row is never the lower one) -- the REPRESENTATIVES,
+// whatever the timing, and no pass has to pick them; the NUMBER of rounds is not fixed by the inputs (what a racing read returns
+// decides how much one launch merges).
+// Afterwards, once: a per-entry 32-bit atomicMax of the order-preserving score bits on link[i] and link[j] is the link score (the
+// upper half of ms_cl_key); the finish launch writes the outputs and counts.  Vector loads, stores and atomics only; no LDS, no
+// scratch.  (A first form kept 32-bit rows in parent[], hooked by row number and picked the representatives afterwards with an
+// atomicMax on best[root]: on a 1M-row graph whose largest component has 443k rows that pass alone took 5.0 ms, every row of the
+// component on one address; DESIGN.md has the trace.)
+struct ms_cc_head {                    // the first MS_CL_HEAD_BYTES of the workspace
+    uint32_t changed[MS_CL_GROUP];     // round (slot) of the current group saw an entry between two trees
+    unsigned long long n_components;
+    unsigned long long saturated;
+};
+
+struct ms_cc_view {
+    ms_cc_head *head;
+    unsigned long long *parent;        // [n] priority key of the row's parent
+    uint32_t *link;                    // [n] order-preserving bits of the row's largest incident weight (0: none)
+    uint8_t *cut;                      // [n] the row's list holds an entry that is not valid
+};
+
+static inline size_t ms_cc_words_bytes(int64_t n) { return ms_align_up(4 * (size_t)n, 16); }
+
+static inline ms_cc_view ms_cc_carve(void *workspace, int64_t n) {
+    char *p = (char *)workspace;
+    ms_cc_view v;
+    v.head = (ms_cc_head *)p;
+    v.parent = (unsigned long long *)(p + MS_CL_HEAD_BYTES);
+    v.link = (uint32_t *)(p + MS_CL_HEAD_BYTES + 8 * (size_t)n);
+    v.cut = (uint8_t *)v.link + ms_cc_words_bytes(n);
+    return v;
+}
+
+// {length, row} as one unsigned key: the longer domain wins, then the smaller row (ms_cl_before); distinct rows, distinct keys.
+__device__ __forceinline__ unsigned long long ms_cc_priority_key(int32_t length, uint32_t row) {
+    return ((unsigned long long)((uint32_t)length ^ 0x80000000u) << 32) | (unsigned long long)(~row);
+}
+
+__device__ __forceinline__ uint32_t ms_cc_key_row(unsigned long long key) { return ~(uint32_t)key; }
+
+// A racing read of parent[]: relaxed, device scope (a vector load that does not trust this CU's cached copy).
+__device__ __forceinline__ unsigned long long ms_cc_parent(const unsigned long long *parent, uint32_t x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The key of the root above row x as this thread reads it: keys only rise along the way, so the walk ends.
+__device__ __forceinline__ unsigned long long ms_cc_root(const unsigned long long *parent, uint32_t x) {
+    for (;;) {
+        const unsigned long long p = ms_cc_parent(parent, x);
+        if (ms_cc_key_row(p) == x) return p;
+        x = ms_cc_key_row(p);
+    }
+}
+
+// The hook step of ONE directed entry i -> j with score s (i inside [0, n)); true: it saw two trees.
+__device__ __forceinline__ bool ms_cc_hook_entry(int64_t i, int64_t j, float s, int64_t n, const int32_t *__restrict__ lengths,
+                                                 float min_score, float mincov, unsigned long long *parent) {
+    int32_t lj;
+    if (!ms_cl_valid(i, j, s, n, lengths, lengths[i], min_score, mincov, &lj)) return false;
+    const unsigned long long ki = ms_cc_root(parent, (uint32_t)i), kj = ms_cc_root(parent, (uint32_t)j);
+    if (ki == kj) return false;
+    const unsigned long long low = ki < kj ? ki : kj, high = ki < kj ? kj : ki;
+    atomicMax(parent + ms_cc_key_row(low), high);
+    return true;
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_init_kernel(int64_t n, const int32_t *__restrict__ lengths,
+                                                                           unsigned long long *parent) {
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        if (i < n) parent[i] = ms_cc_priority_key(lengths[i], (uint32_t)i);
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_hook_kernel(
+        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, unsigned long long *parent, uint32_t *changed_slot) {
+    const int64_t total = n * (int64_t)k;
+    MS_CL_FOR_ENTRIES(total) {
+        const int64_t i = ms_cl_entry_row(base, k);
+        const int64_t e = base + threadIdx.x;
+        const bool saw = i < n && ms_cc_hook_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, parent);
+        if (__ballot(saw) && (threadIdx.x & 63) == 0) *changed_slot = 1u;  // (the value 1 from every wave that stores)
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_hook_edges_kernel(
+        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, unsigned long long *parent, uint32_t *changed_slot) {
+    MS_CL_FOR_ENTRIES(m) {
+        const int64_t e = base + threadIdx.x;
+        bool saw = false;
+        if (e < m) {
+            const int64_t i = edge_src[e];
+            if (i >= 0 && i < n) saw = ms_cc_hook_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, parent);
+        }
+        if (__ballot(saw) && (threadIdx.x & 63) == 0) *changed_slot = 1u;
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_compress_kernel(int64_t n, unsigned long long *parent) {
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const unsigned long long p = ms_cc_parent(parent, (uint32_t)i);
+        if (ms_cc_key_row(p) == (uint32_t)i) continue;
+        const unsigned long long r = ms_cc_root(parent, ms_cc_key_row(p));
+        if (r != p) __hip_atomic_store(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The link step of ONE directed entry i -> j (i inside [0, n)); false: the entry is not valid.
+__device__ __forceinline__ bool ms_cc_link_entry(int64_t i, int64_t j, float s, int64_t n, const int32_t *__restrict__ lengths,
+                                                 float min_score, float mincov, uint32_t *link) {
+    int32_t lj;
+    if (!ms_cl_valid(i, j, s, n, lengths, lengths[i], min_score, mincov, &lj)) return false;
+    const uint32_t b = (uint32_t)(ms_cl_key(s, 0) >> 32);
+    atomicMax(link + i, b);
+    atomicMax(link + j, b);
+    return true;
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_link_kernel(
+        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, uint32_t *link, uint8_t *cut) {
+    const int64_t total = n * (int64_t)k;
+    MS_CL_FOR_ENTRIES(total) {
+        const int64_t i = ms_cl_entry_row(base, k);
+        if (i >= n) continue;
+        const int64_t e = base + threadIdx.x;
+        if (!ms_cc_link_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, link)) cut[i] = 1;
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_link_edges_kernel(
+        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
+        const int32_t *__restrict__ lengths, float min_score, float mincov, uint32_t *link) {
+    MS_CL_FOR_ENTRIES(m) {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) continue;
+        const int64_t i = edge_src[e];
+        if (i < 0 || i >= n) continue;
+        ms_cc_link_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, link);
+    }
+}
+
+__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_finish_kernel(int64_t n, const unsigned long long *__restrict__ parent,
+                                                                             const uint32_t *__restrict__ link, const uint8_t *__restrict__ cut,
+                                                                             int64_t *out_rep, float *out_link_score, ms_cc_head *head) {
+    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        bool rep = false, full = false;
+        if (i < n) {
+            const int64_t r = (int64_t)ms_cc_key_row(parent[i]);           // (compressed: its root, the component's highest-priority row)
+            rep = r == i;
+            full = !cut[i];
+            const uint32_t b = link[i];                                    // (a row that is no representative has a valid entry)
+            out_rep[i] = r;
+            out_link_score[i] = rep ? 1.0f : b ? __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b) : -INFINITY;
+        }
+        const unsigned long long mr = __ballot(rep), mf = __ballot(full);
+        if ((threadIdx.x & 63) == 0) {
+            if (mr) atomicAdd(&head->n_components, (unsigned long long)__popcll(mr));
+            if (mf) atomicAdd(&head->saturated, (unsigned long long)__popcll(mf));
+        }
+    }
+}
+
+extern "C" size_t ms_cluster_components_workspace_bytes(int64_t n) {
+    if (n < 1 || n > 2147483647LL) return 0;
+    return MS_CL_HEAD_BYTES + 8 * (size_t)n + ms_cc_words_bytes(n) + ms_cl_rows_bytes(n);
+}
+
+extern "C" int ms_cluster_components(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                                     const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
+                                     float mincov, int64_t *out_rep, float *out_link_score, int64_t *out_n_components, int32_t *out_rounds,
+                                     int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
+    if (k < 0 || m < 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: need k >= 0 and m >= 0 (k=%d m=%lld)", k, (long long)m);
+    if ((k > 0 && (!nbr_idx || !nbr_score)) || (m > 0 && (!edge_src || !edge_dst || !edge_score)) || !lengths || !out_rep || !out_link_score ||
+        !out_n_components || !out_rounds || !out_saturated || !workspace)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_components: NULL pointer");
+    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
+    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: min_score is NaN (-inf: no cut)");
+    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: mincov must lie in [0, 1]");
+    const size_t need = ms_cluster_components_workspace_bytes(n);
+    if (workspace_bytes < need)
+        MS_FAIL(MS_ERR_ARG, "ms_cluster_components: workspace of %zu bytes, ms_cluster_components_workspace_bytes(%lld) = %zu", workspace_bytes,
+                (long long)n, need);
+    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: workspace must be 16-byte aligned");
+
+    hipStream_t st = (hipStream_t)stream;
+    const ms_cc_view v = ms_cc_carve(workspace, n);
+    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), edge_blocks = ms_cl_blocks(m), row_blocks = ms_cl_blocks(n);
+    MS_HIP_CHECK(hipMemsetAsync(workspace, 0, need, st));                  // no link, no flag, counters 0
+    hipLaunchKernelGGL(ms_components_init_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, lengths, v.parent);
+    MS_LAUNCH_CHECK("ms_components_init_kernel");
+
+    int64_t rounds = 0;
+    for (bool done = false; !done;) {
+        if (rounds > 0) MS_HIP_CHECK(hipMemsetAsync(v.head->changed, 0, sizeof(v.head->changed), st));
+        for (int g = 0; g < MS_CL_GROUP; ++g) {
+            if (k > 0) {
+                hipLaunchKernelGGL(ms_components_hook_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
+                                   min_score, mincov, v.parent, v.head->changed + g);
+                MS_LAUNCH_CHECK("ms_components_hook_kernel");
+            }
+            if (m > 0) {
+                hipLaunchKernelGGL(ms_components_hook_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score,
+                                   m, n, lengths, min_score, mincov, v.parent, v.head->changed + g);
+                MS_LAUNCH_CHECK("ms_components_hook_edges_kernel");
+            }
+            hipLaunchKernelGGL(ms_components_compress_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.parent);
+            MS_LAUNCH_CHECK("ms_components_compress_kernel");
+        }
+        uint32_t changed[MS_CL_GROUP];
+        MS_HIP_CHECK(hipMemcpyAsync(changed, v.head->changed, sizeof(changed), hipMemcpyDeviceToHost, st));
+        MS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int g = 0; g < MS_CL_GROUP && !done; ++g) {
+            ++rounds;
+            done = changed[g] == 0u;                                       // (the rounds behind it in the group changed nothing)
+        }
+        if (!done && rounds > n)                                           // every such round took a root away: unreachable on sound memory
+            MS_FAIL(MS_ERR_HIP, "ms_cluster_components: trees still merging after %lld rounds", (long long)rounds);
+    }
+
+    if (k > 0) {
+        hipLaunchKernelGGL(ms_components_link_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths, min_score,
+                           mincov, v.link, v.cut);
+        MS_LAUNCH_CHECK("ms_components_link_kernel");
+    }
+    if (m > 0) {
+        hipLaunchKernelGGL(ms_components_link_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score, m, n,
+                           lengths, min_score, mincov, v.link);
+        MS_LAUNCH_CHECK("ms_components_link_edges_kernel");
+    }
+    hipLaunchKernelGGL(ms_components_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.parent, v.link, v.cut, out_rep,
+                       out_link_score, v.head);
+    MS_LAUNCH_CHECK("ms_components_finish_kernel");
+    ms_cc_head head;
+    MS_HIP_CHECK(hipMemcpyAsync(&head, v.head, sizeof(head), hipMemcpyDeviceToHost, st));
+    MS_HIP_CHECK(hipStreamSynchronize(st));
+    *out_n_components = (int64_t)head.n_components;
+    *out_saturated = k > 0 ? (int64_t)head.saturated : 0;                  // (no list, no full list)
+    *out_rounds = (int32_t)rounds;
+    return MS_OK;
+}

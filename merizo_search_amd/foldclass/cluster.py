@@ -10,6 +10,10 @@ their neighbours at the threshold from one more pass (ms_threshold_edges: every 
 decided against the fixed threshold), and ms_cluster_greedy_edges clusters the lists plus those entries -- the true threshold
 graph ("The complete graph").
 
+`--cluster_mode connected` (run_cluster(mode="connected")) reads the connected components off the same graph instead
+(ms_cluster_components; DESIGN.md section 5.8, "Connected components"): the longest domain of a component represents it, and the
+third column is each member's strongest own link.
+
 The clustering's definition is the header's (include/merizo_search_amd.h, ms_cluster_greedy): an edge needs a cosine at or
 above --mincos in either direction and the shorter domain to cover --mincov of the longer; the longer domain is the
 representative (cd-hit's greedy order), every other domain goes to its best-scoring adjacent representative.  Coverage is that
@@ -41,14 +45,14 @@ def database_lengths(target_db: dict, qdb) -> np.ndarray:
     return np.asarray(target_db["lengths"]).astype(np.int32)
 
 
-def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, header: bool) -> None:
+def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, header: bool, score_name: str = "emb_score") -> None:
     """Clusters by the representative's row; its own line first, then its members by row.  The cosine column is formatted as
-    results.write_search_results formats emb_score."""
+    results.write_search_results formats emb_score; score_name: its name in the header line."""
     rows = np.arange(rep.shape[0], dtype=np.int64)
     order = np.lexsort((rows, rows != rep, rep))
     with open(path, "w") as handle:
         if header:
-            handle.write("representative\tmember\temb_score\n")
+            handle.write("representative\tmember\t%s\n" % score_name)
         for r in order:
             handle.write("%s\t%s\t%s\n" % (names[int(rep[r])], names[int(r)], "{:.4f}".format(rep_score[r])))
 
@@ -105,7 +109,7 @@ def _edge_pass(engine, target: Target, qdb, in_place: bool, full_rows: np.ndarra
 def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 20, mincos: Optional[float] = None,
                 mincov: float = 0.7, query_batchsize: int = 4096, search_batchsize: int = 262144, header: bool = False,
                 engine=None, timings: Optional[dict] = None, complete: bool = False, max_edges: int = MAX_EDGES,
-                edge_room: int = 2 ** 20):
+                edge_room: int = 2 ** 20, mode: str = "greedy"):
     """Cluster the rows of database `db_name` and write `<output>_cluster.tsv`.  topk: neighbours kept per row (the search
     fetches topk + 1 and drops the row itself); a row whose topk entries all count as edges may have neighbours the clustering
     never sees (`saturated`: raise -k).  Under several ranks every rank scans its shard of the rows; rank 0 alone keeps the
@@ -117,7 +121,11 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     edge pass over this rank's rows (_edge_pass; gathered to rank 0 under several ranks) and ms_cluster_greedy_edges runs on the
     lists plus those entries: the TSV a run at topk = n - 1 would write.  At most max_edges directed entries are held (beyond
     that the run is refused and nothing is written); edge_room: the entries the buffer starts with.  info gains `complete`,
-    `edges` and `rescored`, timings 'edges_ms' (the edge pass: one span per batch of full rows, as 'scan_ms' has one per batch)."""
+    `edges` and `rescored`, timings 'edges_ms' (the edge pass: one span per batch of full rows, as 'scan_ms' has one per batch).
+    mode: 'greedy' (above) or 'connected': the connected components of the same graph (ms_cluster_components on the lists, plus the
+    edge pass's entries under complete) -- rep[i] the longest row of i's component, rep_score[i] the row's strongest own link (the
+    TSV's third column is then headed `link_score`); info holds `n_components` in place of `n_reps`, and `largest`, the rows of the
+    largest component.  Without complete a list that -k cut short may split a component.  info gains `mode` in both."""
     from .dbquery import QueryDB
 
     if engine is None:
@@ -129,6 +137,8 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         _refuse("-c/--mincov must lie in [0, 1], got %r." % (mincov,))
     if topk < 1 or query_batchsize < 1 or search_batchsize < 1:
         _refuse("-k, --query_batchsize and --search_batchsize must be >= 1.")
+    if mode not in ("greedy", "connected"):
+        _refuse("cluster mode must be 'greedy' or 'connected', got %r." % (mode,))
     if int(max_edges) < 1 or int(edge_room) < 1:
         _refuse("--max_edges must be >= 1, got %r." % (max_edges,))
     _require_database(db_name)
@@ -154,7 +164,8 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     logger.info("cluster: %d rows of %s, %d neighbours per row at cosine >= %s, coverage >= %s, batches of %d%s%s"
                 % (n, db_name, k, mincos, mincov, int(query_batchsize),
                    "; queries read in place from the resident rows" if scan.in_place else "",
-                   "; complete: rows with a full list get all their neighbours from an edge pass" if complete else ""))
+                   "; complete: rows with a full list get all their neighbours from an edge pass" if complete else "")
+                + ("; connected components" if mode == "connected" else ""))
     own = engine.to_device(np.arange(n + 1, dtype=np.int64))              # row q excludes [q, q + 1): slices of one array
     nbr_s = nbr_i = count = None
     if rank == 0:                                                         # the graph: rank 0's device, never the host
@@ -168,7 +179,7 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         out = (nbr_s[b0:b1], nbr_i[b0:b1], count[b0:b1]) if rank == 0 else None
         counts.append(scan.search(b0, b1, seqs, 0.0, own[b0:b1], own[b0 + 1:b1 + 1], k, float(mincos), out=out)[2])
     full_rows = np.nonzero(torch.cat(counts).cpu().numpy() == k)[0].astype(np.int64)      # the lists that k may have cut short
-    info = {"n": n, "k": k, "full_lists": int(full_rows.shape[0]), "complete": bool(complete)}
+    info = {"n": n, "k": k, "full_lists": int(full_rows.shape[0]), "complete": bool(complete), "mode": mode}
     edges = None
     if complete:
         info.update(edges=0, rescored=0)
@@ -188,8 +199,10 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         qdb.close()
         return None, None, info
     t0 = times.mark()
-    if complete:
-        e_src, e_dst, e_score = edges if edges is not None else (None, None, None)
+    e_src, e_dst, e_score = edges if edges is not None else (None, None, None)
+    if mode == "connected":
+        rep, rep_score, found = engine.cluster_components(nbr_i, nbr_s, e_src, e_dst, e_score, lengths, float(mincos), float(mincov))
+    elif complete:
         rep, rep_score, found = engine.cluster_greedy_edges(nbr_i, nbr_s, e_src, e_dst, e_score, lengths, float(mincos), float(mincov))
     else:
         rep, rep_score, found = engine.cluster_greedy(nbr_i, nbr_s, lengths, float(mincos), float(mincov))
@@ -198,8 +211,20 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     rep, rep_score = rep.cpu().numpy(), rep_score.cpu().numpy()
     sizes = np.bincount(rep, minlength=n)
     info.update(found, singletons=int((sizes == 1).sum()))
-    write_cluster_tsv(out_path, qdb.names(0, n), rep, rep_score, header)
+    write_cluster_tsv(out_path, qdb.names(0, n), rep, rep_score, header, "link_score" if mode == "connected" else "emb_score")
     qdb.close()
+    if mode == "connected":
+        info["largest"] = int(sizes.max())
+        logger.info("cluster: %d components (%d singletons, the largest of %d rows) of %d rows in %d rounds -> %s"
+                    % (info["n_components"], info["singletons"], info["largest"], n, info["rounds"], out_path))
+        if complete:
+            logger.info("cluster: complete: %d rows had a full list of %d; the edge pass added %d directed entries (%d cells re-scored "
+                        "exactly): the components are those of the full threshold graph"
+                        % (info["full_lists"], k, info["edges"], info["rescored"]))
+        elif info["full_lists"] > 0:
+            logger.warning("cluster: %d lists are full: -k %d may have cut them short, and a component whose only bridge was cut comes "
+                           "out split in two. --complete gives the true components, whatever -k." % (info["full_lists"], k))
+        return rep, rep_score, info
     logger.info("cluster: %d clusters (%d singletons) of %d rows in %d rounds -> %s"
                 % (info["n_reps"], info["singletons"], n, info["rounds"], out_path))
     if complete:

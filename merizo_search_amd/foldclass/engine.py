@@ -252,6 +252,10 @@ class HipEngine:
         """cluster_greedy over the lists plus extra directed entries (src, dst, score) (ms_cluster_greedy_edges)."""
         return self._ops.cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
 
+    def cluster_components(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0):
+        """Connected components of the same graph (ms_cluster_components) -> (rep, link_score, info)."""
+        return self._ops.cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
+
     def threshold_edges(self, db, q, mode: str, min_score: float, lo=None, hi=None, row_offset: int = 0, row_norm_bound=None, out=None,
                         stats=None):
         """Every (query, row) cell of a block of rows at or above min_score, the global rows [lo[q], hi[q]) of each query left out

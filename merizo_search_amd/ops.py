@@ -496,35 +496,33 @@ def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float 
     return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
 
 
-def cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
-                         workspace=None):
-    """cluster_greedy over the union of the lists and m extra directed entries edge_src[e] -> edge_dst[e] with score edge_score[e]
-    (ms_cluster_greedy_edges: the definition is the header's).  nbr_idx int64 [n,k] / nbr_score float32 [n,k], or None None (k = 0:
-    extra entries only); edge_src / edge_dst int64 [m], edge_score float32 [m] CUDA/HIP tensors, or None None None (m = 0);
-    lengths int32 [n] says what n is.  -> (rep, rep_score, info) as cluster_greedy; 'saturated' counts over the lists only."""
+def _cluster_over_edges(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score,
+                        mincov, out, workspace):
+    """cluster_greedy_edges and cluster_components: one argument check, one call shape (`entry`, `workspace_bytes`: the library's
+    names; count_key: what the first count is called in info)."""
     import ctypes
     torch = _lib.require_gpu()
     t = lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)))
     if t.is_floating_point() or t.dim() != 1 or t.numel() < 1:
-        raise MerizoHipError(f"cluster_greedy_edges: lengths: expected n >= 1 integers, got {t.dtype} of shape {tuple(t.shape)}")
+        raise MerizoHipError(f"{who}: lengths: expected n >= 1 integers, got {t.dtype} of shape {tuple(t.shape)}")
     n = int(t.numel())
     if (nbr_idx is None) != (nbr_score is None) or len({edge_src is None, edge_dst is None, edge_score is None}) != 1:
-        raise MerizoHipError("cluster_greedy_edges: the two list tensors go together, and so do the three edge tensors")
+        raise MerizoHipError(f"{who}: the two list tensors go together, and so do the three edge tensors")
     k = 0
     if nbr_idx is not None:
         if (not isinstance(nbr_idx, torch.Tensor) or not isinstance(nbr_score, torch.Tensor) or nbr_score.dim() != 2
                 or nbr_idx.shape != nbr_score.shape or nbr_score.dtype != torch.float32 or nbr_idx.dtype != torch.int64
                 or not nbr_score.is_cuda or not (nbr_idx.is_contiguous() and nbr_score.is_contiguous()) or nbr_score.shape[0] != n):
-            raise MerizoHipError("cluster_greedy_edges: expected contiguous int64 / float32 CUDA tensors of one shape [n,k]")
+            raise MerizoHipError(f"{who}: expected contiguous int64 / float32 CUDA tensors of one shape [n,k]")
         k = int(nbr_score.shape[1])
     m = 0
     if edge_src is not None:
         for name, e, dtype in (("edge_src", edge_src, torch.int64), ("edge_dst", edge_dst, torch.int64), ("edge_score", edge_score, torch.float32)):
             if not isinstance(e, torch.Tensor) or not e.is_cuda or e.dtype != dtype or e.dim() != 1 or not e.is_contiguous():
-                raise MerizoHipError(f"cluster_greedy_edges: {name}: expected a contiguous {dtype} CUDA/HIP tensor [m]")
+                raise MerizoHipError(f"{who}: {name}: expected a contiguous {dtype} CUDA/HIP tensor [m]")
         m = int(edge_src.numel())
         if edge_dst.numel() != m or edge_score.numel() != m:
-            raise MerizoHipError("cluster_greedy_edges: edge_src, edge_dst and edge_score must have one length")
+            raise MerizoHipError(f"{who}: edge_src, edge_dst and edge_score must have one length")
     some = nbr_score if nbr_score is not None else edge_score
     device = some.device if some is not None else (t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
     t = t.to(device=device, dtype=torch.int32).contiguous()
@@ -535,22 +533,44 @@ def cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, len
         rep, rep_score = out
         if (tuple(rep.shape) != (n,) or tuple(rep_score.shape) != (n,) or rep.dtype != torch.int64 or rep_score.dtype != torch.float32
                 or not (rep.is_contiguous() and rep_score.is_contiguous())):
-            raise MerizoHipError("cluster_greedy_edges: out must be contiguous (int64 [n], float32 [n]) tensors")
+            raise MerizoHipError(f"{who}: out must be contiguous (int64 [n], float32 [n]) tensors")
     lib = _lib.load()
-    need = int(lib.ms_cluster_workspace_bytes(n))
+    need = int(getattr(lib, workspace_bytes)(n))
     if need == 0:
-        raise MerizoHipError(f"ms_cluster_workspace_bytes rejected n={n}")
+        raise MerizoHipError(f"{workspace_bytes} rejected n={n}")
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=device)
     elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise MerizoHipError(f"cluster_greedy_edges: workspace must be a contiguous uint8 tensor of at least {need} bytes")
+        raise MerizoHipError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes")
     n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
     with _on(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, t, rep, rep_score, workspace) as dev:
-        check(lib.ms_cluster_greedy_edges(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, ptr(edge_src) if m else 0,
-                                          ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m, ptr(t), float(min_score), float(mincov),
-                                          ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
-                                          ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), "ms_cluster_greedy_edges")
-    return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+        check(getattr(lib, entry)(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, ptr(edge_src) if m else 0,
+                                  ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m, ptr(t), float(min_score), float(mincov),
+                                  ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
+                                  ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), entry)
+    return rep, rep_score, {count_key: int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+
+
+def cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
+                         workspace=None):
+    """cluster_greedy over the union of the lists and m extra directed entries edge_src[e] -> edge_dst[e] with score edge_score[e]
+    (ms_cluster_greedy_edges: the definition is the header's).  nbr_idx int64 [n,k] / nbr_score float32 [n,k], or None None (k = 0:
+    extra entries only); edge_src / edge_dst int64 [m], edge_score float32 [m] CUDA/HIP tensors, or None None None (m = 0);
+    lengths int32 [n] says what n is.  -> (rep, rep_score, info) as cluster_greedy; 'saturated' counts over the lists only."""
+    return _cluster_over_edges("cluster_greedy_edges", "ms_cluster_greedy_edges", "ms_cluster_workspace_bytes", "n_reps", nbr_idx, nbr_score,
+                               edge_src, edge_dst, edge_score, lengths, min_score, mincov, out, workspace)
+
+
+def cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
+                       workspace=None):
+    """Connected components of the graph cluster_greedy_edges clusters (ms_cluster_components: the definition is the header's), with
+    its arguments: lists or None None, extra entries or None None None, lengths int32 [n].  -> (rep int64 [n], link_score float32
+    [n], info): rep[i] the highest-priority row of i's component, link_score[i] 1.0 for a representative and otherwise the largest
+    weight among the row's own edges; info = {'n_components', 'rounds', 'saturated'} ('rounds' may differ from run to run).
+    Synchronises.  out: optional preallocated (rep, link_score); workspace: optional uint8 tensor of
+    ms_cluster_components_workspace_bytes(n)."""
+    return _cluster_over_edges("cluster_components", "ms_cluster_components", "ms_cluster_components_workspace_bytes", "n_components", nbr_idx,
+                               nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov, out, workspace)
 
 
 THRESHOLD_EDGES_CAP = 1 << 16      # slots of threshold_edges' first launch when the caller names none (it launches again beyond)

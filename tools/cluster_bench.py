@@ -2,7 +2,7 @@
 -k 20), with HIP events around its three device parts.
 
     python tools/cluster_bench.py [--rows 1000000] [--k 20] [--mincos 0.4] [--mincov 0.7] [--batch 4096] [--dir DIR]
-                                  [--family_size S [--families F]] [--complete]
+                                  [--family_size S [--families F]] [--complete] [--cluster_mode {greedy,connected}]
 
 Prints one JSON line:
   scan_ms / scan_ms_per_batch     the scan calls (k' = k + 1; the first call builds the image: `scan_first_ms`, left out of the
@@ -16,6 +16,8 @@ Prints one JSON line:
   --complete                      run `cluster --complete`: full_lists, edges, rescored (the share of the edge pass's cells that went
                                   to the exact chain: rescored_share) and edges_ms, the HIP-event spans of the edge pass's batches (edges_batches of them;
                                   edges_first_ms: the first, which loads the kernel), are added
+  --cluster_mode connected        run `cluster --cluster_mode connected`: cluster_ms is then ms_cluster_components, rounds its hook /
+                                  compress rounds, clusters its components; `largest` (the rows of the largest component) is added
 Unit rows drawn at random have cosines ~ N(0, 1/128): at --mincos 0.4 a row of a 1M-row database has a handful of neighbours.
 Needs an MI355X from the start: the rows of the database file are generated on the device (dbsearch_bench.write_database).
 Compare `cluster_ms` with `scan_ms` of the same run."""
@@ -61,6 +63,7 @@ def main():
     ap.add_argument("--family_size", type=int, default=0, help="rows per planted family (0: none)")
     ap.add_argument("--families", type=int, default=50, help="planted families, when --family_size is given")
     ap.add_argument("--complete", action="store_true", help="cluster the full threshold graph (cluster --complete)")
+    ap.add_argument("--cluster_mode", type=str, default="greedy", choices=("greedy", "connected"), help="what is read off the graph")
     args = ap.parse_args()
     import logging
     logging.getLogger().setLevel(logging.WARNING)
@@ -82,10 +85,12 @@ def main():
         t0 = time.perf_counter()
         _rep, _score, info = cluster.run_cluster(prefix, os.path.join(work, "out"), os.path.join(work, "tmp"), "cuda:0", topk=args.k,
                                                  mincos=args.mincos, mincov=args.mincov, query_batchsize=args.batch, engine=engine,
-                                                 timings=times, complete=args.complete)
+                                                 timings=times, complete=args.complete, mode=args.cluster_mode)
         wall = time.perf_counter() - t0
         extra = {"family_size": args.family_size, "families": args.families if args.family_size > 0 else 0, "complete": args.complete,
-                 "full_lists": info["full_lists"]}
+                 "full_lists": info["full_lists"], "cluster_mode": args.cluster_mode}
+        if args.cluster_mode == "connected":
+            extra["largest"] = info["largest"]
         if args.complete:
             cells = info["full_lists"] * args.rows
             extra.update(edges=info["edges"], rescored=info["rescored"], rescored_share=round(info["rescored"] / cells, 8) if cells else 0.0,
@@ -101,7 +106,7 @@ def main():
             "scan_ms_per_batch": round(steady_ms / (calls - 1 if skip_first else calls), 4),
             "graph_write_ms": round(times["drop_ms"], 3), "graph_write_us_per_batch": round(1e3 * times["drop_ms"] / times["drop_calls"], 2),
             "cluster_ms": round(times["cluster_ms"], 3), "rounds": info["rounds"],
-            "clusters": info["n_reps"], "singletons": info["singletons"], "saturated": info["saturated"], **extra}), flush=True)
+            "clusters": info["n_components" if args.cluster_mode == "connected" else "n_reps"], "singletons": info["singletons"], "saturated": info["saturated"], **extra}), flush=True)
     finally:
         if args.dir is None:
             shutil.rmtree(work, ignore_errors=True)

@@ -135,6 +135,11 @@ class HipEngine:
         t = array if isinstance(array, self.torch.Tensor) else self.torch.from_numpy(np.ascontiguousarray(array))
         return t.to(self.device).contiguous()
 
+    def _mode_code(self, mode: str) -> int:
+        """The library's code of the score 'ip', 'ip_prenorm' or 'cosine' names."""
+        ops = self._ops
+        return {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+
     def normalize_(self, x, eps: float = 1e-12):
         return self._ops.l2_normalize_rows_(x, eps)
 
@@ -265,7 +270,7 @@ class HipEngine:
         out: a preallocated (src, dst, score) of one length -- the call then writes at most that many entries and reports the exact
         count, which may be larger; stats receives 'rescored'."""
         ops = self._ops
-        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        code = self._mode_code(mode)
         bound = self.UNIT_ROW_BOUND if row_norm_bound is None else float(row_norm_bound)
         return ops.threshold_edges(db, q, code, min_score, bound, lo=lo, hi=hi, row_offset=row_offset, out=out, stats=stats)
 
@@ -276,7 +281,7 @@ class HipEngine:
         'cosine' = of cosine_topk over cosine_rows (with lengths / qlen / mincov) -> (scores [total], match [ncand,2]).
         total: the floats the matrices take, when the caller packed them without gaps."""
         ops = self._ops
-        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        code = self._mode_code(mode)
         out = None
         if total is not None:           # (the caller laid the matrices out: no copy of the descriptors back to the host)
             out = (self.torch.empty((int(total),), dtype=self.torch.float32, device=self.device),
@@ -298,7 +303,7 @@ class HipEngine:
         drivers hold at their bound of 1 + 1e-6 unless row_norm_bound says otherwise (a longer row is re-scored exactly, never wrong).
         -> (pairs [m,2] sorted, qstatus [nqc]; -1 = a query chain this call does not serve, e.g. more than 64 domains)."""
         ops = self._ops
-        code = {"ip": ops.MODE_IP_NORMQ, "ip_prenorm": ops.MODE_IP_PRENORM, "cosine": ops.MODE_COSINE_UNIT}[mode]
+        code = self._mode_code(mode)
         if route != "lane" and row_norm_bound is None:
             row_norm_bound = 1.0 + 1e-6
         return ops.md_chain_scan(db, chain_start, q, code, qchain, min_score, lengths=lengths, qlen=qlen, mincov=mincov, route=route,

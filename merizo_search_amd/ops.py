@@ -52,6 +52,78 @@ def _f32_cuda(t, name: str, cols: Optional[int] = None):
     return t
 
 
+def _row_vectors(*vectors):
+    """The optional per-row vectors of a call, each given as (name, tensor or None, size): float32 CUDA/HIP vectors of `size` elements."""
+    for name, t, size in vectors:
+        if t is not None:
+            _f32_cuda(t, name)
+            if t.numel() != size:
+                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+
+
+def _int_desc(x, dtype, name: str, device, who: str, cols: Optional[int] = None, length: Optional[int] = None, reshape: bool = False):
+    """An integer descriptor of `who` as a contiguous tensor of the numpy `dtype` on `device`: a tensor of any integer type (a
+    floating-point one is refused), or a host array or list, which is converted as numpy converts it and uploaded.  One dimension,
+    or [rows,cols] when cols is given; of `length` rows when given.  reshape: a descriptor of another shape is laid out in that form
+    (a flat (q0, nqd, q0, nqd, ...) list for [nqc,2]) where its entries allow it."""
+    torch = _lib.require_gpu()
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
+    if t.is_floating_point():
+        raise MerizoHipError(f"{who}: {name}: expected integers, got {t.dtype}")
+    t = t.to(device=device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
+    if reshape and t.numel() % (cols or 1) == 0:
+        t = t.reshape(-1, cols) if cols else t.reshape(-1)
+    if t.dim() != (1 if cols is None else 2) or (cols is not None and t.shape[1] != cols) or (length is not None and t.shape[0] != length):
+        raise MerizoHipError(f"{who}: {name}: expected {'n' if length is None else length} rows{f' of {cols}' if cols else ''}, got {tuple(t.shape)}")
+    return t
+
+
+def _outputs(who: str, spec, out, device):
+    """The outputs of `who` as a tuple: new tensors after spec = ((dtype, shape), ...), or the caller's `out` once each of its tensors
+    is a contiguous CUDA/HIP tensor of that dtype and shape (a shape of None: the caller sized that one)."""
+    torch = _lib.require_gpu()
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=device) for dtype, shape in spec)
+    out = tuple(out)
+    if len(out) != len(spec) or any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous()
+                                    or (shape is not None and tuple(t.shape) != tuple(shape)) for t, (dtype, shape) in zip(out, spec)):
+        form = ", ".join(f"{str(dtype)[6:]} {list(shape) if shape is not None else '[...]'}" for dtype, shape in spec)
+        raise MerizoHipError(f"{who}: out must be contiguous CUDA/HIP tensors ({form})")
+    return out
+
+
+def _workspace_bytes(sizing: str, *sizes) -> int:
+    """What the library's sizing function `sizing` answers for `sizes`; 0 is its refusal."""
+    need = int(getattr(_lib.load(), sizing)(*sizes))
+    if need == 0:
+        raise MerizoHipError(f"{sizing} rejected the sizes {sizes}")
+    return need
+
+
+def _workspace(who: str, sizing: str, sizes, workspace, device):
+    """The scratch of one call of `who`: a new uint8 tensor of `sizing`(*sizes) bytes, or the caller's `workspace` once it is a
+    contiguous uint8 tensor of at least as many (the library would refuse a shorter one with MS_ERR_WORKSPACE, -2)."""
+    torch = _lib.require_gpu()
+    need = _workspace_bytes(sizing, *sizes)
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise MerizoHipError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes ({sizing}: MS_ERR_WORKSPACE (-2))")
+    return workspace
+
+
+def _capped_relaunch(launch, buffers, cap: int):
+    """launch(buffers(cap), cap) -> how many entries the call found; once more into buffers of exactly that many when they exceed cap.
+    -> (the buffers of the last launch, their slots, found).  launch synchronises (it reads the count back): one sync per launch."""
+    cap = max(int(cap), 0)
+    bufs = buffers(cap)
+    found = launch(bufs, cap)
+    if found > cap:
+        bufs, cap = buffers(found), found
+        found = launch(bufs, cap)
+    return bufs, cap, found
+
+
 def l2_normalize_rows_(x, eps: float = 1e-12):
     """In-place F.normalize(x) (reference dbsearch.py:303-304)."""
     _f32_cuda(x, "x", DIM)
@@ -93,16 +165,15 @@ class TopKWorkspace:
     def get(self, n: int, nq: int, k: int):
         torch = _lib.require_gpu()
         with torch.cuda.device(self.device):          # the plan depends on the device's CU count
-            need = int(getattr(_lib.load(), self._sizing)(n, nq, k))
-        if need == 0:
-            raise MerizoHipError(f"{self._sizing} rejected n={n} nq={nq} k={k}")
+            need = _workspace_bytes(self._sizing, n, nq, k)
         if self.buf is None or self.buf.numel() < need:
             self.buf = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self.buf
 
 
 def _out_pair(nq: int, k: int, device, out, who: str):
-    """The (scores f32 [nq,k], idx i64 [nq,k]) outputs of a search: new tensors, or the caller's `out` once it has that form."""
+    """The (scores f32 [nq,k], idx i64 [nq,k]) outputs of a search: new tensors, or the caller's `out` once it has that form
+    (_outputs written out for this one form: every search call passes through here, and a timed step should not build a table)."""
     torch = _lib.require_gpu()
     if out is None:
         return (torch.empty((nq, k), dtype=torch.float32, device=device), torch.empty((nq, k), dtype=torch.int64, device=device))
@@ -122,11 +193,7 @@ def ip_topk(db, q, k: int, mode: int = MODE_IP_PRENORM, inv_norm=None, lengths=N
     _f32_cuda(db, "db", DIM)
     _f32_cuda(q, "q", DIM)
     n, nq = db.shape[0], q.shape[0]
-    for name, t, size in (("inv_norm", inv_norm, n), ("lengths", lengths, n), ("qlen", qlen, nq)):
-        if t is not None:
-            _f32_cuda(t, name)
-            if t.numel() != size:
-                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+    _row_vectors(("inv_norm", inv_norm, n), ("lengths", lengths, n), ("qlen", qlen, nq))
     ws = workspace if isinstance(workspace, torch.Tensor) else (workspace or TopKWorkspace(db.device)).get(n, nq, k)
     out_s, out_i = _out_pair(nq, k, db.device, out, "ip_topk")
     with _on(db, q, inv_norm, lengths, qlen, ws, out_s, out_i) as dev:
@@ -277,11 +344,7 @@ def _pf_args(db, image, q, mode, lengths, qlen):
     if image is not None and (not isinstance(image, PfImage) or image.n != db.shape[0] or
                               image.data.numel() < int(_lib.load().ms_pf_image_bytes(db.shape[0], image.format))):
         raise MerizoHipError("ip_topk_prefiltered: image is not pf_build_image(db)")
-    for name, t, size in (("lengths", lengths, db.shape[0]), ("qlen", qlen, q.shape[0])):
-        if t is not None:
-            _f32_cuda(t, name)
-            if t.numel() != size:
-                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+    _row_vectors(("lengths", lengths, db.shape[0]), ("qlen", qlen, q.shape[0]))
 
 
 def ip_topk_prefiltered(db, q, k: int, row_norm_bound: float = 1.0, mode: int = MODE_IP_PRENORM, row_offset: int = 0,
@@ -359,8 +422,7 @@ def topk_merge(scores, idx):
     if scores.dtype != torch.float32 or idx.dtype != torch.int64 or not scores.is_cuda:
         raise MerizoHipError("topk_merge: expected float32 / int64 CUDA tensors")
     S, nq, k = scores.shape
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=scores.device)
-    out_i = torch.empty((nq, k), dtype=torch.int64, device=scores.device)
+    out_s, out_i = _out_pair(nq, k, scores.device, None, "topk_merge")
     with _on(scores, idx) as dev:
         check(_lib.load().ms_topk_merge(ptr(scores), ptr(idx), S, nq, k, ptr(out_s), ptr(out_i), dev.stream),
               "ms_topk_merge")
@@ -383,16 +445,6 @@ def topk_merge_packed(gathered, S: int, nq: int, k: int, idx_offset: int, out_s,
     return out_s, out_i
 
 
-def _i64_rows(x, nq: int, name: str, device):
-    """lo / hi of topk_drop_ranges: an int64 [nq] device tensor from a tensor or a host array."""
-    torch = _lib.require_gpu()
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.int64)))
-    t = t.to(device=device, dtype=torch.int64).contiguous()
-    if t.dim() != 1 or t.numel() != nq:
-        raise MerizoHipError(f"{name}: expected {nq} rows, got shape {tuple(t.shape)}")
-    return t
-
-
 def topk_drop_ranges(scores, idx, lo, hi, kout: int, min_score: float = float("-inf"), out=None):
     """Drop from sorted top-k lists [nq,kin] the entries whose row lies in [lo[q], hi[q]) and those scoring below min_score;
     the first kout of what remains, in order, (-inf, -1) behind them (ms_topk_drop_ranges).
@@ -407,17 +459,9 @@ def topk_drop_ranges(scores, idx, lo, hi, kout: int, min_score: float = float("-
     kout = int(kout)
     if nq < 1 or not 1 <= kout <= kin:
         raise MerizoHipError(f"topk_drop_ranges: need nq >= 1 and 1 <= kout <= kin (nq={nq} kin={kin} kout={kout})")
-    lo, hi = _i64_rows(lo, nq, "lo", scores.device), _i64_rows(hi, nq, "hi", scores.device)
-    if out is None:
-        out_s = torch.empty((nq, kout), dtype=torch.float32, device=scores.device)
-        out_i = torch.empty((nq, kout), dtype=torch.int64, device=scores.device)
-        out_c = torch.empty((nq,), dtype=torch.int32, device=scores.device)
-    else:
-        out_s, out_i, out_c = out
-        if (tuple(out_s.shape) != (nq, kout) or tuple(out_i.shape) != (nq, kout) or out_c.numel() != nq or out_s.dtype != torch.float32
-                or out_i.dtype != torch.int64 or out_c.dtype != torch.int32
-                or not (out_s.is_contiguous() and out_i.is_contiguous() and out_c.is_contiguous())):
-            raise MerizoHipError("topk_drop_ranges: out must be contiguous (float32 [nq,kout], int64 [nq,kout], int32 [nq]) tensors")
+    lo, hi = (_int_desc(x, np.int64, name, scores.device, "topk_drop_ranges", length=nq) for name, x in (("lo", lo), ("hi", hi)))
+    out_s, out_i, out_c = _outputs("topk_drop_ranges", ((torch.float32, (nq, kout)), (torch.int64, (nq, kout)), (torch.int32, (nq,))), out,
+                                   scores.device)
     with _on(scores, idx, lo, hi, out_s, out_i, out_c) as dev:
         check(_lib.load().ms_topk_drop_ranges(ptr(scores), ptr(idx), nq, kin, ptr(lo), ptr(hi), float(min_score), int(kout),
                                               ptr(out_s), ptr(out_i), ptr(out_c), dev.stream), "ms_topk_drop_ranges")
@@ -458,63 +502,35 @@ def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float 
     host array that is uploaded).  -> (rep int64 [n], rep_score float32 [n], info) with info = {'n_reps', 'rounds',
     'saturated'}.  Synchronises: the call returns when the clustering has finished.  out: optional preallocated (rep,
     rep_score); workspace: optional uint8 tensor of ms_cluster_workspace_bytes(n)."""
-    import ctypes
-    torch = _lib.require_gpu()
-    if (not isinstance(nbr_idx, torch.Tensor) or not isinstance(nbr_score, torch.Tensor) or nbr_score.dim() != 2
-            or nbr_idx.shape != nbr_score.shape or nbr_score.dtype != torch.float32 or nbr_idx.dtype != torch.int64 or not nbr_score.is_cuda):
-        raise MerizoHipError("cluster_greedy: expected int64 / float32 CUDA tensors of one shape [n,k]")
-    if not (nbr_idx.is_contiguous() and nbr_score.is_contiguous()):
-        raise MerizoHipError("cluster_greedy: the neighbour lists must be contiguous")
-    n, k = nbr_score.shape
-    if n < 1 or k < 1:
-        raise MerizoHipError(f"cluster_greedy: need n >= 1 and k >= 1 (n={n} k={k})")
-    t = lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)))
-    if t.is_floating_point() or t.dim() != 1 or t.numel() != n:
-        raise MerizoHipError(f"cluster_greedy: lengths: expected {n} integers, got {t.dtype} of shape {tuple(t.shape)}")
-    t = t.to(device=nbr_score.device, dtype=torch.int32).contiguous()
-    if out is None:
-        rep = torch.empty((n,), dtype=torch.int64, device=nbr_score.device)
-        rep_score = torch.empty((n,), dtype=torch.float32, device=nbr_score.device)
-    else:
-        rep, rep_score = out
-        if (tuple(rep.shape) != (n,) or tuple(rep_score.shape) != (n,) or rep.dtype != torch.int64 or rep_score.dtype != torch.float32
-                or not (rep.is_contiguous() and rep_score.is_contiguous())):
-            raise MerizoHipError("cluster_greedy: out must be contiguous (int64 [n], float32 [n]) tensors")
-    lib = _lib.load()
-    need = int(lib.ms_cluster_workspace_bytes(n))
-    if need == 0:
-        raise MerizoHipError(f"ms_cluster_workspace_bytes rejected n={n}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=nbr_score.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise MerizoHipError(f"cluster_greedy: workspace must be a contiguous uint8 tensor of at least {need} bytes")
-    n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
-    with _on(nbr_idx, nbr_score, t, rep, rep_score, workspace) as dev:
-        check(lib.ms_cluster_greedy(ptr(nbr_idx), ptr(nbr_score), n, k, ptr(t), float(min_score), float(mincov), ptr(rep), ptr(rep_score),
-                                    ctypes.addressof(n_reps), ctypes.addressof(rounds), ctypes.addressof(saturated), ptr(workspace),
-                                    workspace.numel(), dev.stream), "ms_cluster_greedy")
-    return rep, rep_score, {"n_reps": int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+    return _cluster("cluster_greedy", "ms_cluster_greedy", "ms_cluster_workspace_bytes", "n_reps", nbr_idx, nbr_score, None, lengths, min_score,
+                    mincov, out, workspace)
 
 
-def _cluster_over_edges(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score,
-                        mincov, out, workspace):
-    """cluster_greedy_edges and cluster_components: one argument check, one call shape (`entry`, `workspace_bytes`: the library's
-    names; count_key: what the first count is called in info)."""
+def _cluster(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edges, lengths, min_score, mincov, out, workspace):
+    """The three cluster calls: one argument check, one call shape (`entry`, `workspace_bytes`: the library's names; count_key: what
+    the first count is called in info).  edges: (edge_src, edge_dst, edge_score), or None for ms_cluster_greedy, whose entry point
+    takes no edge arguments and needs lists of k >= 1."""
     import ctypes
     torch = _lib.require_gpu()
-    t = lengths if isinstance(lengths, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lengths, dtype=np.int32)))
-    if t.is_floating_point() or t.dim() != 1 or t.numel() < 1:
-        raise MerizoHipError(f"{who}: lengths: expected n >= 1 integers, got {t.dtype} of shape {tuple(t.shape)}")
+    edge_src, edge_dst, edge_score = edges or (None, None, None)
+    device = next((x.device for x in (nbr_score, edge_score, lengths) if isinstance(x, torch.Tensor) and x.is_cuda), None)
+    t = _int_desc(lengths, np.int32, "lengths", device or torch.device("cuda", torch.cuda.current_device()), who)
     n = int(t.numel())
+    if n < 1:
+        raise MerizoHipError(f"{who}: lengths: expected n >= 1 integers, got none")
     if (nbr_idx is None) != (nbr_score is None) or len({edge_src is None, edge_dst is None, edge_score is None}) != 1:
         raise MerizoHipError(f"{who}: the two list tensors go together, and so do the three edge tensors")
     k = 0
     if nbr_idx is not None:
         if (not isinstance(nbr_idx, torch.Tensor) or not isinstance(nbr_score, torch.Tensor) or nbr_score.dim() != 2
                 or nbr_idx.shape != nbr_score.shape or nbr_score.dtype != torch.float32 or nbr_idx.dtype != torch.int64
-                or not nbr_score.is_cuda or not (nbr_idx.is_contiguous() and nbr_score.is_contiguous()) or nbr_score.shape[0] != n):
+                or not nbr_score.is_cuda or not (nbr_idx.is_contiguous() and nbr_score.is_contiguous())):
             raise MerizoHipError(f"{who}: expected contiguous int64 / float32 CUDA tensors of one shape [n,k]")
+        if nbr_score.shape[0] != n:
+            raise MerizoHipError(f"{who}: lengths: expected {nbr_score.shape[0]} integers, one per row of the lists, got {n}")
         k = int(nbr_score.shape[1])
+    if edges is None and k < 1:
+        raise MerizoHipError(f"{who}: need n >= 1 and k >= 1 (n={n} k={k})")
     m = 0
     if edge_src is not None:
         for name, e, dtype in (("edge_src", edge_src, torch.int64), ("edge_dst", edge_dst, torch.int64), ("edge_score", edge_score, torch.float32)):
@@ -523,31 +539,14 @@ def _cluster_over_edges(who, entry, workspace_bytes, count_key, nbr_idx, nbr_sco
         m = int(edge_src.numel())
         if edge_dst.numel() != m or edge_score.numel() != m:
             raise MerizoHipError(f"{who}: edge_src, edge_dst and edge_score must have one length")
-    some = nbr_score if nbr_score is not None else edge_score
-    device = some.device if some is not None else (t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    t = t.to(device=device, dtype=torch.int32).contiguous()
-    if out is None:
-        rep = torch.empty((n,), dtype=torch.int64, device=device)
-        rep_score = torch.empty((n,), dtype=torch.float32, device=device)
-    else:
-        rep, rep_score = out
-        if (tuple(rep.shape) != (n,) or tuple(rep_score.shape) != (n,) or rep.dtype != torch.int64 or rep_score.dtype != torch.float32
-                or not (rep.is_contiguous() and rep_score.is_contiguous())):
-            raise MerizoHipError(f"{who}: out must be contiguous (int64 [n], float32 [n]) tensors")
-    lib = _lib.load()
-    need = int(getattr(lib, workspace_bytes)(n))
-    if need == 0:
-        raise MerizoHipError(f"{workspace_bytes} rejected n={n}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
-        raise MerizoHipError(f"{who}: workspace must be a contiguous uint8 tensor of at least {need} bytes")
+    rep, rep_score = _outputs(who, ((torch.int64, (n,)), (torch.float32, (n,))), out, t.device)
+    workspace = _workspace(who, workspace_bytes, (n,), workspace, t.device)
     n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    extra = () if edges is None else (ptr(edge_src) if m else 0, ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m)
     with _on(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, t, rep, rep_score, workspace) as dev:
-        check(getattr(lib, entry)(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, ptr(edge_src) if m else 0,
-                                  ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m, ptr(t), float(min_score), float(mincov),
-                                  ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
-                                  ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), entry)
+        check(getattr(_lib.load(), entry)(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, *extra, ptr(t), float(min_score),
+                                          float(mincov), ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
+                                          ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), entry)
     return rep, rep_score, {count_key: int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
 
 
@@ -557,8 +556,8 @@ def cluster_greedy_edges(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, len
     (ms_cluster_greedy_edges: the definition is the header's).  nbr_idx int64 [n,k] / nbr_score float32 [n,k], or None None (k = 0:
     extra entries only); edge_src / edge_dst int64 [m], edge_score float32 [m] CUDA/HIP tensors, or None None None (m = 0);
     lengths int32 [n] says what n is.  -> (rep, rep_score, info) as cluster_greedy; 'saturated' counts over the lists only."""
-    return _cluster_over_edges("cluster_greedy_edges", "ms_cluster_greedy_edges", "ms_cluster_workspace_bytes", "n_reps", nbr_idx, nbr_score,
-                               edge_src, edge_dst, edge_score, lengths, min_score, mincov, out, workspace)
+    return _cluster("cluster_greedy_edges", "ms_cluster_greedy_edges", "ms_cluster_workspace_bytes", "n_reps", nbr_idx, nbr_score,
+                    (edge_src, edge_dst, edge_score), lengths, min_score, mincov, out, workspace)
 
 
 def cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
@@ -569,8 +568,8 @@ def cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengt
     weight among the row's own edges; info = {'n_components', 'rounds', 'saturated'} ('rounds' may differ from run to run).
     Synchronises.  out: optional preallocated (rep, link_score); workspace: optional uint8 tensor of
     ms_cluster_components_workspace_bytes(n)."""
-    return _cluster_over_edges("cluster_components", "ms_cluster_components", "ms_cluster_components_workspace_bytes", "n_components", nbr_idx,
-                               nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov, out, workspace)
+    return _cluster("cluster_components", "ms_cluster_components", "ms_cluster_components_workspace_bytes", "n_components", nbr_idx,
+                    nbr_score, (edge_src, edge_dst, edge_score), lengths, min_score, mincov, out, workspace)
 
 
 THRESHOLD_EDGES_CAP = 1 << 16      # slots of threshold_edges' first launch when the caller names none (it launches again beyond)
@@ -593,46 +592,28 @@ def threshold_edges(db, q, mode: int, min_score: float, row_norm_bound: float, l
     if (lo is None) != (hi is None):
         raise MerizoHipError("threshold_edges: lo and hi go together")
     if lo is not None:
-        lo, hi = _i64_rows(lo, nq, "lo", db.device), _i64_rows(hi, nq, "hi", db.device)
-    lib = _lib.load()
-    need = int(lib.ms_threshold_edges_workspace_bytes(n, nq))
-    if need == 0:
-        raise MerizoHipError(f"ms_threshold_edges_workspace_bytes rejected n={n} nq={nq}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise MerizoHipError("threshold_edges: workspace must be a contiguous uint8 tensor")
+        lo, hi = (_int_desc(x, np.int64, name, db.device, "threshold_edges", length=nq) for name, x in (("lo", lo), ("hi", hi)))
+    workspace = _workspace("threshold_edges", "ms_threshold_edges_workspace_bytes", (n, nq), workspace, db.device)
     count = torch.zeros(1, dtype=torch.int64, device=db.device)
     st = torch.zeros(1, dtype=torch.int64, device=db.device)
 
-    def launch(src, dst, score, slots):
+    def launch(bufs, slots):
+        src, dst, score = bufs
         with _on(db, q, lo, hi, src, dst, score, count, st, workspace) as d:
-            check(lib.ms_threshold_edges(ptr(db), n, int(row_offset), ptr(q), nq, int(mode), ptr(lo), ptr(hi), float(min_score),
-                                         float(row_norm_bound), ptr(src), ptr(dst), ptr(score), int(slots), ptr(count), ptr(st),
-                                         ptr(workspace), workspace.numel(), d.stream), "ms_threshold_edges")
+            check(_lib.load().ms_threshold_edges(ptr(db), n, int(row_offset), ptr(q), nq, int(mode), ptr(lo), ptr(hi), float(min_score),
+                                                 float(row_norm_bound), ptr(src), ptr(dst), ptr(score), int(slots), ptr(count), ptr(st),
+                                                 ptr(workspace), workspace.numel(), d.stream), "ms_threshold_edges")
         return int(count.item())
 
-    def buffers(slots):
-        return (torch.empty((max(slots, 1),), dtype=torch.int64, device=db.device), torch.empty((max(slots, 1),), dtype=torch.int64, device=db.device),
-                torch.empty((max(slots, 1),), dtype=torch.float32, device=db.device))
+    def buffers(slots, out=None):         # (src, dst, score) of `slots` entries each
+        return _outputs("threshold_edges", ((torch.int64, (slots,)), (torch.int64, (slots,)), (torch.float32, (slots,))), out, db.device)
 
     if out is not None:
-        src, dst, score = out
-        for name, e, dtype in (("src", src, torch.int64), ("dst", dst, torch.int64), ("score", score, torch.float32)):
-            if not isinstance(e, torch.Tensor) or not e.is_cuda or e.dtype != dtype or e.dim() != 1 or not e.is_contiguous():
-                raise MerizoHipError(f"threshold_edges: out {name}: expected a contiguous {dtype} CUDA/HIP tensor [cap]")
-        cap = int(src.numel())
-        if dst.numel() != cap or score.numel() != cap:
-            raise MerizoHipError("threshold_edges: the three out tensors must have one length")
-        found = launch(src, dst, score, cap)
+        cap = int(out[0].numel()) if isinstance(out[0], torch.Tensor) else 0           # (the first tensor says what the one length is)
+        src, dst, score = buffers(cap, out)
+        found = launch(out, cap)
     else:
-        cap = max(int(cap), 0)
-        src, dst, score = buffers(cap)
-        found = launch(src, dst, score, cap)
-        if found > cap:
-            cap = found
-            src, dst, score = buffers(cap)
-            found = launch(src, dst, score, cap)
+        (src, dst, score), cap, found = _capped_relaunch(launch, lambda slots: buffers(max(slots, 1)), cap)
     if stats is not None:
         stats["rescored"] = int(st.item())
     kept = min(found, cap)
@@ -653,25 +634,11 @@ def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, le
     _f32_cuda(db, "db", DIM)
     _f32_cuda(q, "q", DIM)
     n, nq = db.shape[0], q.shape[0]
-    for name, t, size in (("lengths", lengths, n), ("qlen", qlen, nq)):
-        if t is not None:
-            _f32_cuda(t, name)
-            if t.numel() != size:
-                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
-
-    def dev(x, dtype, name, cols=None):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
-        if t.is_floating_point():
-            raise MerizoHipError(f"md_chain_scores: {name}: expected integers, got {t.dtype}")
-        t = t.to(device=db.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-        if (cols is None and t.dim() != 1) or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
-            raise MerizoHipError(f"md_chain_scores: {name}: unexpected shape {tuple(t.shape)}")
-        return t
-
-    cand_t, trows_t, off_t = dev(cand, np.int32, "cand", 4), dev(trows, np.int64, "trows"), dev(mat_off, np.int64, "mat_off")
+    _row_vectors(("lengths", lengths, n), ("qlen", qlen, nq))
+    cand_t = _int_desc(cand, np.int32, "cand", db.device, "md_chain_scores", cols=4)
     ncand = cand_t.shape[0]
-    if off_t.numel() != ncand:
-        raise MerizoHipError(f"md_chain_scores: mat_off: expected {ncand} entries, got {off_t.numel()}")
+    trows_t = _int_desc(trows, np.int64, "trows", db.device, "md_chain_scores")
+    off_t = _int_desc(mat_off, np.int64, "mat_off", db.device, "md_chain_scores", length=ncand)
     if out is None:
         c_h = (cand if not isinstance(cand, torch.Tensor) else cand.cpu().numpy()).reshape(-1, 4).astype(np.int64)
         o_h = np.asarray(mat_off if not isinstance(mat_off, torch.Tensor) else mat_off.cpu().numpy(), dtype=np.int64).reshape(-1)
@@ -680,24 +647,14 @@ def md_chain_scores(db, q, mode: int, cand, trows, mat_off, min_score: float, le
         scores = torch.zeros((max(total, 1),), dtype=torch.float32, device=db.device)[:total]
         match = torch.empty((ncand, 2), dtype=torch.int32, device=db.device)
     else:
-        scores, match = out
-        if (scores.dtype != torch.float32 or match.dtype != torch.int32 or tuple(match.shape) != (ncand, 2)
-                or not (scores.is_contiguous() and match.is_contiguous()) or not scores.is_cuda):
-            raise MerizoHipError("md_chain_scores: out must be contiguous (float32 [total], int32 [ncand,2]) CUDA tensors")
+        scores, match = _outputs("md_chain_scores", ((torch.float32, None), (torch.int32, (ncand, 2))), out, db.device)
     if ncand == 0:                      # (nothing to score: the library would not launch either)
         return scores, match
-    lib = _lib.load()
-    need = int(lib.ms_md_chain_scores_workspace_bytes(nq))
-    if need == 0:
-        raise MerizoHipError(f"ms_md_chain_scores_workspace_bytes rejected nq={nq}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise MerizoHipError("md_chain_scores: workspace must be a contiguous uint8 tensor")
+    workspace = _workspace("md_chain_scores", "ms_md_chain_scores_workspace_bytes", (nq,), workspace, db.device)
     with _on(db, q, lengths, qlen, cand_t, trows_t, off_t, scores, match, workspace) as d:
-        check(lib.ms_md_chain_scores(ptr(db), n, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov), ptr(cand_t), ncand,
-                                     ptr(trows_t), trows_t.numel(), ptr(off_t), float(min_score), ptr(scores), ptr(match),
-                                     ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scores")
+        check(_lib.load().ms_md_chain_scores(ptr(db), n, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov), ptr(cand_t), ncand,
+                                             ptr(trows_t), trows_t.numel(), ptr(off_t), float(min_score), ptr(scores), ptr(match),
+                                             ptr(workspace), workspace.numel(), d.stream), "ms_md_chain_scores")
     return scores, match
 
 
@@ -715,42 +672,18 @@ def md_best_mappings(scores, cand, mat_off, out=None, workspace=None):
     _f32_cuda(scores, "scores")
     if scores.dim() != 1:
         raise MerizoHipError(f"md_best_mappings: scores: expected float32 [total_cells], got shape {tuple(scores.shape)}")
-
-    def dev(x, dtype, name, cols=None):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
-        if t.is_floating_point():
-            raise MerizoHipError(f"md_best_mappings: {name}: expected integers, got {t.dtype}")
-        t = t.to(device=scores.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-        if (cols is None and t.dim() != 1) or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
-            raise MerizoHipError(f"md_best_mappings: {name}: unexpected shape {tuple(t.shape)}")
-        return t
-
-    cand_t, off_t = dev(cand, np.int32, "cand", 4), dev(mat_off, np.int64, "mat_off")
+    cand_t = _int_desc(cand, np.int32, "cand", scores.device, "md_best_mappings", cols=4)
     ncand, total_cells = cand_t.shape[0], int(scores.numel())
-    if off_t.numel() != ncand:
-        raise MerizoHipError(f"md_best_mappings: mat_off: expected {ncand} entries, got {off_t.numel()}")
-    shapes = ((torch.int32, (ncand, 2)), (torch.int64, (ncand, 2)), (torch.int32, (ncand, 2, MD_BEST_MAX_QD)),
-              (torch.float32, (ncand, 2, MD_BEST_MAX_QD)))
-    if out is None:
-        out = tuple(torch.empty(shape, dtype=dtype, device=scores.device) for dtype, shape in shapes)
-    elif len(out) != 4 or any(not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape
-                              or not t.is_contiguous() for t, (dtype, shape) in zip(out, shapes)):
-        raise MerizoHipError("md_best_mappings: out must be contiguous CUDA tensors (int32 [ncand,2], int64 [ncand,2], "
-                             "int32 [ncand,2,64], float32 [ncand,2,64])")
-    status, total, path, cell = out
+    off_t = _int_desc(mat_off, np.int64, "mat_off", scores.device, "md_best_mappings", length=ncand)
+    status, total, path, cell = _outputs("md_best_mappings", ((torch.int32, (ncand, 2)), (torch.int64, (ncand, 2)),
+                                                              (torch.int32, (ncand, 2, MD_BEST_MAX_QD)), (torch.float32, (ncand, 2, MD_BEST_MAX_QD))),
+                                         out, scores.device)
     if ncand == 0:                      # (nothing to solve: the library would not launch either)
         return status, total, path, cell
-    lib = _lib.load()
-    need = int(lib.ms_md_best_mappings_workspace_bytes(ncand, total_cells))
-    if need == 0:
-        raise MerizoHipError(f"ms_md_best_mappings_workspace_bytes rejected ncand={ncand} total_cells={total_cells}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=scores.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise MerizoHipError("md_best_mappings: workspace must be a contiguous uint8 tensor")
+    workspace = _workspace("md_best_mappings", "ms_md_best_mappings_workspace_bytes", (ncand, total_cells), workspace, scores.device)
     with _on(scores, cand_t, off_t, status, total, path, cell, workspace) as d:
-        check(lib.ms_md_best_mappings(ptr(scores), total_cells, ptr(cand_t), ncand, ptr(off_t), ptr(status), ptr(total), ptr(path),
-                                      ptr(cell), ptr(workspace), workspace.numel(), d.stream), "ms_md_best_mappings")
+        check(_lib.load().ms_md_best_mappings(ptr(scores), total_cells, ptr(cand_t), ncand, ptr(off_t), ptr(status), ptr(total), ptr(path),
+                                              ptr(cell), ptr(workspace), workspace.numel(), d.stream), "ms_md_best_mappings")
     return status, total, path, cell
 
 
@@ -789,11 +722,7 @@ def md_chain_scan_launch(db, chain_start, q, mode: int, qchain, min_score: float
     if out_stats is not None and (not isinstance(out_stats, torch.Tensor) or not out_stats.is_cuda or out_stats.dtype != torch.int64
                                   or out_stats.numel() < 1):
         raise MerizoHipError("md_chain_scan: out_stats: expected an int64 CUDA/HIP tensor of one element")
-    for name, t, size in (("lengths", lengths, n), ("qlen", qlen, nq)):
-        if t is not None:
-            _f32_cuda(t, name)
-            if t.numel() != size:
-                raise MerizoHipError(f"{name}: expected {size} elements, got {t.numel()}")
+    _row_vectors(("lengths", lengths, n), ("qlen", qlen, nq))
     for name, t, dtype in (("chain_start", chain_start, torch.int64), ("qchain", qchain, torch.int32), ("out_pairs", out_pairs, torch.int64),
                            ("out_count", out_count, torch.int64), ("out_qstatus", out_qstatus, torch.int32)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
@@ -804,13 +733,8 @@ def md_chain_scan_launch(db, chain_start, q, mode: int, qchain, min_score: float
     if qchain.numel() != 2 * nqc or out_qstatus.numel() < nqc or out_count.numel() < 1 or cap < 0 or 2 * cap > out_pairs.numel():
         raise MerizoHipError("md_chain_scan: qchain [nqc,2], out_qstatus [nqc], out_count [1] and out_pairs [>= cap,2] do not fit together")
     lib = _lib.load()
-    need = int((lib.ms_md_chain_scan_mq_workspace_bytes if matrix else lib.ms_md_chain_scan_workspace_bytes)(n, nq))
-    if need == 0:
-        raise MerizoHipError(f"ms_md_chain_scan_workspace_bytes rejected n={n} nq={nq}")
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=db.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise MerizoHipError("md_chain_scan: workspace must be a contiguous uint8 tensor")
+    workspace = _workspace("md_chain_scan", "ms_md_chain_scan_mq_workspace_bytes" if matrix else "ms_md_chain_scan_workspace_bytes", (n, nq),
+                           workspace, db.device)
     with _on(db, q, lengths, qlen, chain_start, qchain, out_pairs, out_count, out_qstatus, out_stats, workspace) as d:
         args = (ptr(db), n, ptr(chain_start), nchains, ptr(q), nq, int(mode), ptr(lengths), ptr(qlen), float(mincov), ptr(qchain), nqc,
                 float(min_score), ptr(out_pairs), cap, ptr(out_count), ptr(out_qstatus))
@@ -832,30 +756,20 @@ def md_chain_scan(db, chain_start, q, mode: int, qchain, min_score: float, lengt
     matrix route, 'rescored' (cells of the last call that went to the exact chain).
     A chain table that breaks the header's rules raises."""
     torch = _lib.require_gpu()
-
-    def dev(x, dtype, cols=None):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype)))
-        if t.is_floating_point():
-            raise MerizoHipError(f"md_chain_scan: expected integers, got {t.dtype}")
-        t = t.to(device=db.device, dtype=getattr(torch, np.dtype(dtype).name)).contiguous()
-        return t.reshape(-1, cols) if cols else t.reshape(-1)
-
-    cs, qc = dev(chain_start, np.int64), dev(qchain, np.int32, 2)
+    cs = _int_desc(chain_start, np.int64, "chain_start", db.device, "md_chain_scan", reshape=True)
+    qc = _int_desc(qchain, np.int32, "qchain", db.device, "md_chain_scan", cols=2, reshape=True)
     nqc = qc.shape[0]
     count = torch.zeros(1, dtype=torch.int64, device=db.device)
     status = torch.zeros(max(nqc, 1), dtype=torch.int32, device=db.device)[:nqc]
-    cap = max(int(cap), 0)
-    pairs = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=db.device)
     taken = md_scan_route(route, q.shape[0], row_norm_bound)
     st = torch.zeros(1, dtype=torch.int64, device=db.device) if taken == "matrix" else None
-    kw = dict(lengths=lengths, qlen=qlen, mincov=mincov, route=taken, row_norm_bound=row_norm_bound, out_stats=st)
-    ws = md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, **kw)
-    found = int(count.item())
-    if found > cap:
-        cap = found
-        pairs = torch.empty((cap, 2), dtype=torch.int64, device=db.device)
-        md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=cap, workspace=ws, **kw)
-        found = int(count.item())
+    kw = dict(lengths=lengths, qlen=qlen, mincov=mincov, route=taken, row_norm_bound=row_norm_bound, out_stats=st, workspace=None)
+
+    def launch(pairs, slots):
+        kw["workspace"] = md_chain_scan_launch(db, cs, q, mode, qc, min_score, pairs, count, status, cap=slots, **kw)     # (kept for a second launch)
+        return int(count.item())
+
+    pairs, _cap, found = _capped_relaunch(launch, lambda slots: torch.empty((max(slots, 1), 2), dtype=torch.int64, device=db.device), cap)
     if stats is not None:
         stats["route"] = taken
         if st is not None:
@@ -959,21 +873,7 @@ class EgnnEncoder:
         return out
 
 
-class _TmWorkspace:
-    """Scratch of ms_tmalign_batch on one device, grown on demand and kept across calls."""
-
-    def __init__(self):
-        self.buf = {}
-
-    def get(self, device, nbytes: int):
-        torch = _lib.require_gpu()
-        t = self.buf.get(device)
-        if t is None or t.numel() < nbytes:
-            t = self.buf[device] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        return t
-
-
-_tm_ws = _TmWorkspace()
+_tm_ws = {}          # device -> the scratch of ms_tmalign_batch there, grown on demand and kept across calls
 
 
 def tmalign_batch(coords_list: Sequence[np.ndarray], seqs: Sequence[bytes], pairs, fast: bool = False, device="cuda",
@@ -1027,15 +927,15 @@ def tmalign_batch(coords_list: Sequence[np.ndarray], seqs: Sequence[bytes], pair
     sp = np.ascontiguousarray(pairs[order], dtype=np.int32)
     max1 = max(int(lens[sp[:, 0]].max()), 1)
     max2 = max(int(lens[sp[:, 1]].max()), 1)
-    need = int(lib.ms_tmalign_workspace_bytes(max1, max2, npairs))
-    if need == 0:
-        raise MerizoHipError("ms_tmalign_workspace_bytes rejected the batch")
+    need = _workspace_bytes("ms_tmalign_workspace_bytes", max1, max2, npairs)
     with torch.cuda.device(dev):
         d_xyz = torch.from_numpy(xyz).to(dev)
         d_seq = torch.from_numpy(seq).to(dev)
         d_off = torch.from_numpy(offsets).to(dev)
         d_pairs = torch.from_numpy(sp).to(dev)
-        ws = _tm_ws.get(dev, need)
+        ws = _tm_ws.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = _tm_ws[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
         of = torch.empty((npairs, 3), dtype=torch.float64, device=dev)
         oi = torch.empty((npairs, 3), dtype=torch.int32, device=dev)
         inv = torch.full((npairs, max2), -1, dtype=torch.int32, device=dev) if want_invmap else None

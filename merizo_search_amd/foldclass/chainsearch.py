@@ -112,14 +112,14 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
         open(multi_output, "w").close()
 
     engine = engine or dbsearch.engine_setup(device)
-    ids = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
-    runs = served_runs(md.chain_runs(qdb.store_names(q_lo, q_hi)), ids, q_lo)
+    ids = [md.domid2chainid(n) for n in qdb.stored_names(q_lo, q_hi)]
+    runs = served_runs(md.chain_runs(qdb.stored_names(q_lo, q_hi)), ids, q_lo)
     batches = chain_batches(runs, int(query_batchsize))
     # the target: made resident once (streamed per batch beyond the HBM budget)
     nq_batch = max([sum(b - a for a, b, _qc in batch) for batch in batches] or [1])
     target = Target.of(target_db, engine, nq_batch, 1)
     reader = qdb if same else QueryDB(db_name)
-    starts = reader.store.chain_starts()
+    starts = reader.chain_starts()
     score_mode, masked = target_score_mode(target.faiss, qdb.normalized)
     cov = float(mincov) if masked else 0.0
     logger.info("chain-search: %d query chains of %s (rows %d..%d) against the %d chains of %s in %d batches%s"
@@ -151,8 +151,8 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
             if exclude_same_chain:
                 pairs = drop_own_chain(pairs, [a for a, _b, _qc in batch], starts)
             served = [qc for _a, _b, qc in batch]
-            plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader.store)
-            results = md.score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+            plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader)
+            results = md.score_plans(plans, hits, q_emb, score_mode, engine, reader, target_rows, mincos, qlen=qlen, mincov=cov,
                                      max_mapping_paths=max_paths, report=report)
             append_written(multi_output, part, lambda f: write_multi_dom(results, f, output_headers and number == 0))
             logger.info("chain-search: batch %d of %d done (%d query chains, %d candidate pairs)"

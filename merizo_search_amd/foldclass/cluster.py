@@ -36,15 +36,6 @@ from .target import Target, score_mode
 logger = logging.getLogger(__name__)
 
 
-def database_lengths(target_db: dict, qdb) -> np.ndarray:
-    """Domain lengths int32 [n] of an opened database: the `.pt` layout's `lengths` (read_database), the faiss layout's
-    sequence offsets (end - start of the int64 pairs of `sif`, one view of the mapped file)."""
-    if qdb.faiss:
-        offsets = np.frombuffer(qdb.store.seq[0], dtype=np.int64).reshape(-1, 2)
-        return (offsets[:, 1] - offsets[:, 0]).astype(np.int32)
-    return np.asarray(target_db["lengths"]).astype(np.int32)
-
-
 def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, header: bool, score_name: str = "emb_score") -> None:
     """Clusters by the representative's row; its own line first, then its members by row.  The cosine column is formatted as
     results.write_search_results formats emb_score; score_name: its name in the header line."""
@@ -147,7 +138,7 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     n, k = int(qdb.n), int(topk)
     if k + 1 > n:
         _refuse("-k %d plus the row itself exceed the %d rows of the database." % (k, n))
-    lengths = database_lengths(target_db, qdb)
+    lengths = qdb.lengths()
     rank, _world = sharded.rank_world()
     out_path = output + "_cluster.tsv"
     if rank == 0 and os.path.exists(out_path):

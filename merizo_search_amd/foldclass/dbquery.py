@@ -2,16 +2,17 @@
 
 The reference searches PDB files only ("a few query domains per call", dbsearch.py:531-546): a user who holds embeddings in
 a database -- createdb output of a proteome, a TED shard -- has to re-parse and re-embed the structures to search with them.
-`QueryDB` reads, for a row range of either on-disk layout (dbutil.py), what a search needs of its queries:
+`QueryDB` is the database's `dbrecords.Records` (names, sequences, coordinates, metadata of its rows, either on-disk layout) plus
+what a search needs of its queries besides:
 
     embeddings(lo, hi)    float32 [hi-lo,128] as STORED: raw in the `.pt` layout (the searches normalise queries themselves:
                           MS_MODE_COSINE_UNIT, MS_MODE_IP_NORMQ -- results bit-identical to `search` on the same structure),
                           F.normalize'd in the faiss layout (searched as they are, MS_MODE_IP_PRENORM: a second normalisation
                           would change bits)
-    records(lo, hi)       the query dicts of the drivers: name (normalised as multidomain._TargetStore.entry does), seq,
-                          coords (only when an aligner will read them)
+    records(lo, hi)       the query dicts of the drivers: name (as reported: Records.names), seq, coords (only when an
+                          aligner will read them)
     exclusion_ranges(..)  per query row the database rows a self-search must not report: the row itself, or the contiguous
-                          run of rows of its chain (multidomain.domid2chainid; rows of one chain are adjacent, as
+                          run of rows of its chain (dbrecords.domid2chainid; rows of one chain are adjacent, as
                           multidomain.sibling_rows relies on)
 """
 from __future__ import annotations
@@ -22,7 +23,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import dbutil
-from .multidomain import _TargetStore, domid2chainid, equal_runs
+from .dbrecords import Records, domid2chainid, equal_runs
 
 
 def same_database(prefix_a: str, prefix_b: str) -> bool:
@@ -50,43 +51,28 @@ def parse_row_slice(text, n: int) -> Tuple[int, int]:
     return lo, hi
 
 
-class QueryDB:
-    """Stored embeddings, names, sequences and coordinates of a database's rows, for either layout."""
+class QueryDB(Records):
+    """A database's Records plus its stored embeddings (`matrix`), for either layout."""
 
     def __init__(self, db_name: str, loaded=None):
         """loaded: dbsearch.read_database's dict of this same `.pt` database -- its unpickled index and its mapped tensor are
         used instead of reading both a second time (a database searched against itself)."""
-        self.prefix = db_name
         shared = loaded is not None and not loaded.get("faiss")
-        self.store = _TargetStore(db_name, index=loaded["index"] if shared else None)
-        self.faiss = self.store.faiss
-        self.n = self.store.n
+        super().__init__(db_name, index=loaded["index"] if shared else None)
+        self.prefix = db_name
         if self.faiss:
-            info = dbutil.read_dbinfo(db_name + ".json")
-            folder = os.path.dirname(db_name + ".json")
+            info, self.matrix = dbutil.open_faiss_matrix(db_name + ".json")
             if int(info["DB_SIZE"]) != self.n:
                 raise ValueError("%s.json: DB_SIZE %d, but the names file holds %d records" % (db_name, int(info["DB_SIZE"]), self.n))
-            self.matrix = dbutil.db_memmap(os.path.join(folder, info["dbfname_IP"]), (int(info["DB_SIZE"]), int(info["DB_DIM"])))
-        elif shared:
-            self.matrix = loaded["database"]            # the raw rows on the host (the engine gets its own, normalised copy)
-        else:
-            import torch
-
-            try:                # memory-mapped: a row slice reads its own pages only
-                raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True, mmap=True)
-            except (RuntimeError, TypeError, ValueError):
-                raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True)
-            self.matrix = raw
-        if not self.faiss and self.matrix.size(0) != self.n:
-            raise ValueError("%s.pt holds %d rows, its index %d entries" % (db_name, self.matrix.size(0), self.n))
+        else:       # the raw rows on the host (the engine gets its own, normalised copy)
+            self.matrix = loaded["database"] if shared else dbutil.load_pt_matrix(db_name + ".pt")
+            if self.matrix.size(0) != self.n:
+                raise ValueError("%s.pt holds %d rows, its index %d entries" % (db_name, self.matrix.size(0), self.n))
 
     @property
     def normalized(self) -> bool:
         """Are the stored rows L2-normalised already (the faiss layout)?"""
         return self.faiss
-
-    def close(self) -> None:
-        self.store.close()
 
     def embeddings(self, lo: int, hi: int) -> np.ndarray:
         if self.faiss:
@@ -101,27 +87,6 @@ class QueryDB:
         import torch
         return np.ascontiguousarray(self.matrix[torch.from_numpy(rows)].float().numpy())
 
-    def names(self, lo: int, hi: int) -> List[str]:
-        if self.faiss:
-            rec = np.frombuffer(self.store.names[lo * dbutil.NAME_RECORD: hi * dbutil.NAME_RECORD], dtype="S%d" % dbutil.NAME_RECORD)
-            return [r.decode().rstrip() for r in rec]
-        return [os.path.basename(self.store.index[r][0]).replace(".pdb", "") for r in range(lo, hi)]
-
-    def _blobs(self, pair, lo: int, hi: int, conv):
-        index, data = pair
-        offsets = np.frombuffer(index[lo * 16: hi * 16], dtype=np.int64).reshape(-1, 2)
-        return [dbutil.retrieve_bytes(s, e, mm=data, typeconv=conv) for s, e in offsets]
-
-    def seqs(self, lo: int, hi: int) -> List[str]:
-        if self.faiss:
-            return self._blobs(self.store.seq, lo, hi, dbutil.ascii_conv)
-        return [self.store.index[r][2] for r in range(lo, hi)]
-
-    def coords(self, lo: int, hi: int) -> List[np.ndarray]:
-        if self.faiss:
-            return self._blobs(self.store.coords, lo, hi, dbutil.coord_conv)
-        return [self.store.index[r][1] for r in range(lo, hi)]
-
     def records(self, lo: int, hi: int, with_coords: bool = True) -> List[dict]:
         """Query dicts {name, seq, coords} of rows [lo, hi), in row order (coords None unless asked for)."""
         coords = self.coords(lo, hi) if with_coords else [None] * (hi - lo)
@@ -133,22 +98,17 @@ class QueryDB:
         rows = np.arange(lo, hi, dtype=np.int64)
         if not same_chain:
             return rows, rows + 1
-        chains = [domid2chainid(n) for n in self.store_names(lo, hi)]
+        chains = [domid2chainid(n) for n in self.stored_names(lo, hi)]
         first, last = np.empty(hi - lo, np.int64), np.empty(hi - lo, np.int64)
         for a, b in equal_runs(chains):
             first[a:b], last[a:b] = lo + a, lo + b
         r = lo - 1                                  # the first and the last run may continue outside the slice
-        while r >= 0 and domid2chainid(self.store.name(r)) == chains[0]:
+        while r >= 0 and domid2chainid(self.name(r)) == chains[0]:
             r -= 1
         first[first == first[0]] = r + 1
         r = hi
-        while r < self.n and domid2chainid(self.store.name(r)) == chains[-1]:
+        while r < self.n and domid2chainid(self.name(r)) == chains[-1]:
             r += 1
         last[last == last[-1]] = r
         return first, last
 
-    def store_names(self, lo: int, hi: int) -> List[str]:
-        """Names as stored (the `.pt` index keeps paths): what multidomain.domid2chainid is applied to."""
-        if self.faiss:
-            return self.names(lo, hi)
-        return [self.store.index[r][0] for r in range(lo, hi)]

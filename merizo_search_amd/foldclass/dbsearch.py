@@ -11,6 +11,9 @@ Same function names, argument meaning, return shapes and on-disk layouts as the 
     run_dbsearch                                  dbsearch.py:475-551
     run_dbsearch_db                               (no counterpart: a database as the query side, `db-search`)
 
+Both hit-record loops (dbsearch, _faiss_hit_records) take names, sequences, coordinates and metadata of their hits from the
+database's one host-side reader, dbrecords.Records, which maps each record file once per run.
+
 What differs, deliberately (DESIGN.md "host drivers"):
   * all queries of a call are embedded in ONE ragged GPU launch and searched in ONE batched
     scan, instead of the reference's per-query Python loop; results are the same lists;
@@ -34,7 +37,6 @@ What differs, deliberately (DESIGN.md "host drivers"):
 from __future__ import annotations
 
 import logging
-import mmap
 import os
 import pickle
 import sys
@@ -44,7 +46,9 @@ import numpy as np
 
 from . import sharded
 from . import tmalign as tm
-from .dbutil import ascii_conv, coord_conv, read_dbinfo, retrieve_bytes, retrieve_names_by_idx, retrieve_start_end_by_idx
+from .dbquery import QueryDB, parse_row_slice, same_database
+from .dbrecords import Records
+from .dbutil import load_pt_matrix, pt_metadata_files
 from .network import network_setup
 from .pdbio import read_pdb, write_pdb
 from .target import Target, score_mode
@@ -60,22 +64,17 @@ def read_database(db_name: str, device=None, engine=None) -> dict:
     float32 [N], 'faiss': False, 'mdfn', 'mifn'}; with an engine this rank's rows are made resident on its device at once,
     L2-normalised (engine.cosine_rows: the row half of cosine_similarity, done once) -- in the dict's Target (target.py), which
     the searches ask for the rows.  faiss layout -> {'database': json path, 'faiss': True}; the matrix is opened by Target.of.
+    The host-side rows of either dict -- names, sequences, coordinates, metadata -- are read through Records.of (dbrecords.py).
     """
     if os.path.exists(db_name + ".pt"):
         import torch
 
-        try:        # memory-mapped: under N ranks every rank then reads only the pages of ITS rows (Target.of slices first)
-            raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True, mmap=True)
-        except (RuntimeError, TypeError, ValueError):       # (an archive written in the legacy, non-zip format)
-            raw = torch.load(db_name + ".pt", map_location="cpu", weights_only=True)
+        raw = load_pt_matrix(db_name + ".pt")       # (memory-mapped: Target.of slices this rank's rows first)
         with open(db_name + ".index", "rb") as handle:
             target_index = pickle.load(handle)
         assert len(target_index) == raw.size(0)
         lengths = np.asarray([len(entry[2]) for entry in target_index], dtype=np.float32)
-        mdfn = db_name + ".metadata"
-        mifn = mdfn + ".index"
-        if not os.path.exists(mdfn) or not os.path.exists(mifn):
-            mdfn = mifn = None
+        mifn, mdfn = pt_metadata_files(db_name)
         out = {"database": raw, "index": target_index, "lengths": torch.from_numpy(lengths),
                "faiss": False, "mdfn": mdfn, "mifn": mifn}
         if engine is not None:
@@ -202,26 +201,6 @@ def _chain_list(pdb_chain: Optional[str], n_inputs: int) -> List[str]:
     sys.exit(1)
 
 
-class _Blob:
-    """mmap of an (offsets file, data file) pair of either layout."""
-
-    def __init__(self, index_path: str, data_path: str):
-        self._fi = open(index_path, "rb")
-        self._fd = open(data_path, "rb")
-        self.index = mmap.mmap(self._fi.fileno(), 0, access=mmap.ACCESS_READ)
-        self.data = mmap.mmap(self._fd.fileno(), 0, access=mmap.ACCESS_READ) if os.path.getsize(data_path) else b""
-
-    def fetch(self, idx, conv):
-        return [retrieve_bytes(s, e, self.data, typeconv=conv) for s, e in retrieve_start_end_by_idx(idx, self.index)]
-
-    def close(self):
-        for m in (self.index, self.data):
-            if hasattr(m, "close"):
-                m.close()
-        self._fi.close()
-        self._fd.close()
-
-
 def _aligner_device(network, device):
     engine = getattr(network, "engine", None)
     return getattr(engine, "device", None) or device or "cuda"
@@ -236,13 +215,10 @@ def _hip_tm_outputs(query_dicts, hits, fastmode, device):
 
 def _pt_hip_outputs(query_dicts, target_dict, tops, topk, mincos, fastmode, device):
     """`.pt` path: {rank: tm output} per query for every rank of its top-k that passes mincos, all queries in one batch."""
-    keys, hits = [], []
-    for q, (scores, indices) in enumerate(tops):
-        for rank in range(min(topk, scores.shape[0])):
-            if scores[rank] >= mincos:
-                _name, coords, seq = target_dict["index"][int(indices[rank])][:3]
-                keys.append((q, rank))
-                hits.append((q, coords, seq))
+    keys = [(q, rank) for q, (scores, _indices) in enumerate(tops) for rank in range(min(topk, scores.shape[0]))
+            if scores[rank] >= mincos]
+    records, rows = Records.of(target_dict), [int(tops[q][1][rank]) for q, rank in keys]
+    hits = [(q, coords, seq) for (q, _rank), coords, seq in zip(keys, records.coords(rows), records.seqs(rows))]
     outs = _hip_tm_outputs(query_dicts, hits, fastmode, device)
     per_query = [dict() for _ in tops]
     for (q, rank), out in zip(keys, outs):
@@ -289,19 +265,16 @@ def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: flo
     if tmalign_backend == "hip" and not skip_tmalign and _tm_outputs is None:
         _tm_outputs = _pt_hip_outputs([query_dict], target_dict, [(scores, indices)], topk, mincos, fastmode,
                                       _aligner_device(network, device))[0]
-    meta = None
-    if target_dict["mdfn"] is not None and target_dict["mifn"] is not None:
-        meta = _Blob(target_dict["mifn"], target_dict["mdfn"])
-    metadata = "{ }"
+    # the rows of every rank, from the database's one reader.  Each rank reports its OWN metadata, also one that follows a rank
+    # below mincos (the reference fetches per rank, dbsearch.py:119-123, and carries "{ }" over only in a database without any)
+    records, rows = Records.of(target_dict), [int(i) for i in indices[: min(topk, scores.shape[0])]]
+    names, seqs, metadata = records.stored_names(rows), records.seqs(rows), records.metadata(rows)
     results, all_results = {}, {}
-    for rank in range(min(topk, scores.shape[0])):
-        score, dbindex = scores[rank], int(indices[rank])
-        target_name, target_coords, target_seq = target_dict["index"][dbindex]
+    for rank, dbindex in enumerate(rows):
+        score, target_name, target_seq = scores[rank], names[rank], seqs[rank]
         if skip_tmalign:
-            if meta is not None:
-                metadata = meta.fetch([dbindex], ascii_conv)[0]     # fetched for every rank (dbsearch.py:119-123)
             if score >= mincos:
-                results[rank] = _hit(query_dict, target_name, score, len(target_seq), None, dbindex, metadata)
+                results[rank] = _hit(query_dict, target_name, score, len(target_seq), None, dbindex, metadata[rank])
             continue
         if not (score >= mincos):
             continue
@@ -311,18 +284,14 @@ def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: flo
                 _refused(query_dict, target_name)
                 continue
         else:
-            tm_output = _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode)
+            tm_output = _tmalign_pair(tmp, query_dict, records.coords([dbindex])[0], target_seq, fastmode)
         max_tm = max(tm_output["qtm"], tm_output["ttm"])
         if tm_output["len_ali"] >= len(target_seq) * mincov:       # coverage filter, `.pt` path only (:165)
-            if meta is not None:
-                metadata = meta.fetch([dbindex], ascii_conv)[0]
-            rec = _hit(query_dict, target_name, score, len(target_seq), tm_output, dbindex, metadata)
+            rec = _hit(query_dict, target_name, score, len(target_seq), tm_output, dbindex, metadata[rank])
             if max_tm >= mintm:
                 results[rank] = rec
             else:
                 all_results[rank] = rec
-    if meta is not None:
-        meta.close()
     return results, all_results
 
 
@@ -344,7 +313,6 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
         sys.exit(1)
     engine = network.engine
     nq = len(queries)
-    dbinfo, path = _faiss_files(target_dict)
     logger.info("DB iterator using batchsize of " + str(search_batchsize))
 
     query_dicts = _load_queries(queries, inputs_are_ca, _chain_list(pdb_chain, nq))
@@ -358,20 +326,14 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
     all_results = [dict() for _ in range(nq)]
     if sharded.rank_world()[0] != 0:
         return results, all_results                                       # rank 0 assembles the hit records
-    return _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
-                              _aligner_device(network, device))
+    return _faiss_hit_records(query_dicts, D, I, Records.of(target_dict), mincos, mintm, fastmode, skip_tmalign, tmalign_backend,
+                              tmp, _aligner_device(network, device))
 
 
-def _faiss_files(target_dict: dict):
-    """(the json's contents, key -> path of the file it names) of a faiss-layout database."""
-    dbinfo, db_dir = read_dbinfo(target_dict["database"]), os.path.dirname(target_dict["database"])
-    return dbinfo, lambda key: os.path.join(db_dir, dbinfo[key])
-
-
-def _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
+def _faiss_hit_records(query_dicts, D, I, records: Records, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
                        aligner_device, tm_excluded_before: int = 0):
     """Rank 0's half of dbsearch_faiss (dbsearch.py:312-472): the top-k lists D / I of all queries -> (results, all_results),
-    hit records retrieved from the mmaps of the layout (`path(key)`: the file a json key names), TM-align per hit.
+    hit records retrieved through `records` (the target database's reader), TM-align per hit.
     tm_excluded_before: hits below mintm are keyed by ONE counter over all queries of a search (dbsearch.py:449-452); a
     search made in several calls (run_dbsearch_db's query batches) passes how many the earlier calls counted."""
     nq = len(query_dicts)
@@ -384,23 +346,8 @@ def _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode,
         return results, all_results
 
     logger.info("Retrieve domain hits...")
-    with open(path("db_names_f"), "rb") as handle:
-        names_mm = mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ)
-        hit_ids = retrieve_names_by_idx(hit_indices, names_mm)
-    seq_blob = _Blob(path("sif"), path("sdf"))
-    hit_seqs = seq_blob.fetch(hit_indices, ascii_conv)
-    seq_blob.close()
-    hit_coords = None
-    if not skip_tmalign:
-        ca_blob = _Blob(path("cif"), path("cdf"))
-        hit_coords = ca_blob.fetch(hit_indices, coord_conv)
-        ca_blob.close()
-    if "mif" in dbinfo and "mdf" in dbinfo:
-        md_blob = _Blob(path("mif"), path("mdf"))
-        hit_metadata = md_blob.fetch(hit_indices, ascii_conv)
-        md_blob.close()
-    else:
-        hit_metadata = ["{ }"] * n_hits
+    hit_ids, hit_seqs, hit_metadata = records.names(hit_indices), records.seqs(hit_indices), records.metadata(hit_indices)
+    hit_coords = None if skip_tmalign else records.coords(hit_indices)
 
     if not skip_tmalign:
         logger.info("TM-align top hits...")
@@ -575,11 +522,10 @@ class _ChainStep:
     def __init__(self, qdb, q_lo: int, q_hi: int, target: Target, db_name: str, same: bool, exclude_self: bool,
                  mincos: float, mincov: float, max_mapping_paths: int, times, timings, report: str = "all"):
         from . import multidomain as md
-        from .dbquery import QueryDB
         self.md, self.qdb, self.q_lo, self.engine, self.target = md, qdb, q_lo, target.engine, target
         self.mincos, self.max_paths, self.times = float(mincos), int(max_mapping_paths), times
         self.exclude_self, self.report = exclude_self, report
-        chains = [md.domid2chainid(n) for n in qdb.store_names(q_lo, q_hi)]
+        chains = [md.domid2chainid(n) for n in qdb.stored_names(q_lo, q_hi)]
         self.chains = chains
         self.run_end = np.empty(q_hi - q_lo, np.int64)          # one past the last row (global) of each query row's run
         for a, b in md.equal_runs(chains):
@@ -638,7 +584,7 @@ class _ChainStep:
             qlen = engine.to_device(np.asarray([len(s) for s in self.qdb.seqs(r0, r1)], dtype=np.float32))
         skipped = []
         target_rows = lambda rows: self.target.rows_for(rows, self.reader)
-        res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader.store, target_rows, self.mincos,
+        res = md.cosine_step(hits, q_first, q_emb, self.score_mode, engine, self.reader, target_rows, self.mincos,
                              qlen=qlen, mincov=self.mincov, own_rows=own or None,
                              max_mapping_paths=self.max_paths, log=logger.debug, skipped=skipped, times=self.times,
                              report=self.report)
@@ -684,7 +630,6 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     import time
     from types import SimpleNamespace
 
-    from .dbquery import QueryDB, parse_row_slice, same_database
     from .results import SEARCH_FIELDS, append_written, embedding_only_format, multi_dom_writer, write_search_results
 
     t_start = time.perf_counter()
@@ -714,13 +659,10 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
     except ValueError as exc:
         _refuse("--query_rows: %s" % exc)
-    if target_db["faiss"]:
-        if search_type != "IP":
-            _refuse("Invalid/unsupported faiss search type: " + search_type + "\n\tOnly 'IP' is currently supported.")
-        dbinfo, path = _faiss_files(target_db)
-        n_target = int(dbinfo["DB_SIZE"])
-    else:
-        n_target = int(target_db["database"].shape[0])
+    if target_db["faiss"] and search_type != "IP":
+        _refuse("Invalid/unsupported faiss search type: " + search_type + "\n\tOnly 'IP' is currently supported.")
+    records = qdb if same else Records.of(target_db)                      # the target's rows on the host: one reader for the run
+    n_target = records.n
     ex_lo = ex_hi = np.zeros(q_hi - q_lo, np.int64)                       # lo >= hi: nothing excluded
     if exclude_self:
         ex_lo, ex_hi = qdb.exclusion_ranges(q_lo, q_hi, exclude_same_chain)
@@ -782,7 +724,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
             continue
         D, I, C = Ds.cpu().numpy(), Is.cpu().numpy(), Cs.cpu().numpy()
         if target_db["faiss"]:
-            results, all_results = _faiss_hit_records(query_dicts, D, I, path, dbinfo, mincos, mintm, fastmode, skip_tmalign,
+            results, all_results = _faiss_hit_records(query_dicts, D, I, records, mincos, mintm, fastmode, skip_tmalign,
                                                       tmalign_backend, tmp, aligner_device, tm_excluded_before=tm_excluded)
             tm_excluded += sum(len(per_query) for per_query in all_results)
         else:

@@ -16,6 +16,7 @@ The reference ships no writer for the faiss layout; ``write_faiss_db`` is this p
 from __future__ import annotations
 
 import json
+import mmap
 import os
 import pickle
 from typing import Iterable, List, Optional, Sequence
@@ -35,6 +36,30 @@ def read_dbinfo(dbinfo_path: str) -> dict:
 def db_memmap(filename: str, shape: tuple):
     """float32 [DB_SIZE, DB_DIM] view of `dbfname_IP` (row-major, no header)."""
     return np.memmap(filename, dtype="float32", mode="r", shape=tuple(shape))
+
+
+def open_faiss_matrix(json_path: str):
+    """(the json's contents, the memory-mapped `dbfname_IP` it names) of a faiss-layout database."""
+    info = read_dbinfo(json_path)
+    return info, db_memmap(os.path.join(os.path.dirname(json_path), info["dbfname_IP"]), (int(info["DB_SIZE"]), int(info["DB_DIM"])))
+
+
+def load_pt_matrix(pt_path: str):
+    """The RAW rows of a `.pt` database on the host, memory-mapped: a row slice then reads its own pages only (under N ranks
+    every rank those of ITS rows)."""
+    import torch
+
+    try:
+        return torch.load(pt_path, map_location="cpu", weights_only=True, mmap=True)
+    except (RuntimeError, TypeError, ValueError):       # (an archive written in the legacy, non-zip format)
+        return torch.load(pt_path, map_location="cpu", weights_only=True)
+
+
+def pt_metadata_files(db_name: str):
+    """(offsets file, data file) of a `.pt` database's optional metadata, (None, None) unless both exist (dbsearch.py:59-62)."""
+    mdfn = db_name + ".metadata"
+    mifn = mdfn + ".index"
+    return (mifn, mdfn) if os.path.exists(mdfn) and os.path.exists(mifn) else (None, None)
 
 
 def db_iterator(embeddings, batch_size: int):
@@ -71,6 +96,33 @@ def retrieve_start_end_by_idx(idx, mm, use_sorting: bool = False) -> np.ndarray:
 def retrieve_bytes(start, end, mm, typeconv=None):
     raw = bytes(mm[int(start):int(end)])
     return raw if typeconv is None else typeconv(raw)
+
+
+def map_file(filename: str):
+    """Read-only mmap of a whole file (mmap keeps its own descriptor: the file object is closed at once)."""
+    with open(filename, "rb") as handle:
+        return mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ)
+
+
+class Blob:
+    """mmap of an (offsets file, data file) pair of either layout.  A zero-byte data file (every record empty) is served as b""."""
+
+    def __init__(self, index_path: str, data_path: str):
+        self.index = map_file(index_path)
+        self.data = map_file(data_path) if os.path.getsize(data_path) else b""
+
+    def offsets(self, rows) -> np.ndarray:
+        """(start, end) int64 [m,2] of `rows` -- a slice: one view of the mapped offsets; or an int sequence, in the order given."""
+        pairs = np.frombuffer(self.index, dtype=np.int64).reshape(-1, 2)
+        return pairs[rows] if isinstance(rows, slice) else pairs[np.asarray(rows, dtype=np.int64).reshape(-1)]
+
+    def fetch(self, rows, conv):
+        return [retrieve_bytes(s, e, self.data, typeconv=conv) for s, e in self.offsets(rows)]
+
+    def close(self):
+        for m in (self.index, self.data):
+            if hasattr(m, "close"):
+                m.close()
 
 
 def coord_conv(raw: bytes) -> np.ndarray:

@@ -34,16 +34,16 @@ from __future__ import annotations
 
 import itertools
 import logging
-import mmap
 import os
 import re
 import shutil
 from concurrent.futures import ThreadPoolExecutor
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import dbutil
+from .dbquery import QueryDB
+from .dbrecords import Records, chain_runs, domid2chainid, equal_runs      # (callers and tests say md.chain_runs, md.domid2chainid)
 from .pdbio import read_pdb, write_pdb
 from .tmalign import align_many, check_backend, find_tmalign, run_tmalign
 
@@ -63,38 +63,7 @@ MAX_MAPPING_PATHS = 1_000_000
 REPORTS = ("all", "best")
 BEST_MAX_HIT_DOMAINS = 1024     # report 'best': target domains per chain ms_md_best_mappings serves (MS_MD_BEST_MAX_HD)
 
-_TWO_DIGITS = re.compile(r"[0-9]{2}$")
 _MERIZO_SUFFIX = re.compile(r"_merizo_[0-9]*$")
-
-
-def domid2chainid(domain_id: str) -> str:
-    """'cath-dompdb/2pi4A04.pdb' -> '2pi4A'; 'x/AF-Q93009-F1-model_v4_TED02.pdb' -> 'AF-Q93009-F1-model_v4'.
-
-    Same steps as the reference (:36-39), including its use of str.rstrip('.pdb'), which strips
-    any trailing run of the characters '.', 'p', 'd', 'b' rather than the literal suffix."""
-    stem = os.path.basename(domain_id).rstrip(".pdb")
-    stem = _TWO_DIGITS.sub("", stem).rstrip("_")
-    return stem[: -len("_TED")] if stem.endswith("_TED") else stem
-
-
-def equal_runs(keys: Sequence) -> List[Tuple[int, int]]:
-    """(first, one past the last) position of every run of adjacent equal keys, in order; a key that comes back after another
-    one starts a new run."""
-    runs, a = [], 0
-    for b in range(1, len(keys) + 1):
-        if b == len(keys) or keys[b] != keys[a]:
-            runs.append((a, b))
-            a = b
-    return runs
-
-
-def chain_runs(names: Sequence[str]) -> np.ndarray:
-    """int64 [nchains + 1]: the first row of every run of adjacent names with one domid2chainid (its rstrip('.pdb') quirk
-    included), closed by len(names) -- the target chains of mode `database_cosine`, where a chain IS a run of rows.  Two runs
-    with one chain id that are not adjacent are two chains here (`exhaustive_cosine` would merge them by name; the reference
-    assumes adjacency, :363-394).  A plain loop: about a microsecond-scale call of domid2chainid per name."""
-    starts = [a for a, _b in equal_runs([domid2chainid(name) for name in names])]
-    return np.asarray(starts + [len(names)], dtype=np.int64)
 
 
 def mapping_category(path: Sequence[int], nhd: int) -> int:
@@ -199,91 +168,6 @@ def group_hits(query_names: Sequence[str], query_chains: Sequence[str], search_r
     return index
 
 
-class _TargetStore:
-    """Names, coordinates, sequences and metadata of database rows, for either on-disk layout."""
-
-    def __init__(self, db_name: str, index=None):
-        """index: the unpickled `<db>.index` of a `.pt` database when the caller holds it already."""
-        self.maps = []
-        self.meta = None
-        if os.path.exists(db_name + ".pt"):
-            import pickle
-
-            self.faiss = False
-            if index is not None:
-                self.index = index
-            else:
-                with open(db_name + ".index", "rb") as handle:
-                    self.index = pickle.load(handle)
-            self.n = len(self.index)
-            mdfn = db_name + ".metadata"
-            if os.path.exists(mdfn) and os.path.exists(mdfn + ".index"):
-                self.meta = (self._map(mdfn + ".index"), self._map(mdfn))
-        else:
-            self.faiss = True
-            info = dbutil.read_dbinfo(db_name + ".json")
-            folder = os.path.dirname(db_name + ".json")
-            path = lambda key: os.path.join(folder, info[key])
-            self.names = self._map(path("db_names_f"))
-            self.n = len(self.names) // dbutil.NAME_RECORD
-            self.seq = (self._map(path("sif")), self._map(path("sdf")))
-            self.coords = (self._map(path("cif")), self._map(path("cdf")))
-            if "mif" in info and "mdf" in info:
-                self.meta = (self._map(path("mif")), self._map(path("mdf")))
-
-    def _map(self, filename):
-        handle = open(filename, "rb")
-        mm = mmap.mmap(handle.fileno(), 0, access=mmap.ACCESS_READ)
-        self.maps.append((mm, handle))
-        return mm
-
-    def stored_names(self, lo: int = 0, hi: Optional[int] = None) -> List[str]:
-        """The names of rows [lo, hi) as stored (the `.pt` index keeps paths): what domid2chainid is applied to."""
-        hi = self.n if hi is None else hi
-        if self.faiss:
-            rec = np.frombuffer(self.names[lo * dbutil.NAME_RECORD: hi * dbutil.NAME_RECORD], dtype="S%d" % dbutil.NAME_RECORD)
-            return [r.decode().rstrip() for r in rec]
-        return [self.index[r][0] for r in range(lo, hi)]
-
-    def chain_starts(self) -> np.ndarray:
-        """chain_runs of all rows, computed once per open database."""
-        if getattr(self, "_chain_starts", None) is None:
-            self._chain_starts = chain_runs(self.stored_names())
-        return self._chain_starts
-
-    def close(self):
-        for mm, handle in self.maps:
-            mm.close()
-            handle.close()
-
-    def name(self, row: int) -> str:
-        if self.faiss:
-            return str(dbutil.retrieve_names_by_idx([row], self.names)[0])
-        return self.index[row][0]
-
-    def _blob(self, pair, row, conv):
-        start, end = dbutil.retrieve_start_end_by_idx([row], pair[0])[0]
-        return dbutil.retrieve_bytes(start, end, mm=pair[1], typeconv=conv)
-
-    def entry_name(self, row: int) -> str:
-        """The domain name entry() reports for a database row."""
-        return self.name(row) if self.faiss else os.path.basename(self.index[row][0]).replace(".pdb", "")
-
-    def name_meta(self, row: int):
-        """(domain name, metadata json) of a database row, as entry() gives them -- without its coordinates and sequence."""
-        metadata = self._blob(self.meta, row, dbutil.ascii_conv) if self.meta is not None else "{ }"
-        return self.entry_name(row), metadata
-
-    def entry(self, row: int):
-        """(domain name, coords [N,3], sequence, row, metadata json) of a database row (:426-466)."""
-        metadata = self._blob(self.meta, row, dbutil.ascii_conv) if self.meta is not None else "{ }"
-        if self.faiss:
-            return (self.name(row), self._blob(self.coords, row, dbutil.coord_conv), self._blob(self.seq, row, dbutil.ascii_conv),
-                    row, metadata)
-        name, coords, seq = self.index[row][:3]
-        return (os.path.basename(name).replace(".pdb", ""), coords, seq, row, metadata)
-
-
 def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, device=None, fastmode: bool = False,
                         threads: int = -1, mintm: float = 0.5, inputs_from_easy_search: bool = False,
                         mode: str = "exhaustive_tmalign", pdb_chain: Optional[str] = None, tmalign_backend: str = "auto",
@@ -323,7 +207,7 @@ def multi_domain_search(queries, search_results, db_name: str, tmp_root: str, de
     structures = dict(zip(names, queries))
     hits = group_hits(names, query_chains, search_results)
 
-    store = _TargetStore(db_name)
+    store = Records(db_name)
     try:
         if tmalign_backend == "hip":
             return _multi_domain_hip(hits, structures, store, fastmode, mintm, device)
@@ -360,7 +244,7 @@ def _entry_mappings(scores: np.ndarray, qc: str, qds: List[str], entries) -> lis
     return results
 
 
-def _chain_entries(qc: str, domains: dict, store: "_TargetStore"):
+def _chain_entries(qc: str, domains: dict, store: Records):
     """The database entries of every hit chain with at least as many domains as query chain qc has (:346-394), or
     None (with the reference's log line) when there is nothing to align."""
     nqd = len(domains)
@@ -457,7 +341,7 @@ def compact_target_rows(engine, reader, rows: np.ndarray):
     return engine.cosine_rows(matrix), engine.to_device(np.asarray(lens, dtype=np.float32)), np.arange(len(rows), dtype=np.int64)
 
 
-def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable,
+def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, store: Records, target_rows: Callable,
                 mincos: float, qlen=None, mincov: float = 0.0, own_rows: Optional[dict] = None,
                 max_mapping_paths: int = MAX_MAPPING_PATHS, log=logger.info, skipped: Optional[list] = None, times=None,
                 report: str = "all") -> list:
@@ -474,7 +358,7 @@ def cosine_step(hits, q_first: Dict[str, int], q_emb, score_mode: str, engine, s
                        max_mapping_paths=max_mapping_paths, skipped=skipped, times=times, report=report)
 
 
-def hit_chain_plans(hits, q_first: Dict[str, int], store: "_TargetStore", own_rows: Optional[dict] = None, log=logger.info) -> list:
+def hit_chain_plans(hits, q_first: Dict[str, int], store: Records, own_rows: Optional[dict] = None, log=logger.info) -> list:
     """cosine_step's first half: (qc, hc, q0, nqd, global rows of the hit chain) for every chain the hits of a query chain name
     (step 2), query chains in the order of `hits`, hit chains per query chain in np.unique order of their chain id."""
     plans = []
@@ -489,7 +373,7 @@ def hit_chain_plans(hits, q_first: Dict[str, int], store: "_TargetStore", own_ro
     return plans
 
 
-def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStore", target_rows: Callable, mincos: float, qlen=None,
+def score_plans(plans, hits, q_emb, score_mode: str, engine, store: Records, target_rows: Callable, mincos: float, qlen=None,
                 mincov: float = 0.0, max_mapping_paths: int = MAX_MAPPING_PATHS, skipped: Optional[list] = None, times=None,
                 report: str = "all") -> list:
     """cosine_step's second half: plans (qc, hc, q0, nqd, global rows) -> result tuples.  ONE engine.md_chain_scores call for all
@@ -548,7 +432,7 @@ def score_plans(plans, hits, q_emb, score_mode: str, engine, store: "_TargetStor
     return results
 
 
-def best_lines(plans, hits, store: "_TargetStore", status, total, path, cell, skipped: Optional[list] = None) -> list:
+def best_lines(plans, hits, store: Records, status, total, path, cell, skipped: Optional[list] = None) -> list:
     """Report 'best': md_best_mappings' outputs for `plans` -> tuples (query_chain, nqd, hit_chain, nhd, category, 'score',
     'qd:hd:score,...', '[metadata,...]').  Per pair with an any-order mapping (kind-0 status 1) one line for it and, when its
     category is 0 and an order-preserving mapping exists (kind-1 status 1), a second line for that one.  score: the float64 sum
@@ -649,7 +533,7 @@ def database_candidates(engine, reader, target_db: Optional[dict], starts: np.nd
 
 
 def candidate_plans(pairs: np.ndarray, served: Sequence[str], hits, q_first: Dict[str, int], starts: np.ndarray,
-                    store: "_TargetStore") -> list:
+                    store: Records) -> list:
     """Candidates (index into `served`, target chain number) -> the plans score_plans takes, in `exhaustive_cosine`'s order: query
     chains as `hits` has them, target chains per query chain by chain id (np.unique's order; two runs with one id: by row)."""
     plans = []
@@ -677,7 +561,6 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
     if len(queries) == 1:
         logger.warning("Cannot execute multi-domain search with only one query domain.")
         return None
-    from .dbquery import QueryDB
     from .target import score_mode as target_score_mode
     names, query_chains, structures = _query_structures(queries, inputs_from_easy_search, pdb_chain)
     if len(set(names)) != len(names):
@@ -700,7 +583,7 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
         cov = mincov if masked else 0.0
         target_rows = lambda rows: compact_target_rows(engine, reader, rows)
         if not whole_database:
-            return cosine_step(hits, q_first, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+            return cosine_step(hits, q_first, q_emb, score_mode, engine, reader, target_rows, mincos, qlen=qlen, mincov=cov,
                                max_mapping_paths=max_mapping_paths, report=report)
         served = []
         for qc, domains in hits.items():
@@ -713,14 +596,14 @@ def _multi_domain_embedding(queries, search_results, db_name, device, inputs_fro
                 served.append(qc)
         if not served:
             return []
-        starts = reader.store.chain_starts()
+        starts = reader.chain_starts()
         qchain = np.asarray([(q_first[qc], len(hits[qc])) for qc in served], dtype=np.int32)
         pairs = database_candidates(engine, reader, target_db, starts, q_emb, score_mode, qchain, mincos, qlen, cov, search_batchsize)
         from . import sharded
         if sharded.rank_world()[0] != 0:
             return None
-        plans = candidate_plans(pairs, served, hits, q_first, starts, reader.store)
-        return score_plans(plans, hits, q_emb, score_mode, engine, reader.store, target_rows, mincos, qlen=qlen, mincov=cov,
+        plans = candidate_plans(pairs, served, hits, q_first, starts, reader)
+        return score_plans(plans, hits, q_emb, score_mode, engine, reader, target_rows, mincos, qlen=qlen, mincov=cov,
                            max_mapping_paths=max_mapping_paths, report=report)
     finally:
         reader.close()

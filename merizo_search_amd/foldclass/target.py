@@ -1,15 +1,14 @@
 """`Target`: this rank's rows of a target database on the engine's device, or streamed when they do not fit.
-dbsearch.read_database's dict keeps the reference's keys (host-side values, never overwritten) plus ONE private key, read by
-this module alone: the Target of one (database, engine, shard)."""
+dbsearch.read_database's dict keeps the reference's keys (host-side values, never overwritten) plus two private keys, each read by
+one module alone: here the Target of one (database, engine, shard); in dbrecords.py the host-side Records of the same rows."""
 from __future__ import annotations
 
 import logging
-import os
 
 import numpy as np
 
 from . import multidomain, sharded
-from .dbutil import db_iterator, db_memmap, read_dbinfo
+from .dbutil import db_iterator, open_faiss_matrix
 
 logger = logging.getLogger(__name__)
 
@@ -64,9 +63,7 @@ class Target:
         target_dict.pop(_KEY, None)
         prefilter = hasattr(engine, "lazy_pf_image")        # (the CPU oracle engine of the tests has no prefiltered search)
         if target_dict["faiss"]:
-            info = read_dbinfo(target_dict["database"])
-            matrix = db_memmap(filename=os.path.join(os.path.dirname(target_dict["database"]), info["dbfname_IP"]),
-                               shape=(info["DB_SIZE"], info["DB_DIM"]))
+            info, matrix = open_faiss_matrix(target_dict["database"])
             t = cls(engine, True, info["DB_SIZE"], matrix)
             if (t.hi - t.lo) * matrix.shape[1] * 4 > engine.resident_budget(int(nq), int(k)):
                 logger.info("database shard of %d rows exceeds the resident budget: it is streamed in blocks" % (t.hi - t.lo))

@@ -273,8 +273,8 @@ def expected_lines(planted, layout, search_tsv, pair_scores=oracle_pair_scores, 
         for r in range(lo, hi):
             full = [i for i, c in enumerate(chain_of) if c == chain_of[r]]
             own_rows[chain_of[r]] = (full[0], full[-1] + 1)
-    out = driver_ref(qnames, chain_of[lo:hi], [by_name.get(n, {}) for n in qnames], db.n, db.store.name, db.store.entry_name,
-                     lambda r: db.store.name_meta(r)[1], lambda qi, rows: pair_scores(layout, emb, seqlen, [lo + i for i in qi], rows, mincov),
+    out = driver_ref(qnames, chain_of[lo:hi], [by_name.get(n, {}) for n in qnames], db.n, db.name, db.entry_name,
+                     lambda r: db.name_meta(r)[1], lambda qi, rows: pair_scores(layout, emb, seqlen, [lo + i for i in qi], rows, mincov),
                      mincos, own_rows=own_rows, max_paths=max_paths, skipped=skipped)
     db.close()
     return tsv_rows(out)

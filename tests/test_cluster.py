@@ -160,13 +160,13 @@ def test_cluster_refusals_come_before_any_gpu_work(planted, tmp_path, caplog):
 
 
 def test_database_lengths_of_both_layouts(planted):
-    from merizo_search_amd.foldclass import cluster, dbquery, dbsearch as ds
+    from merizo_search_amd.foldclass import dbquery, dbsearch as ds
     work, _names, lengths, _family = planted
     for layout in ("fa", "pt"):
         prefix = os.path.join(work, layout)
         db = ds.read_database(prefix)
         qdb = dbquery.QueryDB(prefix, loaded=None if db["faiss"] else db)
-        got = cluster.database_lengths(db, qdb)
+        got = qdb.lengths()
         qdb.close()
         assert got.dtype == np.int32 and np.array_equal(got, lengths), layout
 

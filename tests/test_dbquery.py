@@ -118,7 +118,7 @@ def test_db_search_refusals_come_before_any_gpu_work(small_case, tmp_path, caplo
 # ------------------------------------------------------------------ the query-side reader --------
 def test_querydb_reads_both_layouts_alike(small_case):
     from merizo_search_amd.foldclass import dbquery
-    from merizo_search_amd.foldclass.multidomain import _TargetStore
+    from merizo_search_amd.foldclass.dbrecords import Records
     work, names, first, last = small_case
     fa, pt = dbquery.QueryDB(os.path.join(work, "fa")), dbquery.QueryDB(os.path.join(work, "pt"))
     assert fa.n == pt.n == 120 and fa.normalized and not pt.normalized
@@ -134,7 +134,7 @@ def test_querydb_reads_both_layouts_alike(small_case):
                 a, b = db.exclusion_ranges(lo, hi, same_chain)
                 assert np.array_equal(a, first[lo:hi] if same_chain else np.arange(lo, hi))
                 assert np.array_equal(b, last[lo:hi] if same_chain else np.arange(lo, hi) + 1)
-    store = _TargetStore(os.path.join(work, "pt"))                      # the `query` column: the name as _TargetStore.entry gives it
+    store = Records(os.path.join(work, "pt"))                           # the `query` column: the name as Records.entry gives it
     rec = pt.records(3, 6)
     assert [r["name"] for r in rec] == [store.entry(r)[0] for r in range(3, 6)] and rec[0]["coords"] is not None
     assert fa.records(3, 6, with_coords=False)[1]["coords"] is None

@@ -76,7 +76,7 @@ def test_dbutil_retrieval_matches_reference(golden_dir, golden_meta):
     sq = dbutil.startend_memmap(os.path.join(sl, "seq.index"), meta["n"])
     assert np.array_equal(se[:, 1] - se[:, 0], 12 * (sq[:, 1] - sq[:, 0]))     # 12 bytes of CA per residue
     assert set(meta["ted100_json"]) == {"dbfname_IP", "DB_SIZE", "DB_DIM", "db_names_f", "sif", "sdf", "cif", "cdf", "mif", "mdf"}
-    blob = ds._Blob(os.path.join(sl, "cath10.metadata.index"), os.path.join(sl, "cath10.metadata"))
+    blob = dbutil.Blob(os.path.join(sl, "cath10.metadata.index"), os.path.join(sl, "cath10.metadata"))
     assert blob.fetch([0], dbutil.ascii_conv)[0] == meta["cath_first"]
     blob.close()
 
@@ -97,12 +97,12 @@ def test_faiss_layout_writer_roundtrip(tmp_path):
     with open(tmp_path / info["db_names_f"], "rb") as f:
         mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
         assert dbutil.retrieve_names_by_idx([24, 0], mm).tolist() == [short[24], short[0]]
-    ca = ds._Blob(str(tmp_path / info["cif"]), str(tmp_path / info["cdf"]))
+    ca = dbutil.Blob(str(tmp_path / info["cif"]), str(tmp_path / info["cdf"]))
     got = ca.fetch([7, 3], dbutil.coord_conv)
     assert np.array_equal(got[0], coords[7]) and np.array_equal(got[1], coords[3])
-    sq = ds._Blob(str(tmp_path / info["sif"]), str(tmp_path / info["sdf"]))
+    sq = dbutil.Blob(str(tmp_path / info["sif"]), str(tmp_path / info["sdf"]))
     assert sq.fetch([5], dbutil.ascii_conv) == [seqs[5]]
-    mdb = ds._Blob(str(tmp_path / info["mif"]), str(tmp_path / info["mdf"]))
+    mdb = dbutil.Blob(str(tmp_path / info["mif"]), str(tmp_path / info["mdf"]))
     assert mdb.fetch([9], dbutil.ascii_conv) == [md[9]]
     for b in (ca, sq, mdb):
         b.close()

@@ -105,18 +105,18 @@ def _planted_run(planted, layout, engine, target_db, search_batchsize=262144):
     seqlen = np.asarray([len(s) for s in reader.seqs(0, reader.n)], np.float32)
     q_emb = engine.to_device(emb[qrows])
     mode, qlen, cov = ("ip_prenorm", None, 0.0) if layout == "fa" else ("cosine", engine.to_device(seqlen[qrows]), MINCOV)
-    starts = reader.store.chain_starts()
+    starts = reader.chain_starts()
     qchain = np.asarray([(0, 3), (3, 5)], np.int32)
     pairs = md.database_candidates(engine, reader, target_db, starts, q_emb, mode, qchain, MINCOS, qlen, cov, search_batchsize)
-    plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader.store)
-    res = md.score_plans(plans, hits, q_emb, mode, engine, reader.store, lambda rows: md.compact_target_rows(engine, reader, rows), MINCOS,
+    plans = md.candidate_plans(pairs, served, hits, q_first, starts, reader)
+    res = md.score_plans(plans, hits, q_emb, mode, engine, reader, lambda rows: md.compact_target_rows(engine, reader, rows), MINCOS,
                          qlen=qlen, mincov=cov)
     # the restated driver, fed with COMPLETE hit lists: every row at or above mincos is a hit of its query domain
     scores = _pair_scores(layout, emb, seqlen, qrows, list(range(reader.n)), MINCOV)
-    results = [{k: {"query": names[qr], "target": reader.store.entry_name(int(r)), "dbindex": int(r)}
+    results = [{k: {"query": names[qr], "target": reader.entry_name(int(r)), "dbindex": int(r)}
                 for k, r in enumerate(np.flatnonzero(scores[i] >= np.float32(MINCOS)))} for i, qr in enumerate(qrows)]
-    want = mc.driver_ref([names[r] for r in qrows], [chain_of[r] for r in qrows], results, reader.n, reader.store.name, reader.store.entry_name,
-                         lambda r: reader.store.name_meta(r)[1],
+    want = mc.driver_ref([names[r] for r in qrows], [chain_of[r] for r in qrows], results, reader.n, reader.name, reader.entry_name,
+                         lambda r: reader.name_meta(r)[1],
                          lambda qi, rows: _pair_scores(layout, emb, seqlen, [qrows[i] for i in qi], rows, MINCOV), MINCOS)
     reader.close()
     return mc.tsv_rows(res), mc.tsv_rows(want), pairs

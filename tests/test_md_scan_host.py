@@ -53,9 +53,9 @@ def test_the_store_computes_its_chain_table_once(planted):
     from merizo_search_amd.foldclass.dbquery import QueryDB
     for layout in ("fa", "pt"):
         db = QueryDB(os.path.join(planted[0], layout))
-        starts = db.store.chain_starts()
-        assert starts.tolist() == _id_runs(planted[2]) and db.store.chain_starts() is starts
-        assert db.store.stored_names(3, 6) == db.store_names(3, 6)
+        starts = db.chain_starts()
+        assert starts.tolist() == _id_runs(planted[2]) and db.chain_starts() is starts
+        assert db.stored_names(3, 6) == [n if layout == "fa" else "/x/" + n + ".pdb" for n in planted[1][3:6]]     # as write_planted stores them
         db.close()
 
 
@@ -120,11 +120,11 @@ def test_candidate_plans_order_and_rows(planted):
     from merizo_search_amd.foldclass.dbquery import QueryDB
     work, names, chain_of = planted
     db = QueryDB(os.path.join(work, "pt"))
-    starts = db.store.chain_starts()
+    starts = db.chain_starts()
     hits = {"B": {"B1": [], "B2": [], "B3": []}, "A": {"A1": [], "A2": []}}
     nch = len(starts) - 1
     pairs = np.asarray([(0, c) for c in range(nch)][::-1] + [(1, 5), (1, 2)], np.int64)
-    plans = md.candidate_plans(pairs, ["B", "A"], hits, {"B": 0, "A": 3}, starts, db.store)
+    plans = md.candidate_plans(pairs, ["B", "A"], hits, {"B": 0, "A": 3}, starts, db)
     db.close()
     long_enough = [c for c in range(nch) if starts[c + 1] - starts[c] >= 3]
     assert [p[0] for p in plans] == ["B"] * len(long_enough) + ["A"] * sum(1 for c in (2, 5) if starts[c + 1] - starts[c] >= 2)

@@ -9,6 +9,7 @@ import pytest
 import md_scan_case as sc
 import multidom_case as mc
 import pf_adversarial as pa
+from mq_filter_case import mode_code as _mode_code, prepared as _prepared, to_gpu as _t
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -17,24 +18,6 @@ CANARY = -7777
 TAIL = 16
 BOUND = 1.0 + 1e-6                     # the row-norm bound the drivers give for unit rows
 E = 1.05e-3                            # ms_pf_err_coef(MS_PF_F16X1)
-
-
-def _mode_code(mode):
-    from merizo_search_amd import _lib
-    return {"prenorm": _lib.MODE_IP_PRENORM, "normq": _lib.MODE_IP_NORMQ, "unit": _lib.MODE_COSINE_UNIT}[mode]
-
-
-def _prepared(q, mode):
-    import torch
-    from merizo_search_amd import ops
-    if mode == "prenorm":
-        return np.array(q, np.float32)
-    return ops.l2_normalize_rows(torch.from_numpy(np.ascontiguousarray(q, np.float32)).cuda(), 1e-12 if mode == "normq" else 1e-8).cpu().numpy()
-
-
-def _t(a, dt):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
 
 
 def _gpu(db, table, q, mode, qchain, min_score, cap=8192, lengths=None, qlen=None, mincov=0.0, workspace=None, route="matrix", bound=BOUND):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import cluster_complete_case as ccc
+from mq_filter_case import mode_code as _code, prepared as _prepared, to_gpu as _t
 
 pytestmark = pytest.mark.gpu
 NINF = -np.inf
@@ -14,27 +15,9 @@ MODES = ("prenorm", "normq", "unit")
 CUT = 0.5
 
 
-def _code(mode):
-    from merizo_search_amd import _lib
-    return {"prenorm": _lib.MODE_IP_PRENORM, "normq": _lib.MODE_IP_NORMQ, "unit": _lib.MODE_COSINE_UNIT}[mode]
-
-
-def _t(a, dt):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
-
-
 def _unit(x):
     x = np.asarray(x, np.float64)
     return (x / np.linalg.norm(x, axis=-1, keepdims=True)).astype(np.float32)
-
-
-def _prepared(q, mode):
-    """The queries as the scan of `mode` multiplies with them (the GPU's own normalisation launch)."""
-    from merizo_search_amd import ops
-    if mode == "prenorm":
-        return np.array(q, np.float32)
-    return ops.l2_normalize_rows(_t(q, np.float32), 1e-12 if mode == "normq" else 1e-8).cpu().numpy()
 
 
 def _case(n, nq, seed, scale=True):

@@ -13,7 +13,9 @@
  * must be ordered on one stream: the searches keep lists, counters and the exact pass's launch plan in it between their launches) --
  * concurrent searches take one workspace each.  A prefiltered search whose bookkeeping was disturbed all the same (a second stream on
  * its workspace, a launch aborted half way) does not answer: the exact pass queued behind it finds the re-scoring's verdict missing
- * and TRAPS (round 6; ms_debug_prefilter_poison is the test's way in).
+ * and TRAPS (round 6; ms_debug_prefilter_poison is the test's way in).  For the same reason the prefiltered entry points
+ * (ms_ip_topk_prefiltered and its _prepare / _scan / _finish stages) CANNOT BE CAPTURED INTO A GRAPH: the base of the compaction's ticket
+ * and the epochs of the call are kernel arguments, counted on by the host from call to call, so a replay would carry stale ones and trap.
  *
  * Environment: the search path has a handful of diagnostic and tuning switches (MS_LOADER_WAVE, MS_PREPASS_TILES, ...), each read once
  * per process; DESIGN.md, "Switches of the search path", is the one table of their names, defaults and meanings.

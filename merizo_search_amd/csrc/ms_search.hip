@@ -31,12 +31,10 @@
 //   ms_kway_merge_kernel      public merge of S sorted lists (shards after the all-gather, blocks when streaming);
 //                             ms_kway_merge_any_kernel beyond 64 lists
 #include "ms_common.h"
+#include "ms_wsstate.h"
 
 #include <math.h>
 #include <stdlib.h>
-
-#include <atomic>
-#include <mutex>
 
 thread_local char ms_err_buf[512] = "";
 
@@ -476,7 +474,7 @@ struct PfCompact {
 // The two counters of the compaction (slot counter, ticket) are plain atomic adds -- 256 workgroups arrive within a few
 // microseconds, and a compare-and-swap loop per arrival (tried: counters tagged with the call's epoch) serialises them into
 // O(n^2) retries: +250 us at C2.  Round 6: the TICKET is never reset -- it counts on from call to call, the host keeps the running
-// total per workspace (sync_take_tickets) and hands every call the value its first arrival will see (ticket_base): the last
+// total per workspace (ms_wsstate.h) and hands every call the value its first arrival will see (ticket_base): the last
 // workgroup is the one that draws ticket_base + nq - 1.  A counter that is not where the host expects it (a launch that was
 // aborted half way, a second stream sharing the workspace against the header's rule, memory poisoned through
 // ms_debug_prefilter_poison) never produces that ticket, gate[1] keeps the previous call's epoch, and the gated launches queued
@@ -727,6 +725,14 @@ __global__ __launch_bounds__(64) void ms_kway_merge_any_kernel(const float *scor
 
 // ------------------------------------------------------------------ host side ----------
 // (the switches, the launch plan, the workspace carve and the rules shared below: ms_plan.h)
+// The device behind the per-workspace records (ms_wsstate.h: everything the host remembers about a workspace between calls)
+int ms_wsstate::current_device() { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : -1; }
+void *ms_wsstate::alloc_zeroed(size_t bytes) {
+    void *mem = nullptr;
+    if (hipMalloc(&mem, bytes) == hipSuccess && hipMemset(mem, 0, bytes) != hipSuccess) { (void)hipFree(mem); mem = nullptr; }
+    return mem;
+}
+bool ms_wsstate::drain_and_zero(void *block, size_t bytes) { return hipDeviceSynchronize() == hipSuccess && hipMemset(block, 0, bytes) == hipSuccess; }
 namespace {
 
 // CU count of HIP's current device (the device the caller's tensors live on: the Python front end
@@ -742,78 +748,6 @@ int cu_count_cached() {
         cus[dev] = c;
     }
     return cus[dev];
-}
-
-// Histogram counters of the shared bound (ScanHist) must be zero when a scan starts.  ms_sample_bound_kernel zeroes them
-// (every ms_ip_topk / ms_ip_topk_prepare); a staged ms_ip_topk_scan that does not directly follow a prepare on the same
-// workspace and shape (the same workspace scanned twice in a row) gets a hipMemsetAsync in front of it.  The record below is
-// only that optimisation's bookkeeping: per workspace pointer, did the last staged call leave the counters clean?
-struct HistClean { const void *ws; int64_t n; int nq, k; bool clean; };
-HistClean g_hist_clean[16];
-int g_hist_clean_next = 0;
-std::mutex g_hist_clean_mutex;
-bool hist_take_clean(const void *ws, int64_t n, int nq, int k) {         // -> were they clean?  (they are dirty afterwards)
-    std::lock_guard<std::mutex> lock(g_hist_clean_mutex);
-    for (HistClean &e : g_hist_clean)
-        if (e.ws == ws && e.n == n && e.nq == nq && e.k == k) { const bool c = e.clean; e.clean = false; return c; }
-    return false;
-}
-void hist_invalidate(const void *ws) {          // a scan ran on this workspace outside the staged bookkeeping: its counters are dirty
-    std::lock_guard<std::mutex> lock(g_hist_clean_mutex);
-    for (HistClean &e : g_hist_clean)
-        if (e.ws == ws) e.clean = false;
-}
-void hist_mark_clean(const void *ws, int64_t n, int nq, int k) {
-    std::lock_guard<std::mutex> lock(g_hist_clean_mutex);
-    for (HistClean &e : g_hist_clean)
-        if (e.ws == ws) { e.n = n; e.nq = nq; e.k = k; e.clean = true; return; }
-    g_hist_clean[g_hist_clean_next] = HistClean{ws, n, nq, k, true};
-    g_hist_clean_next = (g_hist_clean_next + 1) % 16;
-}
-
-// The arrival counters of the in-launch merge must be zero when a launch starts, and the launch leaves them that way (the
-// last arriver resets its counter).  They do NOT live in the caller's workspace -- memory the library cannot vouch for
-// between calls (a freed workspace's address may come back holding anything) -- but in a small block the library allocates
-// and zeroes itself, one per (workspace pointer, device): calls that share a workspace are serialised by the caller anyway
-// (they share the partial lists), so they may share the block.  64 blocks; a 65th workspace takes over the least recently used
-// one (after a device synchronisation: a rare event).
-struct SyncBlock { const void *ws; int dev; char *mem; uint64_t last_use; uint32_t pf_tickets; };      // pf_tickets: tickets handed out so far = the value of the device's ticket word
-constexpr int SYNC_BLOCKS = 64;
-constexpr size_t SYNC_BYTES = 512;         // [0,256) 64 arrival counters of the in-launch merge; [256] the prefilter's gate word
-SyncBlock g_sync[SYNC_BLOCKS];
-int g_sync_used = 0;
-uint64_t g_sync_clock = 0;
-char *sync_block_for(const void *ws) {
-    std::lock_guard<std::mutex> lock(g_hist_clean_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    for (int i = 0; i < g_sync_used; ++i)
-        if (g_sync[i].ws == ws && g_sync[i].dev == dev) { g_sync[i].last_use = ++g_sync_clock; return g_sync[i].mem; }
-    if (g_sync_used == SYNC_BLOCKS) {
-        // every block is taken: the least recently used one of this device changes hands -- after the device has drained
-        // (launches of its old workspace may still be in flight on another stream) and with its counters zeroed again
-        int lru = -1;
-        for (int i = 0; i < g_sync_used; ++i)
-            if (g_sync[i].dev == dev && (lru < 0 || g_sync[i].last_use < g_sync[lru].last_use)) lru = i;
-        if (lru < 0 || hipDeviceSynchronize() != hipSuccess || hipMemset(g_sync[lru].mem, 0, SYNC_BYTES) != hipSuccess) return nullptr;
-        g_sync[lru].ws = ws;
-        g_sync[lru].last_use = ++g_sync_clock;
-        g_sync[lru].pf_tickets = 0u;
-        return g_sync[lru].mem;
-    }
-    char *mem = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&mem), SYNC_BYTES) != hipSuccess) return nullptr;
-    if (hipMemset(mem, 0, SYNC_BYTES) != hipSuccess) { (void)hipFree(mem); return nullptr; }
-    g_sync[g_sync_used++] = SyncBlock{ws, dev, mem, ++g_sync_clock, 0u};
-    return mem;
-}
-// The re-scoring launch of a prefiltered search draws `count` tickets from the block's ticket word (one per query); -> the value the
-// first of them will see.  Wraps modulo 2^32 like the device counter.
-uint32_t sync_take_tickets(const char *mem, uint32_t count) {
-    std::lock_guard<std::mutex> lock(g_hist_clean_mutex);
-    for (int i = 0; i < g_sync_used; ++i)
-        if (g_sync[i].mem == mem) { const uint32_t base = g_sync[i].pf_tickets; g_sync[i].pf_tickets = base + count; return base; }
-    return 0u;
 }
 
 int check_search_args(const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm,
@@ -836,11 +770,12 @@ int check_search_args(const float *db, int64_t n, const float *q, int nq, int k,
 
 // The opening of the four fp32 entry points: argument check, the plan of the call, workspace check.  out_scores / out_idx are
 // looked at where the stage writes results (ms_ip_topk, ms_ip_topk_finish -- which takes no rows or queries and checks its own few)
-enum Stage { WHOLE, PREPARE, SCAN, FINISH };
+// Stage: the values are bits (pf_run tests them).  PREPARE = queries + sample pass + bound, SCAN = the scan launch, FINISH = the merge
+// (prefiltered: + exact re-scoring + the exact pass over the queries whose proof failed)
+enum Stage { PREPARE = 1, SCAN = 2, FINISH = 4, WHOLE = 7 };
 int open_search(Stage stage, const float *db, int64_t n, const float *q, int nq, int k, int mode, const float *inv_norm, const float *lengths,
                 const float *qlen, const float *out_scores, const int64_t *out_idx, const void *workspace, size_t workspace_bytes, ScanPlan *pl) {
-    static const char *const names[] = {"ms_ip_topk", "ms_ip_topk_prepare", "ms_ip_topk_scan", "ms_ip_topk_finish"};
-    const char *who = names[stage];
+    const char *who = stage == WHOLE ? "ms_ip_topk" : stage == PREPARE ? "ms_ip_topk_prepare" : stage == SCAN ? "ms_ip_topk_scan" : "ms_ip_topk_finish";
     if (stage == FINISH) {
         if (k < 1 || k > 64 || nq < 1 || out_scores == nullptr || out_idx == nullptr) MS_FAIL(MS_ERR_ARG, "%s: bad arguments", who);
     } else {
@@ -973,7 +908,7 @@ void attach_prepass_results(const ScanPlan &pl, char *ws, ScanParams *sp, bool h
 // The counters must start at zero for EVERY scan (a second scan after one prepare would otherwise count rows twice): a staged scan
 // that does not directly follow its prepare zeroes them itself
 int zero_hist_unless_clean(const ScanPlan &pl, const ScanParams &sp, const void *workspace, int64_t n, int nq, int k, hipStream_t st) {
-    if (sp.hist != nullptr && !hist_take_clean(workspace, n, nq, k))
+    if (sp.hist != nullptr && !ms_wsstate::take_clean(workspace, n, nq, k))
         MS_HIP_CHECK(hipMemsetAsync(sp.hist, 0, (size_t)pl.d.nq_pad * 16 * sizeof(uint32_t), st));
     return MS_OK;
 }
@@ -1127,7 +1062,7 @@ int ms_ip_topk_prepare(const float *db, int64_t n, const float *q, int nq, int k
     rc = prepare_scan(pl, db, n, q, nq, mode, inv_norm, lengths, qlen, mincov, (char *)workspace, (hipStream_t)stream, &sp);
     if (rc) return rc;
     rc = run_prepass(pl, &sp, nq, (char *)workspace, (hipStream_t)stream);
-    if (rc == MS_OK && sp.hist != nullptr) hist_mark_clean(workspace, n, nq, k);      // (ms_sample_bound_kernel zeroed the counters)
+    if (rc == MS_OK && sp.hist != nullptr) ms_wsstate::mark_clean(workspace, n, nq, k);      // (ms_sample_bound_kernel zeroed the counters)
     return rc;
 }
 
@@ -1171,10 +1106,10 @@ int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, i
     if (rc) return rc;
     rc = run_prepass(pl, &sp, nq, ws, st);
     if (rc) return rc;
-    hist_invalidate(workspace);     // (a staged ms_ip_topk_scan on this workspace must not take the counters for clean afterwards)
+    ms_wsstate::invalidate(workspace);     // (a staged ms_ip_topk_scan on this workspace must not take the counters for clean afterwards)
     // a handful of queries, one pass: the scan launch merges its own lists (ms_scan_body, last workgroup of a query group)
     char *blk = (k <= 64 && pl.d.qwb < 4 && nq <= ms_settings().fused_merge_max_nq && merge_fits_scan_launch(pl.k_pass, pl.d.P))
-                    ? sync_block_for(ws) : nullptr;
+                    ? ms_wsstate::block(ws) : nullptr;
     if (blk != nullptr) {
         sp.fin_s = out_scores; sp.fin_i = out_idx; sp.fin_row_offset = row_offset; sp.fin_stride = k;
         sp.ticket = reinterpret_cast<uint32_t *>(blk);
@@ -1199,14 +1134,14 @@ int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, i
 }
 
 // ---- prefiltered search (>= 3 query tiles, k <= 48) -------------------------------------------------------------------
-// stages: 1 = queries + sample pass + bound, 2 = the scan launch, 4 = merge + exact re-scoring + the exact pass over the queries
-// whose proof failed
 namespace {
-uint32_t next_epoch() {                                // never 0: the gate word starts at zero
-    static std::atomic<uint32_t> e{1};
-    uint32_t v = e.fetch_add(1);
-    if (v == 0) v = e.fetch_add(1);
-    return v;
+// Stage `stage` of the fp32 path: what a prefiltered call runs for shapes the prefilter does not serve
+int fp32_stage(Stage stage, const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode, const float *lengths, const float *qlen,
+               float mincov, float *out_scores, int64_t *out_idx, void *workspace, size_t workspace_bytes, hipStream_t st) {
+    if (stage == PREPARE) return ms_ip_topk_prepare(db, n, q, nq, k, mode, nullptr, lengths, qlen, mincov, workspace, workspace_bytes, st);
+    if (stage == SCAN) return ms_ip_topk_scan(db, n, q, nq, k, mode, nullptr, lengths, qlen, mincov, workspace, workspace_bytes, st);
+    if (stage == FINISH) return ms_ip_topk_finish(n, row_offset, nq, k, out_scores, out_idx, workspace, workspace_bytes, st);
+    return ms_ip_topk(db, n, row_offset, q, nq, k, mode, nullptr, lengths, qlen, mincov, out_scores, out_idx, workspace, workspace_bytes, st);
 }
 bool pf_format_ok(int f) { return f == MS_PF_BF16X3 || f == MS_PF_F16X2 || f == MS_PF_F16X1; }
 float pf_err_coef(bool image, int format) {
@@ -1217,7 +1152,7 @@ float pf_err_coef(bool image, int format) {
 // ScanPlan::hist_on, which stage 1 goes by: the two differ over an image with MS_LOADER_WAVE=0 (diagnostics), as they always have.
 bool pf_staged_hist(const MsSettings &set) { return set.shared_bound != 0; }
 
-int pf_run(int stages, const float *db, const void *image, int format, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
+int pf_run(Stage stages, const float *db, const void *image, int format, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
            const float *lengths, const float *qlen, float mincov, float row_norm_bound, float *out_scores, int64_t *out_idx,
            void *workspace, size_t workspace_bytes, hipStream_t st) {
     int rc = check_search_args(db, n, q, nq, k, mode, nullptr, lengths, qlen);
@@ -1228,13 +1163,9 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
     const PfLayout L = pf_layout(set, cu_count_cached(), n, nq, k, mode, image != nullptr, format);
     if (workspace == nullptr || workspace_bytes < L.total)
         MS_FAIL(MS_ERR_WORKSPACE, "ms_ip_topk_prefiltered: workspace %zu < %zu bytes", workspace_bytes, L.total);
-    char *blk = L.ok && row_norm_bound > 0.0f && row_norm_bound < INFINITY ? sync_block_for(workspace) : nullptr;
-    if (blk == nullptr) {          // shapes the prefilter does not serve: the fp32 path, same stages
-        if (stages == 7) return ms_ip_topk(db, n, row_offset, q, nq, k, mode, nullptr, lengths, qlen, mincov, out_scores, out_idx, workspace, workspace_bytes, st);
-        if (stages == 1) return ms_ip_topk_prepare(db, n, q, nq, k, mode, nullptr, lengths, qlen, mincov, workspace, workspace_bytes, st);
-        if (stages == 2) return ms_ip_topk_scan(db, n, q, nq, k, mode, nullptr, lengths, qlen, mincov, workspace, workspace_bytes, st);
-        return ms_ip_topk_finish(n, row_offset, nq, k, out_scores, out_idx, workspace, workspace_bytes, st);
-    }
+    char *blk = L.ok && row_norm_bound > 0.0f && row_norm_bound < INFINITY ? ms_wsstate::block(workspace) : nullptr;
+    if (blk == nullptr)            // shapes the prefilter does not serve: the fp32 path, same stages
+        return fp32_stage(stages, db, n, row_offset, q, nq, k, mode, lengths, qlen, mincov, out_scores, out_idx, workspace, workspace_bytes, st);
     char *ws = (char *)workspace;
     const ScanPlan &pl = L.pf;
     const bool f16 = is_f16_image(image, format);
@@ -1244,41 +1175,40 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
     const float rawq_eps = (f16 && (mode == MS_MODE_IP_NORMQ || mode == MS_MODE_COSINE_UNIT) && ((uintptr_t)q & 15) == 0 && set.pf_rawq)
                                ? (mode == MS_MODE_IP_NORMQ ? 1e-12f : 1e-8f) : 0.0f;
     ScanParams sp;
-    if ((stages & 1) && rawq_eps == 0.0f) rc = prepare_scan(pl, db, n, q, nq, mode, nullptr, lengths, qlen, mincov, ws, st, &sp);
+    if ((stages & PREPARE) && rawq_eps == 0.0f) rc = prepare_scan(pl, db, n, q, nq, mode, nullptr, lengths, qlen, mincov, ws, st, &sp);
     else sp = fill_scan_params(pl, db, n, q, nq, nullptr, lengths, qlen, mincov, ws, mode);
     if (rc) return rc;
     if (rawq_eps > 0.0f) { sp.qn = q; sp.qnorm_eps = 0.0f; sp.qraw_eps = rawq_eps; }
     sp.prefilter = 1; sp.pf_image = image; sp.pf_format = format;
-    if (stages & 1) {
+    if (stages & PREPARE) {
         rc = run_prepass(pl, &sp, nq, ws, st);
         if (rc) return rc;
-        if (sp.hist != nullptr) hist_mark_clean(workspace, n, nq, L.kp);
-        if ((stages & 2) && sp.hist != nullptr) (void)hist_take_clean(workspace, n, nq, L.kp);
+        if (sp.hist != nullptr && (stages & SCAN)) ms_wsstate::invalidate(workspace);            // (the sample pass zeroed the counters: this call's scan uses
+        else if (sp.hist != nullptr) ms_wsstate::mark_clean(workspace, n, nq, L.kp);             //  them up, or they are clean for a staged one)
     } else {
         if (pl.prepass_tiles > 0) attach_prepass_results(pl, ws, &sp, pf_staged_hist(set));
-        if (stages & 2) rc = zero_hist_unless_clean(pl, sp, workspace, n, nq, L.kp, st);
+        if (stages & SCAN) rc = zero_hist_unless_clean(pl, sp, workspace, n, nq, L.kp, st);
         if (rc) return rc;
     }
     sp.debug_flags = set.pf_debug;
-    if (stages & 2) {
+    if (stages & SCAN) {
         if (f16 && pl.d.n_qgroups >= 2 && pl.d.n_qgroups <= 16 && set.pf_pace) {
             // several query groups walk every row stream: they pace each other through progress words (ms_scan_pf16.h) so that a tile
             // one of them fetched is still in the XCD's L2 when the others want it
-            static std::atomic<uint32_t> pace_epoch{1};
             sp.prog = pl.prog(ws);
-            sp.prog_epoch = pace_epoch.fetch_add(1) & 0xFFu;
+            sp.prog_epoch = ms_wsstate::next_pace_epoch(workspace);
         }
         rc = launch_scan(pl, sp, st);
         if (rc) return rc;
     }
-    if (stages & 4) {
+    if (stages & FINISH) {
         if (out_scores == nullptr || out_idx == nullptr) MS_FAIL(MS_ERR_ARG, "ms_ip_topk_prefiltered: NULL outputs");
-        uint32_t *gate = reinterpret_cast<uint32_t *>(blk + 256);
-        const uint32_t epoch = next_epoch();
+        uint32_t *gate = reinterpret_cast<uint32_t *>(blk + ms_wsstate::GATE_OFFSET);
+        const uint32_t epoch = ms_wsstate::next_gate_epoch(workspace);
         const ScanPlan &px = L.exact;
         PfCompact cp;
         cp.qn_c = L.qn_c(ws); cp.lb_c = L.lb_c(ws); cp.qlen_c = L.qlen_c(ws); cp.qmap = L.qmap(ws); cp.dp = L.dp(ws); cp.gate = gate; cp.epoch = epoch; cp.n = n;
-        cp.cus = cu_count_cached(); cp.nq = nq; cp.ticket_base = sync_take_tickets(blk, (uint32_t)nq);
+        cp.cus = cu_count_cached(); cp.nq = nq; cp.ticket_base = ms_wsstate::peek_tickets(workspace);
         // ONE launch: merge of the per-stream candidate lists (sparse; stream-major behind the image scans) + exact re-scoring + proof + compaction
         PfRescore ra;
         ra.db = db; ra.qn = sp.qn; ra.as = L.as(ws); ra.ai = L.ai(ws); ra.lengths = lengths; ra.qlen = qlen; ra.out_s = out_scores; ra.out_i = out_idx; ra.flag = L.flag(ws);
@@ -1292,6 +1222,7 @@ int pf_run(int stages, const float *db, const void *image, int format, int64_t n
         hipLaunchKernelGGL(ms_merge_rescore_kernel, dim3(nq), dim3(256), block_lds, st, sp.part_s, sp.part_i, pl.d.P, L.as(ws), L.ai(ws),
                            sp.list_sm ? (size_t)pl.d.nq_pad * L.kp : (size_t)0, ra);
         MS_LAUNCH_CHECK("ms_merge_rescore_kernel");
+        ms_wsstate::commit_tickets(workspace, (uint32_t)nq);       // (only now: a failing return above leaves the host's total where the device word is)
         // The exact pass, for the flagged queries ONLY (the reference's semantics are per query: dbsearch.py:234-242): an fp32 scan
         // and a merge over the compacted batch, decomposed on the device (ScanDevPlan), both returning at once when no query was
         // flagged.  No sample pass: the k-th best exact score among a query's candidates is already a lower bound on its k-th
@@ -1361,34 +1292,34 @@ int ms_ip_topk_prefiltered(const float *db, const void *pf_image, int pf_format,
                            const float *lengths, const float *qlen, float mincov, float row_norm_bound, float *out_scores,
                            int64_t *out_idx, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
     if (k > 64) return ms_ip_topk(db, n, row_offset, q, nq, k, mode, nullptr, lengths, qlen, mincov, out_scores, out_idx, workspace, workspace_bytes, stream);
-    return pf_run(7, db, pf_image, pf_format, n, row_offset, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, out_scores, out_idx, workspace,
+    return pf_run(WHOLE, db, pf_image, pf_format, n, row_offset, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, out_scores, out_idx, workspace,
                   workspace_bytes, (hipStream_t)stream);
 }
 int ms_ip_topk_prefiltered_prepare(const float *db, const void *pf_image, int pf_format, int64_t n, const float *q, int nq, int k, int mode,
                                    const float *lengths, const float *qlen, float mincov, float row_norm_bound, void *workspace,
                                    size_t workspace_bytes, ms_stream_t stream) {
-    return pf_run(1, db, pf_image, pf_format, n, 0, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, nullptr, nullptr, workspace, workspace_bytes,
+    return pf_run(PREPARE, db, pf_image, pf_format, n, 0, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, nullptr, nullptr, workspace, workspace_bytes,
                   (hipStream_t)stream);
 }
 int ms_ip_topk_prefiltered_scan(const float *db, const void *pf_image, int pf_format, int64_t n, const float *q, int nq, int k, int mode,
                                 const float *lengths, const float *qlen, float mincov, float row_norm_bound, void *workspace,
                                 size_t workspace_bytes, ms_stream_t stream) {
-    return pf_run(2, db, pf_image, pf_format, n, 0, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, nullptr, nullptr, workspace, workspace_bytes,
+    return pf_run(SCAN, db, pf_image, pf_format, n, 0, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, nullptr, nullptr, workspace, workspace_bytes,
                   (hipStream_t)stream);
 }
 int ms_ip_topk_prefiltered_finish(const float *db, const void *pf_image, int pf_format, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
                                   const float *lengths, const float *qlen, float mincov, float row_norm_bound, float *out_scores,
                                   int64_t *out_idx, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
-    return pf_run(4, db, pf_image, pf_format, n, row_offset, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, out_scores, out_idx, workspace,
+    return pf_run(FINISH, db, pf_image, pf_format, n, row_offset, q, nq, k, mode, lengths, qlen, mincov, row_norm_bound, out_scores, out_idx, workspace,
                   workspace_bytes, (hipStream_t)stream);
 }
 // Diagnostics for the tests (synchronises the device): the state the last prefiltered search on this workspace left behind --
 // *flagged = how many of its queries needed the exact pass (0: the prefilter proved every answer).
 int ms_debug_prefilter_state(void *workspace, unsigned int *gate_value, unsigned int *last_epoch, unsigned int *flagged) {
-    char *blk = sync_block_for(workspace);
+    char *blk = ms_wsstate::block(workspace);
     if (blk == nullptr || hipDeviceSynchronize() != hipSuccess) return -1;
     unsigned int w[3] = {0, 0, 0};
-    if (hipMemcpy(w, blk + 256, 12, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(w, blk + ms_wsstate::GATE_OFFSET, 12, hipMemcpyDeviceToHost) != hipSuccess) return -1;
     *gate_value = w[0]; *last_epoch = w[1]; *flagged = w[2];
     return 0;
 }
@@ -1397,10 +1328,10 @@ int ms_debug_prefilter_state(void *workspace, unsigned int *gate_value, unsigned
 // this workspace -- what an aborted launch, or a second stream on the same workspace, would leave behind.  The next prefiltered
 // search on the workspace must then fail loudly (the gated launch traps: ms_gate_closed), never answer.
 int ms_debug_prefilter_poison(void *workspace, unsigned int slot_counter, unsigned int ticket) {
-    char *blk = sync_block_for(workspace);
+    char *blk = ms_wsstate::block(workspace);
     if (blk == nullptr || hipDeviceSynchronize() != hipSuccess) return -1;
     const unsigned int w[2] = {slot_counter, ticket};
-    if (hipMemcpy(blk + 256 + 16, w, 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (hipMemcpy(blk + ms_wsstate::GATE_OFFSET + 16, w, 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
     return 0;
 }
 

@@ -243,6 +243,66 @@ def test_prefiltered_stages_equal_the_one_shot_call_and_repeat(image, torch_gpu)
         assert torch.equal(out[1], i0) and torch.equal(out[0].view(torch.int32), s0.view(torch.int32))
 
 
+@pytest.mark.parametrize("image", ["f16x1", None])
+def test_prefiltered_stages_of_two_workspaces_interleaved(image, torch_gpu):
+    """The host's books (clean counters, epochs, ticket total) are kept per workspace: the stages of two searches, each on its own
+    workspace, taken in turns -- and one of them scanned twice -- both equal the one-shot call."""
+    torch = torch_gpu
+    from merizo_search_amd import ops
+    n, nq, k, bound = 70_000, 96, 10, 1.0 + 1e-6
+    d = _dev(torch, _norm_db(n, seed=451))
+    img = _img(ops, d, image, bound)
+    qs = [_dev(torch, _norm_db(nq, seed=452 + j)) for j in range(2)]
+    wss = [ops.PrefilterWorkspace(d.device).get(n, nq, k) for _ in range(2)]
+    refs = [ops.ip_topk(d, dq, k) for dq in qs]
+    outs = [(torch.zeros_like(s), torch.zeros_like(i)) for s, i in refs]
+    A, B = 0, 1
+    for stage, j in [("prepare", A), ("prepare", B), ("scan", B), ("scan", A), ("scan", A), ("finish", A), ("finish", B)]:
+        ops.ip_topk_prefiltered_stage(stage, d, qs[j], k, wss[j], bound, out=outs[j], image=img)
+    for (s0, i0), (s, i), ws in zip(refs, outs, wss):
+        assert torch.equal(i, i0) and torch.equal(s.view(torch.int32), s0.view(torch.int32))
+        assert ops.prefilter_flagged(ws) == 0
+
+
+def test_more_workspaces_than_the_library_keeps_records_for(torch_gpu):
+    """The library keeps its per-workspace state (the block with the arrival counters, gate words and ticket; the ticket total; the
+    epochs) for a fixed number of workspaces (at most 128).  A prefiltered workspace whose record went to others in the meantime
+    starts over -- block, ticket total and epochs together -- and answers exactly, and so does every workspace on the way."""
+    torch = torch_gpu
+    from merizo_search_amd import ops
+    from oracle import oracle as orc
+    n, nq, k, bound = 70_000, 96, 10, 1.0 + 1e-6
+    db, q = _norm_db(n, seed=461), _norm_db(nq, seed=462)
+    d, dq = _dev(torch, db), _dev(torch, q)
+    img = _img(ops, d, "f16x1", bound)
+    P = ops.PrefilterWorkspace(d.device).get(n, nq, k)
+    s_ref, i_ref = orc.ip_topk(db, q, k, order=1)
+
+    def search_P():
+        s, i = ops.ip_topk_prefiltered(d, dq, k, bound, workspace=P, image=img)
+        assert np.array_equal(i.cpu().numpy(), i_ref) and np.array_equal(s.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
+
+    search_P()
+    # 160 workspaces of a few-query search that merges inside its scan launch: each takes a record with a block
+    m, mq = 777, 2
+    small, sq = _norm_db(m, seed=463), _norm_db(mq, seed=464)
+    d_small, d_sq = _dev(torch, small), _dev(torch, sq)
+    ss_ref, si_ref = orc.ip_topk(small, sq, k, order=1)
+    wss = [ops.TopKWorkspace(d.device).get(m, mq, k) for _ in range(160)]
+    assert len({w.data_ptr() for w in wss} | {P.data_ptr()}) == 161
+
+    def search_small(w):
+        s, i = ops.ip_topk(d_small, d_sq, k, workspace=w)
+        assert np.array_equal(i.cpu().numpy(), si_ref) and np.array_equal(s.cpu().numpy().view(np.uint32), ss_ref.view(np.uint32))
+
+    for w in wss:
+        search_small(w)
+    search_P()
+    search_P()
+    search_small(wss[0])
+    assert ops.prefilter_flagged(P) == 0
+
+
 def test_engine_uses_the_prefilter_for_large_batches_on_a_resident_database(torch_gpu):
     """foldclass/engine.py: ip_topk with a row-norm bound (what dbsearch_faiss passes for a resident shard) == without."""
     torch = torch_gpu

@@ -569,6 +569,29 @@ def test_staged_scan_twice_after_one_prepare_is_still_exact(torch_gpu):
         assert np.array_equal(out_i.cpu().numpy(), i_ref) and np.array_equal(out_s.cpu().numpy().view(np.uint32), s_ref.view(np.uint32))
 
 
+def test_staged_searches_of_two_workspaces_interleaved(torch_gpu):
+    """Whether the shared-bound counters are still clean is kept per workspace: the stages of two searches, each on its own
+    workspace, taken in turns -- and one of them scanned twice after its prepare -- both equal the one-shot call."""
+    torch = torch_gpu
+    from merizo_search_amd import ops
+    n, nq, k = 70_000, 64, 7
+    d = _dev(torch, _norm_db(n, seed=15))
+    qs = [_dev(torch, _norm_db(nq, seed=16 + j)) for j in range(2)]
+    wss = [ops.TopKWorkspace(d.device).get(n, nq, k) for _ in range(2)]
+    refs = [ops.ip_topk(d, dq, k) for dq in qs]
+    outs = [(torch.zeros_like(s), torch.zeros_like(i)) for s, i in refs]
+    A, B = 0, 1
+    ops.ip_topk_prepare(d, qs[A], k, wss[A])
+    ops.ip_topk_prepare(d, qs[B], k, wss[B])
+    ops.ip_topk_scan(d, qs[B], k, wss[B])
+    ops.ip_topk_scan(d, qs[A], k, wss[A])
+    ops.ip_topk_scan(d, qs[A], k, wss[A])
+    ops.ip_topk_finish(n, nq, k, wss[A], *outs[A])
+    ops.ip_topk_finish(n, nq, k, wss[B], *outs[B])
+    for (s0, i0), (s, i) in zip(refs, outs):
+        assert torch.equal(i, i0) and torch.equal(s.view(torch.int32), s0.view(torch.int32))
+
+
 @pytest.mark.parametrize("n,nq,k", [(1, 1, 1), (5000, 1, 10), (200_000, 3, 10), (1_000_000, 1, 10), (1_000_000, 8, 16), (300_000, 5, 1),
                                     (40, 2, 10), (777, 8, 10)])
 def test_few_queries_merge_inside_the_scan_launch(n, nq, k, torch_gpu):

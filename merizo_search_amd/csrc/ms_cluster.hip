@@ -20,6 +20,12 @@
 // ms_cluster_greedy_edges adds m directed entries held as three arrays (row i, row j, score) to the lists: the mark and the
 // assign step get a second launch over them, with i read instead of derived from the entry's place; ms_cluster_greedy is that
 // call with m == 0 -- the launches it always made, in their order.
+//
+// How the file is laid out: where a directed entry comes from is an ENTRY SOURCE (ms_cl_lists, ms_cl_edges), and every per-entry
+// step -- mark and assign here, hook and link of ms_cluster_components below -- is ONE kernel template over the source, launched
+// over the lists and then over the extras by MS_CL_LAUNCH_ENTRIES.  The three entry points share their argument checks
+// (ms_cl_check_args), the host loop over the rounds (ms_cl_rounds) and the read-back behind the finish launch (ms_cl_read_head).
+// Another way of reading the graph is another per-entry function.
 #include "ms_common.h"
 
 #define MS_CL_THREADS 256
@@ -32,9 +38,10 @@
 #define MS_CL_REP_NEW 2                // chosen by the last decide launch: covers its neighbours in the next mark launch
 #define MS_CL_REP 3
 
-struct ms_cl_head {                    // the first MS_CL_HEAD_BYTES of the workspace
-    uint32_t remaining[MS_CL_GROUP];   // rows still undecided after round (slot) of the current group
-    unsigned long long n_reps;
+struct ms_cl_head {                    // the first MS_CL_HEAD_BYTES of the workspace (both clusterings)
+    uint32_t word[MS_CL_GROUP];        // per round (slot) of the current group, 0 = it was the last: greedy: rows still undecided
+                                       // after it; components: it saw an entry between two trees
+    unsigned long long n_reps;         // representatives (components: as many as components)
     unsigned long long saturated;
 };
 
@@ -82,16 +89,46 @@ __device__ __forceinline__ unsigned long long ms_cl_key(float s, int64_t row) {
     return ((unsigned long long)b << 32) | (unsigned long long)(~(uint32_t)row);
 }
 
-// The entry a thread of a grid-stride pass works on: entry e = base + thread of the [n,k] lists, its row i (one 64-bit
-// division per workgroup and pass, a 32-bit one per thread).
+// A grid-stride pass over `total` entries: the thread works on entry e = base + thread.
 #define MS_CL_FOR_ENTRIES(total)                                                                                   \
     for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < (total); base += (int64_t)gridDim.x * MS_CL_THREADS)
 
+// The row i of entry base + thread of the [n,k] lists (one 64-bit division per workgroup and pass, a 32-bit one per thread).
 __device__ __forceinline__ int64_t ms_cl_entry_row(int64_t base, int k) {
     const int64_t row0 = base / k;
     const uint32_t local = (uint32_t)(base - row0 * k) + threadIdx.x;      // < k + 256
     return row0 + (int64_t)(local / (uint32_t)k);
 }
+
+// The two ENTRY SOURCES, passed to the per-entry kernels by value: entry e of total() is i -> dst[e] with score[e], and row(base) is
+// the i of the thread's entry e = base + thread, or -1: no such entry, or an i outside [0, n) -- nothing may be looked up with it.
+struct ms_cl_lists {                   // the [n,k] lists: i is DERIVED from the entry's place
+    const int64_t *__restrict__ dst;
+    const float *__restrict__ score;
+    int64_t n;
+    int k;
+    static constexpr bool owns_cut = true;                                 // an entry that is not valid sets cut[i]
+    __device__ __forceinline__ int64_t total() const { return n * (int64_t)k; }
+    __device__ __forceinline__ int64_t row(int64_t base) const {
+        const int64_t i = ms_cl_entry_row(base, k);
+        return i < n ? i : -1;
+    }
+};
+
+struct ms_cl_edges {                   // the m extra entries src[e] -> dst[e]: i is READ, and range-checked before it is used
+    const int64_t *__restrict__ src, *__restrict__ dst;
+    const float *__restrict__ score;
+    int64_t n, m;
+    static constexpr bool owns_cut = false;                                // (`cut`, and with it out_saturated, is the lists' alone:
+                                                                           // an extra entry that is not valid says nothing about a LIST)
+    __device__ __forceinline__ int64_t total() const { return m; }
+    __device__ __forceinline__ int64_t row(int64_t base) const {
+        const int64_t e = base + threadIdx.x;
+        if (e >= m) return -1;
+        const int64_t i = src[e];
+        return i >= 0 && i < n ? i : -1;
+    }
+};
 
 // The mark step of ONE directed entry i -> j with score s (i inside [0, n)): what the header comment calls push, pull and cover.
 __device__ __forceinline__ void ms_cl_mark_entry(int64_t i, const int64_t *__restrict__ jp, const float *__restrict__ sp, int64_t n,
@@ -115,34 +152,17 @@ __device__ __forceinline__ void ms_cl_mark_entry(int64_t i, const int64_t *__res
     }
 }
 
+// (The launch over the extra entries runs between a round's list launch and its decide launch; with k == 0 it is the round's only
+// mark launch, so it resets the count too: the same value, whichever launch stores it.)
+template <typename Src>
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_kernel(
-        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
+        const Src from, const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
         uint8_t *blocked, uint8_t *covered, uint32_t *remaining_slot) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *remaining_slot = 0u;         // (this round's decide launch counts into it)
-    const int64_t total = n * (int64_t)k;
-    MS_CL_FOR_ENTRIES(total) {
-        const int64_t i = ms_cl_entry_row(base, k);
-        if (i >= n) continue;
-        const int64_t e = base + threadIdx.x;
-        ms_cl_mark_entry(i, nbr_idx + e, nbr_score + e, n, lengths, min_score, mincov, status, blocked, covered);
-    }
-}
-
-// The same step over the m extra entries edge_src[e] -> edge_dst[e]: i is READ, and an entry whose i lies outside [0, n) is skipped
-// before anything is looked up with it.  (Launched between a round's list launch and its decide launch; with k == 0 it is the
-// round's only mark launch, so it resets the count too: the same value, whichever launch stores it.)
-__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_mark_edges_kernel(
-        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
-        uint8_t *blocked, uint8_t *covered, uint32_t *remaining_slot) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *remaining_slot = 0u;
-    MS_CL_FOR_ENTRIES(m) {
-        const int64_t e = base + threadIdx.x;
-        if (e >= m) continue;
-        const int64_t i = edge_src[e];
-        if (i < 0 || i >= n) continue;
-        ms_cl_mark_entry(i, edge_dst + e, edge_score + e, n, lengths, min_score, mincov, status, blocked, covered);
+    MS_CL_FOR_ENTRIES(from.total()) {
+        const int64_t i = from.row(base), e = base + threadIdx.x;
+        if (i < 0) continue;
+        ms_cl_mark_entry(i, from.dst + e, from.score + e, from.n, lengths, min_score, mincov, status, blocked, covered);
     }
 }
 
@@ -181,29 +201,14 @@ __device__ __forceinline__ bool ms_cl_assign_entry(int64_t i, int64_t j, float s
     return true;
 }
 
+template <typename Src>
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_kernel(
-        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
+        const Src from, const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status,
         unsigned long long *best, uint8_t *cut) {
-    const int64_t total = n * (int64_t)k;
-    MS_CL_FOR_ENTRIES(total) {
-        const int64_t i = ms_cl_entry_row(base, k);
-        if (i >= n) continue;
-        const int64_t e = base + threadIdx.x;
-        if (!ms_cl_assign_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, status, best)) cut[i] = 1;
-    }
-}
-
-// (An extra entry that is not valid says nothing about a LIST: `cut`, and with it out_saturated, is the lists' alone.)
-__global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_assign_edges_kernel(
-        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, const uint8_t *__restrict__ status, unsigned long long *best) {
-    MS_CL_FOR_ENTRIES(m) {
-        const int64_t e = base + threadIdx.x;
-        if (e >= m) continue;
-        const int64_t i = edge_src[e];
-        if (i < 0 || i >= n) continue;
-        ms_cl_assign_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, status, best);
+    MS_CL_FOR_ENTRIES(from.total()) {
+        const int64_t i = from.row(base), e = base + threadIdx.x;
+        if (i < 0) continue;
+        if (!ms_cl_assign_entry(i, from.dst[e], from.score[e], from.n, lengths, min_score, mincov, status, best) && Src::owns_cut) cut[i] = 1;
     }
 }
 
@@ -246,84 +251,131 @@ static inline unsigned ms_cl_blocks(int64_t items) {
     return (unsigned)(b < MS_CL_MAX_BLOCKS ? b : MS_CL_MAX_BLOCKS);
 }
 
-// Both entry points: the lists ([n,k], k >= 0) and the extra entries (m >= 0), `who` in the messages.
-static int ms_cl_run(const char *who, const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
-                     const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score, float mincov,
-                     int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps, int32_t *out_rounds, int64_t *out_saturated,
-                     void *workspace, size_t workspace_bytes, ms_stream_t stream) {
-    const size_t need = ms_cluster_workspace_bytes(n);
-    if (workspace_bytes < need)
-        MS_FAIL(MS_ERR_ARG, "%s: workspace of %zu bytes, ms_cluster_workspace_bytes(%lld) = %zu", who, workspace_bytes, (long long)n, need);
-    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
+// What all three entry points are handed: the lists ([n,k]; lists_only: k >= 1 and never NULL, else k >= 0), the extra entries
+// (m >= 0), the cuts, the outputs and the workspace.  The checks they all make, in one order, `who` in the messages.
+struct ms_cl_args {
+    ms_cl_lists lists;
+    ms_cl_edges edges;
+    const int32_t *lengths;
+    float min_score, mincov;
+    int64_t *out_rep;
+    float *out_score;
+    int64_t *out_count;
+    int32_t *out_rounds;
+    int64_t *out_saturated;
+    void *workspace;
+    size_t workspace_bytes;
+};
 
-    hipStream_t st = (hipStream_t)stream;
-    const ms_cl_view v = ms_cl_carve(workspace, n);
-    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), edge_blocks = ms_cl_blocks(m), row_blocks = ms_cl_blocks(n);
-    MS_HIP_CHECK(hipMemsetAsync(workspace, 0, need, st));                  // every row undecided, no flag, no key, counters 0
+static int ms_cl_check_args(const char *who, bool lists_only, const ms_cl_args &a, size_t (*ws_bytes)(int64_t), const char *ws_bytes_name) {
+    const ms_cl_lists &l = a.lists;
+    const ms_cl_edges &e = a.edges;
+    if (!lists_only && (l.k < 0 || e.m < 0)) MS_FAIL(MS_ERR_ARG, "%s: need k >= 0 and m >= 0 (k=%d m=%lld)", who, l.k, (long long)e.m);
+    if (((lists_only || l.k > 0) && (!l.dst || !l.score)) || (e.m > 0 && (!e.src || !e.dst || !e.score)) || !a.lengths ||
+        !a.out_rep || !a.out_score || !a.out_count || !a.out_rounds || !a.out_saturated || !a.workspace)
+        MS_FAIL(MS_ERR_ARG, "%s: NULL pointer", who);
+    if (l.n < 1 || l.n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "%s: need 1 <= n <= 2^31 - 1 (n=%lld)", who, (long long)l.n);
+    if (lists_only && l.k < 1) MS_FAIL(MS_ERR_ARG, "%s: need k >= 1 (k=%d)", who, l.k);
+    if (a.min_score != a.min_score) MS_FAIL(MS_ERR_ARG, "%s: min_score is NaN (-inf: no cut)", who);
+    if (!(a.mincov >= 0.0f && a.mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "%s: mincov must lie in [0, 1]", who);
+    const size_t need = ws_bytes(l.n);
+    if (a.workspace_bytes < need)
+        MS_FAIL(MS_ERR_ARG, "%s: workspace of %zu bytes, %s(%lld) = %zu", who, a.workspace_bytes, ws_bytes_name, (long long)l.n, need);
+    if (((uintptr_t)a.workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "%s: workspace must be 16-byte aligned", who);
+    return MS_OK;
+}
 
-    int64_t rounds = 0;
+// One per-entry pass on stream ST: KERNEL over the lists of ms_cl_args A (k > 0), then over its extra entries (m > 0).  EMPTY_TOO:
+// with k == 0 the second launch is made whatever m, with one workgroup when m == 0 (the mark step: it resets the round's count).
+#define MS_CL_LAUNCH_ENTRIES(KERNEL, A, EMPTY_TOO, ST, ...)                                                                                \
+    do {                                                                                                                                   \
+        if ((A).lists.k > 0) {                                                                                                             \
+            hipLaunchKernelGGL(KERNEL<ms_cl_lists>, dim3(ms_cl_blocks((A).lists.n * (int64_t)(A).lists.k)), dim3(MS_CL_THREADS), 0, ST,   \
+                               (A).lists, __VA_ARGS__);                                                                                    \
+            MS_LAUNCH_CHECK(#KERNEL "<ms_cl_lists>");                                                                                     \
+        }                                                                                                                                  \
+        if ((A).edges.m > 0 || ((EMPTY_TOO) && (A).lists.k == 0)) {                                                                        \
+            hipLaunchKernelGGL(KERNEL<ms_cl_edges>, dim3((A).edges.m > 0 ? ms_cl_blocks((A).edges.m) : 1u), dim3(MS_CL_THREADS), 0, ST,   \
+                               (A).edges, __VA_ARGS__);                                                                                    \
+            MS_LAUNCH_CHECK(#KERNEL "<ms_cl_edges>");                                                                                     \
+        }                                                                                                                                  \
+    } while (0)
+
+// The rounds of a clustering.  round(g) enqueues one round whose launches leave head->word[g] zero when it was the last one needed;
+// MS_CL_GROUP of them go out between two looks at the words (one 16-byte read-back).  The first zero word ends it: `rounds` counts up
+// to that round (the rounds behind it in the group changed nothing).  Both clusterings need at most n rounds: stuck(last word,
+// rounds) makes the error of a call that is past them -- unreachable on sound memory.
+template <typename Round, typename Stuck>
+static int ms_cl_rounds(int64_t n, const ms_cl_head *head, hipStream_t st, int64_t &rounds, Round round, Stuck stuck) {
     for (bool done = false; !done;) {
         for (int g = 0; g < MS_CL_GROUP; ++g) {
-            if (k > 0) {
-                hipLaunchKernelGGL(ms_cluster_mark_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
-                                   min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
-                MS_LAUNCH_CHECK("ms_cluster_mark_kernel");
-            }
-            if (m > 0 || k == 0) {                                         // (k == 0 and m == 0: one workgroup that resets the count)
-                hipLaunchKernelGGL(ms_cluster_mark_edges_kernel, dim3(m > 0 ? edge_blocks : 1u), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst,
-                                   edge_score, m, n, lengths, min_score, mincov, v.status, v.blocked, v.covered, v.head->remaining + g);
-                MS_LAUNCH_CHECK("ms_cluster_mark_edges_kernel");
-            }
-            hipLaunchKernelGGL(ms_cluster_decide_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.blocked, v.covered,
-                               v.head->remaining + g);
-            MS_LAUNCH_CHECK("ms_cluster_decide_kernel");
+            const int rc = round(g);
+            if (rc) return rc;
         }
-        uint32_t remaining[MS_CL_GROUP];
-        MS_HIP_CHECK(hipMemcpyAsync(remaining, v.head->remaining, sizeof(remaining), hipMemcpyDeviceToHost, st));
+        uint32_t word[MS_CL_GROUP];
+        MS_HIP_CHECK(hipMemcpyAsync(word, head->word, sizeof(word), hipMemcpyDeviceToHost, st));
         MS_HIP_CHECK(hipStreamSynchronize(st));
         for (int g = 0; g < MS_CL_GROUP && !done; ++g) {
             ++rounds;
-            done = remaining[g] == 0u;                                     // (the rounds behind it in the group changed nothing)
+            done = word[g] == 0u;
         }
-        if (!done && rounds > n)                                           // every round decides a row: unreachable on sound memory
-            MS_FAIL(MS_ERR_HIP, "%s: %lld rows still undecided after %lld rounds", who, (long long)remaining[MS_CL_GROUP - 1],
-                    (long long)rounds);
+        if (!done && rounds > n) return stuck(word[MS_CL_GROUP - 1], rounds);
     }
-
-    if (k > 0) {
-        hipLaunchKernelGGL(ms_cluster_assign_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
-                           min_score, mincov, v.status, v.best, v.cut);
-        MS_LAUNCH_CHECK("ms_cluster_assign_kernel");
-    }
-    if (m > 0) {
-        hipLaunchKernelGGL(ms_cluster_assign_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score, m, n,
-                           lengths, min_score, mincov, v.status, v.best);
-        MS_LAUNCH_CHECK("ms_cluster_assign_edges_kernel");
-    }
-    hipLaunchKernelGGL(ms_cluster_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.best, v.cut, out_rep,
-                       out_rep_score, v.head);
-    MS_LAUNCH_CHECK("ms_cluster_finish_kernel");
-    ms_cl_head head;
-    MS_HIP_CHECK(hipMemcpyAsync(&head, v.head, sizeof(head), hipMemcpyDeviceToHost, st));
-    MS_HIP_CHECK(hipStreamSynchronize(st));
-    *out_n_reps = (int64_t)head.n_reps;
-    *out_saturated = k > 0 ? (int64_t)head.saturated : 0;                  // (no list, no full list)
-    *out_rounds = (int32_t)rounds;
     return MS_OK;
+}
+
+// Behind the finish launch: the head's counts and the rounds -> the call's scalar outputs.
+static int ms_cl_read_head(const ms_cl_head *dev, const ms_cl_args &a, int64_t rounds, hipStream_t st) {
+    ms_cl_head head;
+    MS_HIP_CHECK(hipMemcpyAsync(&head, dev, sizeof(head), hipMemcpyDeviceToHost, st));
+    MS_HIP_CHECK(hipStreamSynchronize(st));
+    *a.out_count = (int64_t)head.n_reps;
+    *a.out_saturated = a.lists.k > 0 ? (int64_t)head.saturated : 0;        // (no list, no full list)
+    *a.out_rounds = (int32_t)rounds;
+    return MS_OK;
+}
+
+// Both greedy entry points.
+static int ms_cl_run(const char *who, bool lists_only, const ms_cl_args &a, ms_stream_t stream) {
+    const int rc = ms_cl_check_args(who, lists_only, a, ms_cluster_workspace_bytes, "ms_cluster_workspace_bytes");
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = a.lists.n;
+    const ms_cl_view v = ms_cl_carve(a.workspace, n);
+    const unsigned row_blocks = ms_cl_blocks(n);
+    MS_HIP_CHECK(hipMemsetAsync(a.workspace, 0, ms_cluster_workspace_bytes(n), st));      // every row undecided, no flag, no key, counters 0
+
+    int64_t rounds = 0;
+    const int rr = ms_cl_rounds(
+            n, v.head, st, rounds,
+            [&](int g) -> int {
+                MS_CL_LAUNCH_ENTRIES(ms_cluster_mark_kernel, a, true, st, a.lengths, a.min_score, a.mincov, v.status, v.blocked, v.covered,
+                                     v.head->word + g);
+                hipLaunchKernelGGL(ms_cluster_decide_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.blocked, v.covered,
+                                   v.head->word + g);
+                MS_LAUNCH_CHECK("ms_cluster_decide_kernel");
+                return MS_OK;
+            },
+            [&](uint32_t last, int64_t r) -> int {                         // (every round decides a row)
+                MS_FAIL(MS_ERR_HIP, "%s: %lld rows still undecided after %lld rounds", who, (long long)last, (long long)r);
+            });
+    if (rr) return rr;
+
+    MS_CL_LAUNCH_ENTRIES(ms_cluster_assign_kernel, a, false, st, a.lengths, a.min_score, a.mincov, v.status, v.best, v.cut);
+    hipLaunchKernelGGL(ms_cluster_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.status, v.best, v.cut, a.out_rep,
+                       a.out_score, v.head);
+    MS_LAUNCH_CHECK("ms_cluster_finish_kernel");
+    return ms_cl_read_head(v.head, a, rounds, st);
 }
 
 extern "C" int ms_cluster_greedy(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int32_t *lengths,
                                  float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
                                  int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
                                  ms_stream_t stream) {
-    if (!nbr_idx || !nbr_score || !lengths || !out_rep || !out_rep_score || !out_n_reps || !out_rounds || !out_saturated || !workspace)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: NULL pointer");
-    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
-    if (k < 1) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: need k >= 1 (k=%d)", k);
-    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: min_score is NaN (-inf: no cut)");
-    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy: mincov must lie in [0, 1]");
-    return ms_cl_run("ms_cluster_greedy", nbr_idx, nbr_score, n, k, nullptr, nullptr, nullptr, 0, lengths, min_score, mincov, out_rep,
-                     out_rep_score, out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes, stream);
+    return ms_cl_run("ms_cluster_greedy", true,
+                     {{nbr_idx, nbr_score, n, k}, {nullptr, nullptr, nullptr, n, 0}, lengths, min_score, mincov, out_rep, out_rep_score,
+                      out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes},
+                     stream);
 }
 
 extern "C" int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
@@ -331,15 +383,10 @@ extern "C" int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_
                                        float min_score, float mincov, int64_t *out_rep, float *out_rep_score, int64_t *out_n_reps,
                                        int32_t *out_rounds, int64_t *out_saturated, void *workspace, size_t workspace_bytes,
                                        ms_stream_t stream) {
-    if (k < 0 || m < 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: need k >= 0 and m >= 0 (k=%d m=%lld)", k, (long long)m);
-    if ((k > 0 && (!nbr_idx || !nbr_score)) || (m > 0 && (!edge_src || !edge_dst || !edge_score)) || !lengths || !out_rep || !out_rep_score ||
-        !out_n_reps || !out_rounds || !out_saturated || !workspace)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: NULL pointer");
-    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
-    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: min_score is NaN (-inf: no cut)");
-    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_greedy_edges: mincov must lie in [0, 1]");
-    return ms_cl_run("ms_cluster_greedy_edges", nbr_idx, nbr_score, n, k, edge_src, edge_dst, edge_score, m, lengths, min_score, mincov,
-                     out_rep, out_rep_score, out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes, stream);
+    return ms_cl_run("ms_cluster_greedy_edges", false,
+                     {{nbr_idx, nbr_score, n, k}, {edge_src, edge_dst, edge_score, n, m}, lengths, min_score, mincov, out_rep, out_rep_score,
+                      out_n_reps, out_rounds, out_saturated, workspace, workspace_bytes},
+                     stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -368,14 +415,8 @@ extern "C" int ms_cluster_greedy_edges(const int64_t *nbr_idx, const float *nbr_
 // scratch.  (A first form kept 32-bit rows in parent[], hooked by row number and picked the representatives afterwards with an
 // atomicMax on best[root]: on a 1M-row graph whose largest component has 443k rows that pass alone took 5.0 ms, every row of the
 // component on one address; DESIGN.md has the trace.)
-struct ms_cc_head {                    // the first MS_CL_HEAD_BYTES of the workspace
-    uint32_t changed[MS_CL_GROUP];     // round (slot) of the current group saw an entry between two trees
-    unsigned long long n_components;
-    unsigned long long saturated;
-};
-
 struct ms_cc_view {
-    ms_cc_head *head;
+    ms_cl_head *head;                  // word[]: the rounds' `changed` words
     unsigned long long *parent;        // [n] priority key of the row's parent
     uint32_t *link;                    // [n] order-preserving bits of the row's largest incident weight (0: none)
     uint8_t *cut;                      // [n] the row's list holds an entry that is not valid
@@ -386,7 +427,7 @@ static inline size_t ms_cc_words_bytes(int64_t n) { return ms_align_up(4 * (size
 static inline ms_cc_view ms_cc_carve(void *workspace, int64_t n) {
     char *p = (char *)workspace;
     ms_cc_view v;
-    v.head = (ms_cc_head *)p;
+    v.head = (ms_cl_head *)p;
     v.parent = (unsigned long long *)(p + MS_CL_HEAD_BYTES);
     v.link = (uint32_t *)(p + MS_CL_HEAD_BYTES + 8 * (size_t)n);
     v.cut = (uint8_t *)v.link + ms_cc_words_bytes(n);
@@ -434,28 +475,13 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_components_init_kernel(int64
     }
 }
 
+template <typename Src>
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_components_hook_kernel(
-        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, unsigned long long *parent, uint32_t *changed_slot) {
-    const int64_t total = n * (int64_t)k;
-    MS_CL_FOR_ENTRIES(total) {
-        const int64_t i = ms_cl_entry_row(base, k);
-        const int64_t e = base + threadIdx.x;
-        const bool saw = i < n && ms_cc_hook_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, parent);
-        if (__ballot(saw) && (threadIdx.x & 63) == 0) *changed_slot = 1u;  // (the value 1 from every wave that stores)
-    }
-}
-
-__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_hook_edges_kernel(
-        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, unsigned long long *parent, uint32_t *changed_slot) {
-    MS_CL_FOR_ENTRIES(m) {
-        const int64_t e = base + threadIdx.x;
-        bool saw = false;
-        if (e < m) {
-            const int64_t i = edge_src[e];
-            if (i >= 0 && i < n) saw = ms_cc_hook_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, parent);
-        }
+        const Src from, const int32_t *__restrict__ lengths, float min_score, float mincov, unsigned long long *parent, uint32_t *changed_slot) {
+    MS_CL_FOR_ENTRIES(from.total()) {
+        const int64_t i = from.row(base), e = base + threadIdx.x;
+        const bool saw = i >= 0 && ms_cc_hook_entry(i, from.dst[e], from.score[e], from.n, lengths, min_score, mincov, parent);
+        // (the ballot is every lane's, the ones without an entry too; the value 1 from every wave that stores)
         if (__ballot(saw) && (threadIdx.x & 63) == 0) *changed_slot = 1u;
     }
 }
@@ -482,33 +508,19 @@ __device__ __forceinline__ bool ms_cc_link_entry(int64_t i, int64_t j, float s, 
     return true;
 }
 
+template <typename Src>
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_components_link_kernel(
-        const int64_t *__restrict__ nbr_idx, const float *__restrict__ nbr_score, int64_t n, int k,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, uint32_t *link, uint8_t *cut) {
-    const int64_t total = n * (int64_t)k;
-    MS_CL_FOR_ENTRIES(total) {
-        const int64_t i = ms_cl_entry_row(base, k);
-        if (i >= n) continue;
-        const int64_t e = base + threadIdx.x;
-        if (!ms_cc_link_entry(i, nbr_idx[e], nbr_score[e], n, lengths, min_score, mincov, link)) cut[i] = 1;
-    }
-}
-
-__global__ __launch_bounds__(MS_CL_THREADS) void ms_components_link_edges_kernel(
-        const int64_t *__restrict__ edge_src, const int64_t *__restrict__ edge_dst, const float *__restrict__ edge_score, int64_t m, int64_t n,
-        const int32_t *__restrict__ lengths, float min_score, float mincov, uint32_t *link) {
-    MS_CL_FOR_ENTRIES(m) {
-        const int64_t e = base + threadIdx.x;
-        if (e >= m) continue;
-        const int64_t i = edge_src[e];
-        if (i < 0 || i >= n) continue;
-        ms_cc_link_entry(i, edge_dst[e], edge_score[e], n, lengths, min_score, mincov, link);
+        const Src from, const int32_t *__restrict__ lengths, float min_score, float mincov, uint32_t *link, uint8_t *cut) {
+    MS_CL_FOR_ENTRIES(from.total()) {
+        const int64_t i = from.row(base), e = base + threadIdx.x;
+        if (i < 0) continue;
+        if (!ms_cc_link_entry(i, from.dst[e], from.score[e], from.n, lengths, min_score, mincov, link) && Src::owns_cut) cut[i] = 1;
     }
 }
 
 __global__ __launch_bounds__(MS_CL_THREADS) void ms_components_finish_kernel(int64_t n, const unsigned long long *__restrict__ parent,
                                                                              const uint32_t *__restrict__ link, const uint8_t *__restrict__ cut,
-                                                                             int64_t *out_rep, float *out_link_score, ms_cc_head *head) {
+                                                                             int64_t *out_rep, float *out_link_score, ms_cl_head *head) {
     for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < n; base += (int64_t)gridDim.x * MS_CL_THREADS) {
         const int64_t i = base + threadIdx.x;
         bool rep = false, full = false;
@@ -522,7 +534,7 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_components_finish_kernel(int
         }
         const unsigned long long mr = __ballot(rep), mf = __ballot(full);
         if ((threadIdx.x & 63) == 0) {
-            if (mr) atomicAdd(&head->n_components, (unsigned long long)__popcll(mr));
+            if (mr) atomicAdd(&head->n_reps, (unsigned long long)__popcll(mr));
             if (mf) atomicAdd(&head->saturated, (unsigned long long)__popcll(mf));
         }
     }
@@ -537,72 +549,36 @@ extern "C" int ms_cluster_components(const int64_t *nbr_idx, const float *nbr_sc
                                      const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
                                      float mincov, int64_t *out_rep, float *out_link_score, int64_t *out_n_components, int32_t *out_rounds,
                                      int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
-    if (k < 0 || m < 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: need k >= 0 and m >= 0 (k=%d m=%lld)", k, (long long)m);
-    if ((k > 0 && (!nbr_idx || !nbr_score)) || (m > 0 && (!edge_src || !edge_dst || !edge_score)) || !lengths || !out_rep || !out_link_score ||
-        !out_n_components || !out_rounds || !out_saturated || !workspace)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_components: NULL pointer");
-    if (n < 1 || n > 2147483647LL) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: need 1 <= n <= 2^31 - 1 (n=%lld)", (long long)n);
-    if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: min_score is NaN (-inf: no cut)");
-    if (!(mincov >= 0.0f && mincov <= 1.0f)) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: mincov must lie in [0, 1]");
-    const size_t need = ms_cluster_components_workspace_bytes(n);
-    if (workspace_bytes < need)
-        MS_FAIL(MS_ERR_ARG, "ms_cluster_components: workspace of %zu bytes, ms_cluster_components_workspace_bytes(%lld) = %zu", workspace_bytes,
-                (long long)n, need);
-    if (((uintptr_t)workspace & 15u) != 0) MS_FAIL(MS_ERR_ARG, "ms_cluster_components: workspace must be 16-byte aligned");
-
+    const ms_cl_args a = {{nbr_idx, nbr_score, n, k}, {edge_src, edge_dst, edge_score, n, m}, lengths, min_score, mincov, out_rep, out_link_score,
+                          out_n_components, out_rounds, out_saturated, workspace, workspace_bytes};
+    const int rc = ms_cl_check_args("ms_cluster_components", false, a, ms_cluster_components_workspace_bytes, "ms_cluster_components_workspace_bytes");
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const ms_cc_view v = ms_cc_carve(workspace, n);
-    const unsigned entry_blocks = ms_cl_blocks(n * (int64_t)k), edge_blocks = ms_cl_blocks(m), row_blocks = ms_cl_blocks(n);
-    MS_HIP_CHECK(hipMemsetAsync(workspace, 0, need, st));                  // no link, no flag, counters 0
+    const unsigned row_blocks = ms_cl_blocks(n);
+    MS_HIP_CHECK(hipMemsetAsync(workspace, 0, ms_cluster_components_workspace_bytes(n), st));      // no link, no flag, counters 0
     hipLaunchKernelGGL(ms_components_init_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, lengths, v.parent);
     MS_LAUNCH_CHECK("ms_components_init_kernel");
 
     int64_t rounds = 0;
-    for (bool done = false; !done;) {
-        if (rounds > 0) MS_HIP_CHECK(hipMemsetAsync(v.head->changed, 0, sizeof(v.head->changed), st));
-        for (int g = 0; g < MS_CL_GROUP; ++g) {
-            if (k > 0) {
-                hipLaunchKernelGGL(ms_components_hook_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths,
-                                   min_score, mincov, v.parent, v.head->changed + g);
-                MS_LAUNCH_CHECK("ms_components_hook_kernel");
-            }
-            if (m > 0) {
-                hipLaunchKernelGGL(ms_components_hook_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score,
-                                   m, n, lengths, min_score, mincov, v.parent, v.head->changed + g);
-                MS_LAUNCH_CHECK("ms_components_hook_edges_kernel");
-            }
-            hipLaunchKernelGGL(ms_components_compress_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.parent);
-            MS_LAUNCH_CHECK("ms_components_compress_kernel");
-        }
-        uint32_t changed[MS_CL_GROUP];
-        MS_HIP_CHECK(hipMemcpyAsync(changed, v.head->changed, sizeof(changed), hipMemcpyDeviceToHost, st));
-        MS_HIP_CHECK(hipStreamSynchronize(st));
-        for (int g = 0; g < MS_CL_GROUP && !done; ++g) {
-            ++rounds;
-            done = changed[g] == 0u;                                       // (the rounds behind it in the group changed nothing)
-        }
-        if (!done && rounds > n)                                           // every such round took a root away: unreachable on sound memory
-            MS_FAIL(MS_ERR_HIP, "ms_cluster_components: trees still merging after %lld rounds", (long long)rounds);
-    }
+    const int rr = ms_cl_rounds(
+            n, v.head, st, rounds,
+            [&](int g) -> int {
+                // (no launch of a round resets its word, as the greedy mark launch does: a memset per group behind the first)
+                if (g == 0 && rounds > 0) MS_HIP_CHECK(hipMemsetAsync(v.head->word, 0, sizeof(v.head->word), st));
+                MS_CL_LAUNCH_ENTRIES(ms_components_hook_kernel, a, false, st, lengths, min_score, mincov, v.parent, v.head->word + g);
+                hipLaunchKernelGGL(ms_components_compress_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.parent);
+                MS_LAUNCH_CHECK("ms_components_compress_kernel");
+                return MS_OK;
+            },
+            [&](uint32_t, int64_t r) -> int {                              // (every round that saw two trees took a root away)
+                MS_FAIL(MS_ERR_HIP, "ms_cluster_components: trees still merging after %lld rounds", (long long)r);
+            });
+    if (rr) return rr;
 
-    if (k > 0) {
-        hipLaunchKernelGGL(ms_components_link_kernel, dim3(entry_blocks), dim3(MS_CL_THREADS), 0, st, nbr_idx, nbr_score, n, k, lengths, min_score,
-                           mincov, v.link, v.cut);
-        MS_LAUNCH_CHECK("ms_components_link_kernel");
-    }
-    if (m > 0) {
-        hipLaunchKernelGGL(ms_components_link_edges_kernel, dim3(edge_blocks), dim3(MS_CL_THREADS), 0, st, edge_src, edge_dst, edge_score, m, n,
-                           lengths, min_score, mincov, v.link);
-        MS_LAUNCH_CHECK("ms_components_link_edges_kernel");
-    }
+    MS_CL_LAUNCH_ENTRIES(ms_components_link_kernel, a, false, st, lengths, min_score, mincov, v.link, v.cut);
     hipLaunchKernelGGL(ms_components_finish_kernel, dim3(row_blocks), dim3(MS_CL_THREADS), 0, st, n, v.parent, v.link, v.cut, out_rep,
                        out_link_score, v.head);
     MS_LAUNCH_CHECK("ms_components_finish_kernel");
-    ms_cc_head head;
-    MS_HIP_CHECK(hipMemcpyAsync(&head, v.head, sizeof(head), hipMemcpyDeviceToHost, st));
-    MS_HIP_CHECK(hipStreamSynchronize(st));
-    *out_n_components = (int64_t)head.n_components;
-    *out_saturated = k > 0 ? (int64_t)head.saturated : 0;                  // (no list, no full list)
-    *out_rounds = (int32_t)rounds;
-    return MS_OK;
+    return ms_cl_read_head(v.head, a, rounds, st);
 }

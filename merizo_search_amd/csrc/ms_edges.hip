@@ -2,7 +2,8 @@
 // (query, global row, score) -- what `cluster --complete` asks for the rows whose neighbour lists came back full (DESIGN.md
 // section 5.8).  The definition is the header's; the score is ms_ip_topk's for that query and row, bit for bit.
 //
-// Route: ms_md_chain_scan_mq's, without the chain logic (its header comment derives the error bound E and the threshold).  A
+// Route: ms_md_chain_scan_mq's, without the chain logic (its header comment derives the error bound E and the threshold; the
+// filter loop is the one both kernels call, ms_mq_cells of ms_mq.h; this file keeps the list's encoding and the drain).  A
 // workgroup of 4 waves takes tiles of 64 rows, grid-stride: the tile is staged as fp32 in LDS (ms_mq_stage), each wave converts
 // it to its two 32-row fp16 A operands in registers and keeps them for its query tiles (wave w: tiles w, w + 4, ... of 32
 // queries), 2 x 8 v_mfma_f32_32x32x16_f16 per query tile, every accumulator compared with
@@ -95,67 +96,16 @@ __global__ __launch_bounds__(256, 2) void ms_threshold_edges_kernel(
         const int nrows = (int)min((int64_t)MS_MDS_TILE, n - r0);
         ms_mq_stage(db, r0, nrows, nullptr, 0.0f, b2, tile, lim, rflag, tid);
         ms_mq_convert(tile, rflag, rscale, r, h, af);
-        // the B operand and threshold of query tile qt: requested one tile ahead (an L2 round trip per tile otherwise)
-        f16x8 bn[8];
-        float thn = INFINITY;
-        auto request = [&](int qt) __attribute__((always_inline)) {
-            const int q = 32 * qt + r;
-            const f16x8 *bsrc = reinterpret_cast<const f16x8 *>(qh + (size_t)q * MS_DIM + 64 * h);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) bn[b] = bsrc[b];
-            thn = thr[q];
-        };
-        if (wave < nqt) request(wave);
-        for (int qt = wave; qt < nqt; qt += 4) {
-            const int q = 32 * qt + r;
-            f16x8 bq[8];
-#pragma unroll
-            for (int b = 0; b < 8; ++b) bq[b] = bn[b];
-            const float th = thn;
-            if (qt + 4 < nqt) request(qt + 4);
-            f32x16 o0 = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, o1 = o0;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][b], bq[b], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][b], bq[b], o1, 0, 0, 0);
-            }
-            // register 4 g + j of half hf: row 32 hf + 8 g + 4 h + j, query r.  PROVED BELOW THE CUT iff a < th (never for a NaN a).
-            bool open = false;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) open = open || !(o0[i] < th) || !(o1[i] < th);
-            if (__ballot(open) == 0ull) continue;
-            uint32_t regs = 0u;                                                  // registers with an unproved cell (uniform)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                regs |= (__ballot(!(o0[i] < th)) != 0ull ? 1u : 0u) << i;
-                regs |= (__ballot(!(o1[i] < th)) != 0ull ? 1u : 0u) << (16 + i);
-            }
-#pragma unroll 1
-            while (regs != 0u) {
-                const int i = __builtin_ctz(regs);
-                regs &= regs - 1u;
-                const float a = ms_mq_select(o0, o1, i);
-                const int row = 32 * (i >> 4) + 8 * ((i & 15) >> 2) + 4 * h + (i & 3);
-                const bool pass = !(a < th) && row < nrows && q < nq;
-                const ms_u64 pm = __ballot(pass);
-                if (pass) list[cnt + __popcll(pm & ms_mds_low_bits(lane))] = make_uint2((uint32_t)q, (uint32_t)row);
-                cnt += __popcll(pm);
-                if (cnt > MS_MQ_LIST - 64) drain();
-            }
-        }
-        drain();
+        ms_mq_cells(af, qh, thr, 0, nqt, nrows, nq, wave, lane, cnt,
+                    [&](int slot, int ql, int row) __attribute__((always_inline)) { list[slot] = make_uint2((uint32_t)ql, (uint32_t)row); }, drain);
     }
-    // the re-score count: one add per wave
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nresc += __shfl_xor(nresc, off);
-    if (lane == 0 && nresc != 0u) atomicAdd(&ctl[2], (ms_u64)nresc);
+    ms_mq_count_rescored(nresc, lane, ctl);
 }
 
-// workspace: prepared queries [nq_pad][128] fp32 | their fp16 operands [nq_pad][128] | thresholds [nq_pad] | ctl [4]
+// workspace: ms_mq_ws (prepared queries | their fp16 operands | thresholds) | ctl [4]
 extern "C" size_t ms_threshold_edges_workspace_bytes(int64_t n, int nq) {
     if (nq < 1 || n < 0 || nq > 0x7FFFFFE0) return 0;
-    const size_t nq_pad = (size_t)ms_mq_pad(nq);
-    return nq_pad * MS_DIM * (sizeof(float) + sizeof(_Float16)) + ms_align_up(nq_pad * sizeof(float), 16) + 4 * sizeof(ms_u64);
+    return ms_mq_ws_bytes((size_t)ms_mq_pad(nq)) + 4 * sizeof(ms_u64);
 }
 
 extern "C" int ms_threshold_edges(const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int mode, const int64_t *lo,
@@ -171,33 +121,26 @@ extern "C" int ms_threshold_edges(const float *db, int64_t n, int64_t row_offset
     if ((lo == nullptr) != (hi == nullptr)) MS_FAIL(MS_ERR_ARG, "ms_threshold_edges: lo and hi go together");
     if (min_score != min_score) MS_FAIL(MS_ERR_ARG, "ms_threshold_edges: min_score is NaN (-inf: no cut)");
     if ((((uintptr_t)db | (uintptr_t)workspace) & 15u) != 0) MS_FAIL(MS_ERR_ARG, "ms_threshold_edges: db and workspace must be 16-byte aligned");
-    if (!ms_mq_bound_ok(row_norm_bound))
-        MS_FAIL(MS_ERR_RANGE, "ms_threshold_edges: the fp16 operands need a row-norm bound in [2^-40, 2^40] (got %g)", (double)row_norm_bound);
+    MS_MQ_CHECK_BOUND("ms_threshold_edges");
     if (n > 2147483647LL) MS_FAIL(MS_ERR_RANGE, "ms_threshold_edges: at most 2^31 - 1 rows per call (n=%lld)", (long long)n);
     const size_t need = ms_threshold_edges_workspace_bytes(n, nq);
     if (need == 0 || workspace_bytes < need) MS_FAIL(MS_ERR_WORKSPACE, "ms_threshold_edges: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const int nq_pad = ms_mq_pad(nq);
-    float *qn = (float *)workspace;
-    _Float16 *qh = (_Float16 *)(qn + (size_t)nq_pad * MS_DIM);
-    float *thr = (float *)(qh + (size_t)nq_pad * MS_DIM);
-    ms_u64 *ctl = (ms_u64 *)((char *)thr + ms_align_up((size_t)nq_pad * sizeof(float), 16));
+    const ms_mq_params p = ms_mq_derive(row_norm_bound);
+    const ms_mq_ws w = ms_mq_carve(workspace, nq_pad);
+    ms_u64 *ctl = (ms_u64 *)w.tail;
     // ctl[0] the slot counter, ctl[1] always 0 here (the chain scans' table status), ctl[2] the re-score count: all reset by the call
     hipLaunchKernelGGL(ms_md_scan_setup_kernel, dim3(1), dim3(256), 0, st, (const int32_t *)nullptr, 0, nq, (int32_t *)nullptr, ctl);
     MS_LAUNCH_CHECK("ms_md_scan_setup_kernel");
     const bool work = n > 0;
-    if (work) {
-        const int rc = ms_launch_prepare_queries(q, nq, nq_pad, mode, qn, st);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(ms_md_scan_mq_prep_kernel, dim3((unsigned)(work ? (nq_pad + 255) / 256 : 1)), dim3(256), 0, st, qn, nq, work ? nq_pad : 0,
-                       min_score, ms_mq_eb(row_norm_bound), ms_mq_sr(row_norm_bound), qh, thr, ctl);
-    MS_LAUNCH_CHECK("ms_md_scan_mq_prep_kernel");
+    const int rc = ms_mq_launch_operands(q, nq, nq_pad, mode, work, min_score, p, w, ctl, st);
+    if (rc) return rc;
     if (work) {
         const int64_t ntiles = (n + MS_MDS_TILE - 1) / MS_MDS_TILE;
         const unsigned grid = (unsigned)(ntiles < MS_MDS_MAX_GRID ? ntiles : MS_MDS_MAX_GRID);
-        hipLaunchKernelGGL(ms_threshold_edges_kernel, dim3(grid), dim3(256), 0, st, db, n, row_offset, qn, qh, thr, nq, nq_pad, lo, hi,
-                           min_score, ms_mq_b2(row_norm_bound), ldexpf(1.0f, ms_mq_sr(row_norm_bound)), out_src, out_dst, out_score, cap, ctl);
+        hipLaunchKernelGGL(ms_threshold_edges_kernel, dim3(grid), dim3(256), 0, st, db, n, row_offset, w.qn, w.qh, w.thr, nq, nq_pad, lo, hi,
+                           min_score, p.b2, p.rscale, out_src, out_dst, out_score, cap, ctl);
         MS_LAUNCH_CHECK("ms_threshold_edges_kernel");
     }
     hipLaunchKernelGGL(ms_md_scan_finish_kernel, dim3(1), dim3(1), 0, st, ctl, out_count, out_stats);

@@ -42,7 +42,8 @@
 // by the stride, and as nqd <= 64 the chain ends inside it.  nq and nqc are not limited.
 // LDS: 76.6 KB per workgroup (two workgroups share a CU).  Vector stores only; LDS atomics; per wave one global atomic per emission
 // and one for the re-score count at its end.  No scratch.
-#include "ms_mq.h"                           // the operands, the staged tile, the exact cell: shared with ms_edges.hip
+#include "ms_mq.h"                           // the operands, the staged tile, the filter loop (ms_mq_cells), the exact cell and the
+                                             // host's parameters, workspace front and operand launches: shared with ms_edges.hip
 
 #define MS_MQ_QSTEP 4096                     // q0 / MS_MQ_QSTEP = the block that serves a query chain
 #define MS_MQ_QB (MS_MQ_QSTEP + 64)          // queries per block: 130 tiles of 32
@@ -105,55 +106,8 @@ __global__ __launch_bounds__(256, 2) void ms_md_chain_scan_mq_kernel(
     // every query tile of the block against the staged tile of nrows rows
     auto cells = [&](int nrows) __attribute__((always_inline)) {
         const int nqt = min(MS_MQ_QB / 32, (nq_pad - qb0) / 32);
-        // the B operand and threshold of query tile t: requested one tile ahead (an L2 round trip per tile otherwise)
-        f16x8 bn[8];
-        float thn = INFINITY;
-        auto request = [&](int t) __attribute__((always_inline)) {
-            const int qn_ = qb0 + 32 * t + r;
-            const f16x8 *bsrc = reinterpret_cast<const f16x8 *>(qh + (size_t)qn_ * MS_DIM + 64 * h);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) bn[b] = bsrc[b];
-            thn = thr[qn_];
-        };
-        if (wave < nqt) request(wave);
-        for (int qt = wave; qt < nqt; qt += 4) {
-            const int ql = 32 * qt + r, q = qb0 + ql;
-            f16x8 bq[8];
-#pragma unroll
-            for (int b = 0; b < 8; ++b) bq[b] = bn[b];
-            const float th = thn;
-            if (qt + 4 < nqt) request(qt + 4);
-            f32x16 o0 = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, o1 = o0;
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][b], bq[b], o0, 0, 0, 0);
-                o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][b], bq[b], o1, 0, 0, 0);
-            }
-            // register 4 g + j of half hf: row 32 hf + 8 g + 4 h + j, query r.  PROVED ZERO iff a < th (never for a NaN a).
-            bool open = false;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) open = open || !(o0[i] < th) || !(o1[i] < th);
-            if (__ballot(open) == 0ull) continue;
-            uint32_t regs = 0u;                                                  // registers with an unproved cell (uniform)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                regs |= (__ballot(!(o0[i] < th)) != 0ull ? 1u : 0u) << i;
-                regs |= (__ballot(!(o1[i] < th)) != 0ull ? 1u : 0u) << (16 + i);
-            }
-#pragma unroll 1
-            while (regs != 0u) {
-                const int i = __builtin_ctz(regs);
-                regs &= regs - 1u;
-                const float a = ms_mq_select(o0, o1, i);
-                const int row = 32 * (i >> 4) + 8 * ((i & 15) >> 2) + 4 * h + (i & 3);
-                const bool pass = !(a < th) && row < nrows && q < nq;
-                const ms_u64 m = __ballot(pass);
-                if (pass) list[cnt + __popcll(m & ms_mds_low_bits(lane))] = ((uint32_t)ql << 6) | (uint32_t)row;
-                cnt += __popcll(m);
-                if (cnt > MS_MQ_LIST - 64) drain();
-            }
-        }
-        drain();
+        ms_mq_cells(af, qh, thr, qb0, nqt, nrows, nq, wave, lane, cnt,
+                    [&](int slot, int ql, int row) __attribute__((always_inline)) { list[slot] = ((uint32_t)ql << 6) | (uint32_t)row; }, drain);
     };
 
     // (only the masks of queries that exist, to a multiple of 64: a call with a few queries does not clear 33 KB per tile)
@@ -276,19 +230,13 @@ __global__ __launch_bounds__(256, 2) void ms_md_chain_scan_mq_kernel(
             }
         }
     }
-    // the re-score count: one add per wave
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nresc += __shfl_xor(nresc, off);
-    if (lane == 0 && nresc != 0u) atomicAdd(&ctl[2], (ms_u64)nresc);
+    ms_mq_count_rescored(nresc, lane, ctl);
 }
 
-// workspace: prepared queries [nq_pad][128] fp32 | their fp16 operands [nq_pad][128] | thresholds [nq_pad] | first [nranges] | ctl [3]
-
+// workspace: ms_mq_ws (prepared queries | their fp16 operands | thresholds) | first [nranges] | ctl [3]
 extern "C" size_t ms_md_chain_scan_mq_workspace_bytes(int64_t n, int nq) {
     if (nq < 1 || n < 0 || nq > 0x7FFFFFE0) return 0;
-    const size_t nq_pad = (size_t)ms_mq_pad(nq);
-    return nq_pad * MS_DIM * (sizeof(float) + sizeof(_Float16)) + ms_align_up(nq_pad * sizeof(float), 16) +
-           (size_t)(ms_mds_ranges(n) + 3) * sizeof(int64_t);
+    return ms_mq_ws_bytes((size_t)ms_mq_pad(nq)) + (size_t)(ms_mds_ranges(n) + 3) * sizeof(int64_t);
 }
 
 extern "C" int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *chain_start, int64_t nchains, const float *q, int nq, int mode,
@@ -296,16 +244,14 @@ extern "C" int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *ch
                                    int64_t *out_pairs, int64_t cap, int64_t *out_count, int32_t *out_qstatus, float row_norm_bound,
                                    int64_t *out_stats, void *workspace, size_t workspace_bytes, ms_stream_t stream) {
     MS_MDS_CHECK_ARGS("ms_md_chain_scan_mq");
-    if (!(row_norm_bound >= 9.094947e-13f && row_norm_bound <= 1.0995116e12f))
-        MS_FAIL(MS_ERR_RANGE, "ms_md_chain_scan_mq: the fp16 operands need a row-norm bound in [2^-40, 2^40] (got %g)", (double)row_norm_bound);
+    MS_MQ_CHECK_BOUND("ms_md_chain_scan_mq");
     const size_t need = ms_md_chain_scan_mq_workspace_bytes(n, nq);
     if (need == 0 || workspace_bytes < need) MS_FAIL(MS_ERR_WORKSPACE, "ms_md_chain_scan_mq: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const int nq_pad = ms_mq_pad(nq);
-    float *qn = (float *)workspace;
-    _Float16 *qh = (_Float16 *)(qn + (size_t)nq_pad * MS_DIM);
-    float *thr = (float *)(qh + (size_t)nq_pad * MS_DIM);
-    int64_t *first = (int64_t *)((char *)thr + ms_align_up((size_t)nq_pad * sizeof(float), 16));
+    const ms_mq_params p = ms_mq_derive(row_norm_bound);
+    const ms_mq_ws w = ms_mq_carve(workspace, nq_pad);
+    int64_t *first = (int64_t *)w.tail;
     const int64_t nranges = ms_mds_ranges(n);
     ms_u64 *ctl = (ms_u64 *)(first + nranges);
     MS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ms_md_chain_scan_mq_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -314,24 +260,16 @@ extern "C" int ms_md_chain_scan_mq(const float *db, int64_t n, const int64_t *ch
                        nq, out_qstatus, ctl);
     MS_LAUNCH_CHECK("ms_md_scan_setup_kernel");
     const bool work = nqc > 0 && nchains > 0 && n > 0;
-    int rc = MS_OK;
-    if (work) rc = ms_launch_prepare_queries(q, nq, nq_pad, mode, qn, st);
+    const int rc = ms_mq_launch_operands(q, nq, nq_pad, mode, work, min_score, p, w, ctl, st);
     if (rc) return rc;
-    // (the set-up launch of the operands runs in every call: it resets the re-score count)
-    const int sr = 14 - ilogbf(row_norm_bound);
-    const float eb = ms_pf_err_coef(MS_PF_F16X1) * row_norm_bound;
-    hipLaunchKernelGGL(ms_md_scan_mq_prep_kernel, dim3((unsigned)(work ? (nq_pad + 255) / 256 : 1)), dim3(256), 0, st, qn, nq, work ? nq_pad : 0,
-                       min_score, eb, sr, qh, thr, ctl);
-    MS_LAUNCH_CHECK("ms_md_scan_mq_prep_kernel");
     if (work) {
         const int64_t ncheck = nchains < n + 1 ? nchains : n + 1;
         hipLaunchKernelGGL(ms_md_scan_table_kernel, dim3((unsigned)((ncheck + 1 + 255) / 256)), dim3(256), 0, st, chain_start, nchains, ncheck,
                            n, nranges, first, ctl);
         MS_LAUNCH_CHECK("ms_md_scan_table_kernel");
         const unsigned grid = (unsigned)(nranges < MS_MDS_MAX_GRID ? nranges : MS_MDS_MAX_GRID);
-        hipLaunchKernelGGL(ms_md_chain_scan_mq_kernel, dim3(grid), dim3(256), MS_MQ_LDS, st, db, n, chain_start, nchains, qn, qh, thr, nq, nq_pad,
-                           lengths, qlen, mincov, qchain, nqc, min_score, row_norm_bound * row_norm_bound * (1.0f + 1e-5f), ldexpf(1.0f, sr), out_pairs, cap, first,
-                           nranges, ctl);
+        hipLaunchKernelGGL(ms_md_chain_scan_mq_kernel, dim3(grid), dim3(256), MS_MQ_LDS, st, db, n, chain_start, nchains, w.qn, w.qh, w.thr, nq,
+                           nq_pad, lengths, qlen, mincov, qchain, nqc, min_score, p.b2, p.rscale, out_pairs, cap, first, nranges, ctl);
         MS_LAUNCH_CHECK("ms_md_chain_scan_mq_kernel");
     }
     hipLaunchKernelGGL(ms_md_scan_finish_kernel, dim3(1), dim3(1), 0, st, ctl, out_count, out_stats);

@@ -77,7 +77,7 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
     rank 0 writes."""
     from . import dbsearch
     from . import multidomain as md
-    from .dbquery import QueryDB, parse_row_slice, same_database
+    from .dbquery import QueryDB
     from .results import append_written, multi_dom_writer
     from .target import Target, score_mode as target_score_mode
 
@@ -91,18 +91,9 @@ def run_chain_search(query_db: str, db_name: str, output: str, tmp: str, device=
     if report not in md.REPORTS:
         dbsearch._refuse("--multi_domain_report must be one of %s, got %r." % (", ".join(md.REPORTS), report))
     write_multi_dom = multi_dom_writer(report)
-    same = same_database(query_db, db_name)
-    if exclude_same_chain and not same:
-        dbsearch._refuse("--exclude_same_chain removes the query chain itself from its candidates: it needs the query database and "
-                         "the target database to be the same, got %s and %s." % (query_db, db_name))
-    for prefix in (query_db, db_name):
-        dbsearch._require_database(prefix)
-    target_db = dbsearch.read_database(db_name=db_name)                   # (host side only: nothing is uploaded yet)
-    qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
-    try:
-        q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
-    except ValueError as exc:
-        dbsearch._refuse("--query_rows: %s" % exc)
+    target_db, qdb, same, q_lo, q_hi = dbsearch.open_query_and_target(
+        query_db, db_name, query_rows,
+        "--exclude_same_chain removes the query chain itself from its candidates: it needs" if exclude_same_chain else None)
     rank = sharded.rank_world()[0]
     os.makedirs(tmp, exist_ok=True)
     multi_output = output + "_search_multi_dom.tsv"

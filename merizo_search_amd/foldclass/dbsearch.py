@@ -6,13 +6,15 @@ Same function names, argument meaning, return shapes and on-disk layouts as the 
     read_database                                 dbsearch.py:48-72
     search_query_against_db                       dbsearch.py:75-81
     knn_exact                                     dbsearch.py:213-248 (knn_exact_faiss)
-    dbsearch                                      dbsearch.py:84-200   `.pt` database
+    dbsearch                                      dbsearch.py:84-200   `.pt` database, one query
     dbsearch_faiss                                dbsearch.py:203-472  faiss-layout database
+    hit_records                                   dbsearch.py:119-200 and :312-472  top-k lists -> hit records, both layouts
     run_dbsearch                                  dbsearch.py:475-551
     run_dbsearch_db                               (no counterpart: a database as the query side, `db-search`)
 
-Both hit-record loops (dbsearch, _faiss_hit_records) take names, sequences, coordinates and metadata of their hits from the
-database's one host-side reader, dbrecords.Records, which maps each record file once per run.
+Every driver turns its top-k lists into hit records with hit_records: one selection, one fetch per field from the database's
+one host-side reader (dbrecords.Records, which maps each record file once per run), one TM-align batch or one call of the
+binary per hit, one loop; what the two layouts do differently there is a rule that names `faiss`.
 
 What differs, deliberately (DESIGN.md "host drivers"):
   * all queries of a call are embedded in ONE ragged GPU launch and searched in ONE batched
@@ -201,29 +203,8 @@ def _chain_list(pdb_chain: Optional[str], n_inputs: int) -> List[str]:
     sys.exit(1)
 
 
-def _aligner_device(network, device):
-    engine = getattr(network, "engine", None)
+def _aligner_device(engine, device):
     return getattr(engine, "device", None) or device or "cuda"
-
-
-def _hip_tm_outputs(query_dicts, hits, fastmode, device):
-    """TM-align the (query number, target coords, target seq) triples of `hits` in one GPU batch -> list of dicts
-    (extract_tmalign_values' shape) or None where TM-align refuses the pair."""
-    return tm.align_many([(query_dicts[q]["coords"], query_dicts[q]["seq"], c, s) for q, c, s in hits], fast=fastmode,
-                         device=device)
-
-
-def _pt_hip_outputs(query_dicts, target_dict, tops, topk, mincos, fastmode, device):
-    """`.pt` path: {rank: tm output} per query for every rank of its top-k that passes mincos, all queries in one batch."""
-    keys = [(q, rank) for q, (scores, _indices) in enumerate(tops) for rank in range(min(topk, scores.shape[0]))
-            if scores[rank] >= mincos]
-    records, rows = Records.of(target_dict), [int(tops[q][1][rank]) for q, rank in keys]
-    hits = [(q, coords, seq) for (q, _rank), coords, seq in zip(keys, records.coords(rows), records.seqs(rows))]
-    outs = _hip_tm_outputs(query_dicts, hits, fastmode, device)
-    per_query = [dict() for _ in tops]
-    for (q, rank), out in zip(keys, outs):
-        per_query[q][rank] = out
-    return per_query
 
 
 def _refused(query_dict, target_name) -> None:
@@ -241,58 +222,81 @@ def _tmalign_pair(tmp, query_dict, target_coords, target_seq, fastmode, target_n
     return tm.run_tmalign(qfn, tfn, options="-fast" if fastmode else None, keep_pdbs=False)
 
 
+# ------------------------------------------------------------------ top-k lists -> hit records
+def hit_records(query_dicts, D, I, records: Records, faiss: bool, *, mincos, mintm, mincov, fastmode, skip_tmalign, tmalign_backend,
+                tmp, aligner_device, tm_excluded_before: int = 0):
+    """The top-k lists of a call's queries -> (results, all_results), one dict of hit records per query, twice: the hits at or
+    above mintm and those below it (dbsearch.py:119-200 and :312-472).  D float32 / I int64 [nq,k]: scores and global rows, best
+    first, (-inf, -1) behind the real entries.  A hit is an entry with D >= mincos and I >= 0; names, sequences, coordinates and
+    metadata of ALL hits of the call come from `records` (the target database's reader) in one fetch per field, with
+    tmalign_backend 'hip' they are aligned in ONE GPU batch, else one call of the binary per hit.
+    faiss: the layout of the target database, which decides the keys (`.pt`: the hit's rank = its column in D, in both dicts;
+    faiss: a dense counter per query, and for hits below mintm ONE counter over all queries of a search, dbsearch.py:449-452),
+    the coverage rule (`.pt` only, :165), the names of the binary's temporary files and the three log lines of the faiss path.
+    tm_excluded_before: a search made in several calls (run_dbsearch_db's query batches) passes how many hits below mintm the
+    earlier calls counted."""
+    nq = len(query_dicts)
+    results = [dict() for _ in range(nq)]
+    all_results = [dict() for _ in range(nq)]
+    keep = np.where((D >= mincos) & (I >= 0))                  # row-major: grouped by query, rank order
+    rows, scores, queries, ranks = I[keep], D[keep], keep[0], keep[1]
+    n_hits = len(rows)
+    if n_hits == 0:
+        return results, all_results
+    if faiss:
+        logger.info("Retrieve domain hits...")
+    # (each hit reports its OWN metadata, also one that follows a rank below mincos; "{ }" only in a database without any)
+    names, seqs, metadata = records.stored_names(rows), records.seqs(rows), records.metadata(rows)
+    hip_outputs = None
+    if not skip_tmalign:
+        if faiss:
+            logger.info("TM-align top hits...")
+        coords = records.coords(rows)
+        if tmalign_backend == "hip":                           # every (query, hit) pair of the call in one GPU batch
+            hip_outputs = tm.align_many([(query_dicts[q]["coords"], query_dicts[q]["seq"], c, s) for q, c, s in zip(queries, coords, seqs)],
+                                        fast=fastmode, device=aligner_device)
+    counts = [0] * nq
+    n_tm_exclude = int(tm_excluded_before)
+    for h, (qi, row, rank) in enumerate(zip(queries.tolist(), rows.tolist(), ranks.tolist())):      # (plain ints)
+        qd, t_len = query_dicts[qi], len(seqs[h])
+        key = counts[qi] if faiss else rank
+        tm_output = None
+        if not skip_tmalign:
+            if hip_outputs is None:
+                tm_output = _tmalign_pair(tmp, qd, coords[h], seqs[h], fastmode, target_name=names[h], named=faiss)
+            else:
+                tm_output = hip_outputs[h]
+                if tm_output is None:
+                    _refused(qd, names[h])
+                    continue
+            if not faiss and not (tm_output["len_ali"] >= t_len * mincov):        # coverage filter, `.pt` path only (:165)
+                continue
+        rec = _hit(qd, names[h], scores[h], t_len, tm_output, row, metadata[h])
+        if skip_tmalign or max(tm_output["qtm"], tm_output["ttm"]) >= mintm:
+            results[qi][key] = rec
+            counts[qi] += 1
+        else:
+            all_results[qi][n_tm_exclude if faiss else key] = rec
+            n_tm_exclude += 1
+    if faiss and n_tm_exclude > tm_excluded_before:
+        logger.info("Excluded " + str(n_tm_exclude - int(tm_excluded_before)) + " hits (across all query domains) by TM-score threshold(>=" + str(mintm) + ")")
+    return results, all_results
+
+
 # ------------------------------------------------------------------ `.pt` driver -------
 def dbsearch(query, target_dict: dict, tmp: str, network, topk: int, mincov: float, mincos: float, mintm: float,
              fastmode: bool, device=None, inputs_are_ca: bool = False, pdb_chain: str = "A", skip_tmalign: bool = False,
-             score_corrections=None, _embedding=None, _topk=None, tmalign_backend: str = "auto", _tm_outputs=None):
-    """One query against a `.pt` database -> (results, all_results), dicts keyed by the hit's
-    position in the top-k (dbsearch.py:84-200).  `_embedding` / `_topk` let run_dbsearch pass one
-    row of a batched embedding / batched scan instead of recomputing per query; `_tm_outputs` ({rank: output}) the
-    GPU aligner's results of a batch run_dbsearch made for all queries (tmalign_backend='hip')."""
+             score_corrections=None, tmalign_backend: str = "auto"):
+    """One query against a `.pt` database -> (results, all_results), dicts keyed by the hit's position in the top-k
+    (dbsearch.py:84-200): embed, scan, hit_records on the one list."""
     query_dict = query if inputs_are_ca else read_pdb(pdbfile=query, pdb_chain=pdb_chain)
-    engine = network.engine
-    if _topk is None:
-        if _embedding is None:
-            _embedding = network.embed_many([query_dict["coords"]])
-        query_dict["embedding"] = _embedding.reshape(1, -1)
-        result = search_query_against_db(query_dict, target_dict, mincov, topk, score_corrections, engine=engine)
-        scores = result["scores"].cpu().numpy()
-        indices = result["indices"].cpu().numpy()
-    else:
-        query_dict["embedding"] = _embedding
-        scores, indices = _topk
-
-    if tmalign_backend == "hip" and not skip_tmalign and _tm_outputs is None:
-        _tm_outputs = _pt_hip_outputs([query_dict], target_dict, [(scores, indices)], topk, mincos, fastmode,
-                                      _aligner_device(network, device))[0]
-    # the rows of every rank, from the database's one reader.  Each rank reports its OWN metadata, also one that follows a rank
-    # below mincos (the reference fetches per rank, dbsearch.py:119-123, and carries "{ }" over only in a database without any)
-    records, rows = Records.of(target_dict), [int(i) for i in indices[: min(topk, scores.shape[0])]]
-    names, seqs, metadata = records.stored_names(rows), records.seqs(rows), records.metadata(rows)
-    results, all_results = {}, {}
-    for rank, dbindex in enumerate(rows):
-        score, target_name, target_seq = scores[rank], names[rank], seqs[rank]
-        if skip_tmalign:
-            if score >= mincos:
-                results[rank] = _hit(query_dict, target_name, score, len(target_seq), None, dbindex, metadata[rank])
-            continue
-        if not (score >= mincos):
-            continue
-        if _tm_outputs is not None:
-            tm_output = _tm_outputs[rank]
-            if tm_output is None:
-                _refused(query_dict, target_name)
-                continue
-        else:
-            tm_output = _tmalign_pair(tmp, query_dict, records.coords([dbindex])[0], target_seq, fastmode)
-        max_tm = max(tm_output["qtm"], tm_output["ttm"])
-        if tm_output["len_ali"] >= len(target_seq) * mincov:       # coverage filter, `.pt` path only (:165)
-            rec = _hit(query_dict, target_name, score, len(target_seq), tm_output, dbindex, metadata[rank])
-            if max_tm >= mintm:
-                results[rank] = rec
-            else:
-                all_results[rank] = rec
-    return results, all_results
+    query_dict["embedding"] = network.embed_many([query_dict["coords"]]).reshape(1, -1)
+    top = search_query_against_db(query_dict, target_dict, mincov, topk, score_corrections, engine=network.engine)
+    results, all_results = hit_records([query_dict], top["scores"].cpu().numpy()[None], top["indices"].cpu().numpy()[None],
+                                       Records.of(target_dict), False, mincos=mincos, mintm=mintm, mincov=mincov, fastmode=fastmode,
+                                       skip_tmalign=skip_tmalign, tmalign_backend=tmalign_backend, tmp=tmp,
+                                       aligner_device=_aligner_device(network.engine, device))
+    return results[0], all_results[0]
 
 
 # ------------------------------------------------------------------ faiss-layout driver -
@@ -321,67 +325,11 @@ def dbsearch_faiss(queries, target_dict: dict, tmp: str, network, topk: int, min
     # this rank's rows of the matrix, resident (F.normalize, :303-304, + knn_exact_faiss, :213-248, as ONE launch for the few
     # queries of a CLI search; more than 64 queries: the prefiltered search) or streamed block by block; then the exchange
     Ds, Is = Target.of(target_dict, engine, nq, int(topk)).topk(emb, int(topk), raw_queries=True, search_batchsize=search_batchsize)
-    D, I = Ds.cpu().numpy(), Is.cpu().numpy()
-    results = [dict() for _ in range(nq)]
-    all_results = [dict() for _ in range(nq)]
     if sharded.rank_world()[0] != 0:
-        return results, all_results                                       # rank 0 assembles the hit records
-    return _faiss_hit_records(query_dicts, D, I, Records.of(target_dict), mincos, mintm, fastmode, skip_tmalign, tmalign_backend,
-                              tmp, _aligner_device(network, device))
-
-
-def _faiss_hit_records(query_dicts, D, I, records: Records, mincos, mintm, fastmode, skip_tmalign, tmalign_backend, tmp,
-                       aligner_device, tm_excluded_before: int = 0):
-    """Rank 0's half of dbsearch_faiss (dbsearch.py:312-472): the top-k lists D / I of all queries -> (results, all_results),
-    hit records retrieved through `records` (the target database's reader), TM-align per hit.
-    tm_excluded_before: hits below mintm are keyed by ONE counter over all queries of a search (dbsearch.py:449-452); a
-    search made in several calls (run_dbsearch_db's query batches) passes how many the earlier calls counted."""
-    nq = len(query_dicts)
-    results = [dict() for _ in range(nq)]
-    all_results = [dict() for _ in range(nq)]
-    keep = np.where((D >= mincos) & (I >= 0))                  # row-major: grouped by query, rank order
-    hit_indices, hit_scores, query_indices = I[keep], D[keep], keep[0]
-    n_hits = len(hit_indices)
-    if n_hits == 0:
-        return results, all_results
-
-    logger.info("Retrieve domain hits...")
-    hit_ids, hit_seqs, hit_metadata = records.names(hit_indices), records.seqs(hit_indices), records.metadata(hit_indices)
-    hit_coords = None if skip_tmalign else records.coords(hit_indices)
-
-    if not skip_tmalign:
-        logger.info("TM-align top hits...")
-    hip_outputs = None
-    if not skip_tmalign and tmalign_backend == "hip":               # every hit of the call in one GPU batch
-        hip_outputs = _hip_tm_outputs(query_dicts, [(int(query_indices[h]), hit_coords[h], hit_seqs[h]) for h in range(n_hits)],
-                                      fastmode, aligner_device)
-    counts = [0] * nq
-    n_tm_exclude = int(tm_excluded_before)
-    for h in range(n_hits):
-        qi = int(query_indices[h])
-        qd = query_dicts[qi]
-        t_len = len(hit_seqs[h])
-        if skip_tmalign:
-            results[qi][counts[qi]] = _hit(qd, hit_ids[h], hit_scores[h], t_len, None, hit_indices[h], hit_metadata[h])
-            counts[qi] += 1
-            continue
-        if hip_outputs is not None:
-            tm_output = hip_outputs[h]
-            if tm_output is None:
-                _refused(qd, hit_ids[h])
-                continue
-        else:
-            tm_output = _tmalign_pair(tmp, qd, hit_coords[h], hit_seqs[h], fastmode, target_name=hit_ids[h], named=True)
-        rec = _hit(qd, hit_ids[h], hit_scores[h], t_len, tm_output, hit_indices[h], hit_metadata[h])
-        if max(tm_output["qtm"], tm_output["ttm"]) >= mintm:
-            results[qi][counts[qi]] = rec
-            counts[qi] += 1
-        else:
-            all_results[qi][n_tm_exclude] = rec
-            n_tm_exclude += 1
-    if n_tm_exclude > tm_excluded_before:
-        logger.info("Excluded " + str(n_tm_exclude - int(tm_excluded_before)) + " hits (across all query domains) by TM-score threshold(>=" + str(mintm) + ")")
-    return results, all_results
+        return [dict() for _ in range(nq)], [dict() for _ in range(nq)]   # rank 0 assembles the hit records
+    return hit_records(query_dicts, Ds.cpu().numpy(), Is.cpu().numpy(), Records.of(target_dict), True, mincos=mincos, mintm=mintm,
+                       mincov=mincov, fastmode=fastmode, skip_tmalign=skip_tmalign, tmalign_backend=tmalign_backend, tmp=tmp,
+                       aligner_device=_aligner_device(network.engine, device))
 
 
 # ------------------------------------------------------------------ dispatcher ---------
@@ -403,10 +351,7 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
         os.mkdir(tmp)
     if network is None:
         network, device = network_setup(threads=threads, device=device, weights_path=weights_path)
-    if not skip_tmalign and tmalign_backend == "auto" and tm.find_tmalign() is None:
-        logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
-                       "TM-align columns are unavailable")
-        skip_tmalign = True
+    skip_tmalign = tm.skip_without_binary(skip_tmalign, tmalign_backend)
     if target_db is None:
         target_db = read_database(db_name=db_name, device=device, engine=network.engine)
 
@@ -423,22 +368,11 @@ def run_dbsearch(inputs, db_name: str, tmp: str, device, topk: int, fastmode: bo
     emb = sharded.embed_distributed(network, [qd["coords"] for qd in query_dicts])   # ragged launches, data-parallel over ranks
     batch = {"seq": [qd["seq"] for qd in query_dicts], "embedding": emb}
     top = search_query_against_db(batch, target_db, mincov, topk, engine=network.engine)   # one batched scan (+ exchange)
-    top_s, top_i = top["scores"].cpu().numpy(), top["indices"].cpu().numpy()
-    search_results, all_search_results = [], []
     if sharded.rank_world()[0] != 0:
         return [dict() for _ in query_dicts], [dict() for _ in query_dicts]      # rank 0 assembles the hit records
-    tm_outputs = [None] * len(query_dicts)
-    if not skip_tmalign and tmalign_backend == "hip":               # every (query, hit) pair of the call in one GPU batch
-        tm_outputs = _pt_hip_outputs(query_dicts, target_db, list(zip(top_s, top_i)), topk, mincos, fastmode,
-                                     _aligner_device(network, device))
-    for row, qd in enumerate(query_dicts):
-        res, all_res = dbsearch(query=qd, target_dict=target_db, tmp=tmp, network=network, topk=topk, mincov=mincov,
-                                mincos=mincos, mintm=mintm, fastmode=fastmode, device=device, inputs_are_ca=True,
-                                skip_tmalign=skip_tmalign, _embedding=emb[row:row + 1], _topk=(top_s[row], top_i[row]),
-                                tmalign_backend=tmalign_backend, _tm_outputs=tm_outputs[row])
-        search_results.append(res)
-        all_search_results.append(all_res)
-    return search_results, all_search_results
+    return hit_records(query_dicts, top["scores"].cpu().numpy(), top["indices"].cpu().numpy(), Records.of(target_db), False,
+                       mincos=mincos, mintm=mintm, mincov=mincov, fastmode=fastmode, skip_tmalign=skip_tmalign,
+                       tmalign_backend=tmalign_backend, tmp=tmp, aligner_device=_aligner_device(network.engine, device))
 
 
 # ------------------------------------------------------------------ database x database -
@@ -601,6 +535,26 @@ def _require_database(prefix: str) -> None:
                 % (prefix, prefix, prefix))
 
 
+def open_query_and_target(query_db: str, db_name: str, query_rows: Optional[str], needs_same: Optional[str] = None):
+    """The two sides of a search of database `query_db` against database `db_name` (run_dbsearch_db, chainsearch.run_chain_search)
+    -> (target_db: read_database's dict, host side only -- nothing is uploaded yet; qdb: the query side's QueryDB; same: do both
+    prefixes name one database; q_lo, q_hi: the query rows of query_rows = 'LO:HI', all rows for None).
+    needs_same: an option that only a search of a database against itself can serve was given -- the refusal's opening words."""
+    same = same_database(query_db, db_name)
+    if needs_same and not same:
+        _refuse("%s the query database and the target database to be the same, got %s and %s." % (needs_same, query_db, db_name))
+    for prefix in (query_db, db_name):
+        _require_database(prefix)
+    target_db = read_database(db_name=db_name)
+    # (a `.pt` database searched against itself: ONE unpickled index and one mapped tensor serve both sides)
+    qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
+    try:
+        q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
+    except ValueError as exc:
+        _refuse("--query_rows: %s" % exc)
+    return target_db, qdb, same, q_lo, q_hi
+
+
 def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="cuda", topk: int = 1, fastmode: bool = False,
                     mincos: float = 0.5, mintm: float = 0.5, mincov: float = 0.7, search_batchsize: int = 262144,
                     search_type: str = "IP", skip_tmalign: bool = False, tmalign_backend: str = "auto",
@@ -624,11 +578,10 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
     seed the candidates are each batch's reported results, and with exclude_self a query chain is never its own candidate
     (_ChainStep).  max_mapping_paths: multidomain.MAX_MAPPING_PATHS unless given.  multi_domain_report: 'all' = every mapping of a
     pair, 'best' = the best one(s) per pair with their score (multidomain.best_lines; no path cap).
-    Everything else -- thresholds, hit records, columns -- is the code of dbsearch / dbsearch_faiss.  Returns the number of
+    Everything else -- thresholds, hit records, columns -- is the code of `search` (hit_records).  Returns the number of
     queries searched.  `timings`: a dict that receives which path ran ('in_place': the queries were row ranges of the resident
     matrix; 'streamed': the target went through engine.device_blocks) and HIP-event totals of the scan calls and the drop step."""
     import time
-    from types import SimpleNamespace
 
     from .results import SEARCH_FIELDS, append_written, embedding_only_format, multi_dom_writer, write_search_results
 
@@ -646,19 +599,9 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
         _refuse("--multi_domain_report must be 'all' or 'best', got %r." % (multi_domain_report,))
     write_multi_dom = multi_dom_writer(multi_domain_report)
     exclude_self = exclude_self or exclude_same_chain
-    same = same_database(query_db, db_name)
-    if exclude_self and not same:
-        _refuse("--exclude_self / --exclude_same_chain remove the query's own rows from its hits: they need the query database "
-                "and the target database to be the same, got %s and %s." % (query_db, db_name))
-    for prefix in (query_db, db_name):
-        _require_database(prefix)
-    target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
-    # (a `.pt` database searched against itself: ONE unpickled index and one mapped tensor serve both sides)
-    qdb = QueryDB(query_db, loaded=target_db if same and not target_db["faiss"] else None)
-    try:
-        q_lo, q_hi = parse_row_slice(query_rows, qdb.n)
-    except ValueError as exc:
-        _refuse("--query_rows: %s" % exc)
+    target_db, qdb, same, q_lo, q_hi = open_query_and_target(
+        query_db, db_name, query_rows,
+        "--exclude_self / --exclude_same_chain remove the query's own rows from its hits: they need" if exclude_self else None)
     if target_db["faiss"] and search_type != "IP":
         _refuse("Invalid/unsupported faiss search type: " + search_type + "\n\tOnly 'IP' is currently supported.")
     records = qdb if same else Records.of(target_db)                      # the target's rows on the host: one reader for the run
@@ -673,10 +616,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
                 % (topk, max_excluded, n_target))
 
     rank, world = sharded.rank_world()
-    if not skip_tmalign and tmalign_backend == "auto" and tm.find_tmalign() is None:
-        logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
-                       "TM-align columns are unavailable")
-        skip_tmalign = True
+    skip_tmalign = tm.skip_without_binary(skip_tmalign, tmalign_backend)
     fields = embedding_only_format(list(format_list) if format_list is not None else SEARCH_FIELDS.split(","), skip_tmalign)
     if not os.path.exists(tmp):
         os.makedirs(tmp, exist_ok=True)
@@ -691,8 +631,6 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
 
     engine = engine or engine_setup(device)
     times = _DeviceTimes(engine, timings)
-    network = SimpleNamespace(engine=engine)
-    aligner_device = _aligner_device(network, device)
     target = Target.of(target_db, engine, min(int(query_batchsize), q_hi - q_lo), kk)      # resident once, or streamed per batch
     scan = _BatchScan(target, qdb, same, kk, search_batchsize, times)
     logger.info("db-search: %d queries of %s against %d rows of %s in batches of %d (k = %d%s)%s"
@@ -709,7 +647,7 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
                                 MAX_MAPPING_PATHS if max_mapping_paths is None else max_mapping_paths, times, timings,
                                 report=multi_domain_report)
     md_all = {}
-    tm_excluded = 0                                                       # (the faiss path's one counter of hits below mintm)
+    tm_excluded = 0                                                       # (hits below mintm so far: the faiss layout keys them by it)
     t_loop = time.perf_counter()
     for b0 in range(q_lo, q_hi, int(query_batchsize)):
         b1 = min(q_hi, b0 + int(query_batchsize))
@@ -719,27 +657,15 @@ def run_dbsearch_db(query_db: str, db_name: str, output: str, tmp: str, device="
             seqs = [qd["seq"] for qd in query_dicts]
         elif not target_db["faiss"]:
             seqs = qdb.seqs(b0, b1)                                       # (every rank masks by query length)
-        Ds, Is, Cs = scan.search(b0, b1, seqs, mincov, d_lo[b0 - q_lo: b1 - q_lo], d_hi[b0 - q_lo: b1 - q_lo], int(topk), float(mincos))
+        Ds, Is, _counts = scan.search(b0, b1, seqs, mincov, d_lo[b0 - q_lo: b1 - q_lo], d_hi[b0 - q_lo: b1 - q_lo], int(topk), float(mincos))
         if rank != 0:
             continue
-        D, I, C = Ds.cpu().numpy(), Is.cpu().numpy(), Cs.cpu().numpy()
-        if target_db["faiss"]:
-            results, all_results = _faiss_hit_records(query_dicts, D, I, records, mincos, mintm, fastmode, skip_tmalign,
-                                                      tmalign_backend, tmp, aligner_device, tm_excluded_before=tm_excluded)
-            tm_excluded += sum(len(per_query) for per_query in all_results)
-        else:
-            tops = [(D[r, : C[r]], I[r, : C[r]]) for r in range(b1 - b0)]
-            tm_outputs = [None] * (b1 - b0)
-            if not skip_tmalign and tmalign_backend == "hip":
-                tm_outputs = _pt_hip_outputs(query_dicts, target_db, tops, topk, mincos, fastmode, aligner_device)
-            results, all_results = [], []
-            for r, qd in enumerate(query_dicts):
-                res, all_res = dbsearch(query=qd, target_dict=target_db, tmp=tmp, network=network, topk=topk, mincov=mincov,
-                                        mincos=mincos, mintm=mintm, fastmode=fastmode, device=device, inputs_are_ca=True,
-                                        skip_tmalign=skip_tmalign, _topk=tops[r], tmalign_backend=tmalign_backend,
-                                        _tm_outputs=tm_outputs[r])
-                results.append(res)
-                all_results.append(all_res)
+        # (the drop step pads a list with (-inf, -1) behind its entries: hit_records needs no count)
+        results, all_results = hit_records(query_dicts, Ds.cpu().numpy(), Is.cpu().numpy(), records, target_db["faiss"], mincos=mincos,
+                                           mintm=mintm, mincov=mincov, fastmode=fastmode, skip_tmalign=skip_tmalign,
+                                           tmalign_backend=tmalign_backend, tmp=tmp, aligner_device=_aligner_device(engine, device),
+                                           tm_excluded_before=tm_excluded)
+        tm_excluded += sum(len(per_query) for per_query in all_results)
         part = os.path.join(tmp, "db_search_batch.tsv")
         first = header and b0 == q_lo
         for out_path, per_batch in zip(written, (results, all_results)):

@@ -150,24 +150,31 @@ def unpack_results(buf, world: int, nq: int, k: int):
     return scores, idx
 
 
-def allgather_results(scores, idx, group=None):
-    """All-gather every rank's [nq,k] results -> ([S,nq,k], [S,nq,k]) on every rank."""
+def _all_gather(mine, group=None, out=None):
+    """Every rank's `mine` (one shape and dtype on all ranks) -> `out` [world, *mine.shape] on every rank (allocated here unless
+    given): one RCCL all-gather over xGMI under nccl; gloo gathers into parts and stacks them."""
     import torch
     import torch.distributed as dist
 
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-        return scores.unsqueeze(0), idx.unsqueeze(0)
     world = dist.get_world_size(group)
-    nq, k = scores.shape
-    mine = pack_results(scores, idx)
-    out = torch.empty((world, mine.numel()), dtype=torch.uint8, device=mine.device)
+    if out is None:
+        out = torch.empty((world,) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
     if dist.get_backend(group) == "nccl":
-        dist.all_gather_into_tensor(out, mine, group=group)          # one RCCL all-gather over xGMI
+        dist.all_gather_into_tensor(out, mine, group=group)
     else:
         parts = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(parts, mine, group=group)
-        out = torch.stack(parts)
-    return unpack_results(out, world, nq, k)
+        out.copy_(torch.stack(parts))
+    return out
+
+
+def allgather_results(scores, idx, group=None):
+    """All-gather every rank's [nq,k] results -> ([S,nq,k], [S,nq,k]) on every rank."""
+    _rank, world = rank_world(group)
+    if world == 1:
+        return scores.unsqueeze(0), idx.unsqueeze(0)
+    nq, k = scores.shape
+    return unpack_results(_all_gather(pack_results(scores, idx), group), world, nq, k)
 
 
 def exchange_and_merge(scores, idx, engine, group=None):
@@ -195,22 +202,11 @@ def gather_pairs(pairs, device, group=None) -> np.ndarray:
     if world == 1:
         return pairs
     import torch
-    import torch.distributed as dist
 
-    def all_gather(mine):
-        out = torch.empty((world,) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
-        if dist.get_backend(group) == "nccl":
-            dist.all_gather_into_tensor(out, mine, group=group)
-        else:
-            parts = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(parts, mine, group=group)
-            out.copy_(torch.stack(parts))
-        return out
-
-    counts = all_gather(torch.tensor([pairs.shape[0]], dtype=torch.int64, device=device)).reshape(-1).cpu().numpy()
+    counts = _all_gather(torch.tensor([pairs.shape[0]], dtype=torch.int64, device=device), group).reshape(-1).cpu().numpy()
     block = torch.zeros((max(int(counts.max()), 1), 2), dtype=torch.int64, device=device)
     block[: pairs.shape[0]] = torch.from_numpy(pairs).to(device)
-    gathered = all_gather(block).cpu().numpy()
+    gathered = _all_gather(block, group).cpu().numpy()
     return np.concatenate([gathered[r, : int(counts[r])] for r in range(world)], axis=0)
 
 
@@ -227,26 +223,14 @@ def gather_edges(src, dst, score, device, total: Optional[int] = None, rescored:
     _rank, world = rank_world(group)
     if world == 1:
         return (None if limit is not None and total > limit else (src, dst, score)), total, int(rescored)
-    import torch.distributed as dist
-
-    def all_gather(mine):
-        out = torch.empty((world,) + tuple(mine.shape), dtype=mine.dtype, device=mine.device)
-        if dist.get_backend(group) == "nccl":
-            dist.all_gather_into_tensor(out, mine, group=group)
-        else:
-            parts = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(parts, mine, group=group)
-            out.copy_(torch.stack(parts))
-        return out
-
-    counts = all_gather(torch.tensor([m, total, int(rescored)], dtype=torch.int64, device=device)).cpu().numpy()
+    counts = _all_gather(torch.tensor([m, total, int(rescored)], dtype=torch.int64, device=device), group).cpu().numpy()
     all_total, all_rescored = int(counts[:, 1].sum()), int(counts[:, 2].sum())
     if limit is not None and all_total > limit:
         return None, all_total, all_rescored
     block = torch.zeros((max(int(counts[:, 0].max()), 1), 3), dtype=torch.int64, device=device)
     block[:m, 0], block[:m, 1] = src.to(device), dst.to(device)
     block[:m, 2] = score.to(device).contiguous().view(torch.int32).to(torch.int64)
-    gathered = all_gather(block)
+    gathered = _all_gather(block, group)
     cat = torch.cat([gathered[r, : int(counts[r, 0])] for r in range(world)], dim=0)
     return (cat[:, 0].contiguous(), cat[:, 1].contiguous(), cat[:, 2].to(torch.int32).view(torch.float32).contiguous()), all_total, all_rescored
 
@@ -274,7 +258,6 @@ def embed_distributed(network, coords_list: Sequence[np.ndarray], group=None):
     if world == 1 or len(coords_list) < 2:
         return network.embed_many(coords_list)
     import torch
-    import torch.distributed as dist
 
     shares = balance_by_cost([float(np.asarray(c).shape[0]) ** 2 for c in coords_list], world)
     cap = max(len(s) for s in shares)
@@ -284,13 +267,7 @@ def embed_distributed(network, coords_list: Sequence[np.ndarray], group=None):
     block = torch.zeros((cap, 128), dtype=torch.float32, device=device)
     if mine:
         block[: len(mine)] = local
-    gathered = torch.empty((world, cap, 128), dtype=torch.float32, device=device)
-    if dist.get_backend(group) == "nccl":
-        dist.all_gather_into_tensor(gathered, block, group=group)
-    else:
-        parts = [torch.empty_like(block) for _ in range(world)]
-        dist.all_gather(parts, block, group=group)
-        gathered.copy_(torch.stack(parts))
+    gathered = _all_gather(block, group)
     out = torch.empty((len(coords_list), 128), dtype=torch.float32, device=device)
     for r, share in enumerate(shares):
         if share:
@@ -323,18 +300,10 @@ class PackedExchange:
         self.merged_i = torch.empty((nq, k), dtype=torch.int64, device=device)
 
     def exchange(self):
-        import torch
-        import torch.distributed as dist
-
         if self.world == 1:
             self.gathered[0].copy_(self.mine)
-        elif dist.get_backend(self.group) == "nccl":
-            dist.all_gather_into_tensor(self.gathered, self.mine, group=self.group)      # one RCCL all-gather over xGMI
-        else:
-            parts = [torch.empty_like(self.mine) for _ in range(self.world)]
-            dist.all_gather(parts, self.mine, group=self.group)
-            self.gathered.copy_(torch.stack(parts))
-        return self.gathered
+            return self.gathered
+        return _all_gather(self.mine, self.group, out=self.gathered)
 
     def blocks(self):
         """Views ([S,nq,k] float32, [S,nq,k] int64) of the gathered blocks (strided, no copy)."""

@@ -84,6 +84,15 @@ def check_backend(backend: str, device=None) -> None:
         raise ValueError("tmalign_backend 'hip' runs TM-align on the GPU: it needs a cuda device, got %r" % (device,))
 
 
+def skip_without_binary(skip_tmalign: bool, backend: str) -> bool:
+    """The skip_tmalign a search runs with: backend 'auto' with no TM-align binary makes it embedding-only, and says so."""
+    if not skip_tmalign and backend == "auto" and find_tmalign() is None:
+        logger.warning("no TM-align binary found (set $MERIZO_TMALIGN): running an embedding-only search; "
+                       "TM-align columns are unavailable")
+        return True
+    return skip_tmalign
+
+
 def pdb_values(coords) -> np.ndarray:
     """The fp64 coordinates TM-align parses from the %8.3f PDB text the binary path writes: float("%.3f" % v)."""
     c = np.asarray(coords, dtype=np.float32).astype(np.float64).reshape(-1, 3)

@@ -327,6 +327,48 @@ int ms_cluster_components(const int64_t *nbr_idx, const float *nbr_score, int64_
                           float mincov, int64_t *out_rep, float *out_link_score, int64_t *out_n_components, int32_t *out_rounds,
                           int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* The distinct unordered pairs of the SAME graph, and a verdict per pair written back onto it: what `cluster --mintm` runs around
+ * its TM-align stage.  The graph arguments are those of ms_cluster_greedy_edges -- lists [n,k] (k == 0 with NULL lists: none), m
+ * extra directed entries (m == 0 with NULL arrays: none), lengths, min_score, mincov -- a directed entry is VALID under exactly
+ * the rule of ms_cluster_greedy (an edge_src or a row outside [0, n) is never dereferenced), and the priority is its priority.
+ * The CANONICAL pair of a valid entry i -> j is (a, b): a the higher-priority row of {i, j}, b the other one.
+ *
+ * ms_cluster_pairs: out_count int64 [2] (device): out_count[0] = the number of distinct canonical pairs over all valid entries,
+ * exact whatever cap is; out_count[1] = the list rows whose k entries are ALL valid (*out_saturated of the cluster calls, 0 when
+ * k == 0: reported here because the lists are about to be edited).  out_pairs int32 [cap][2] (device): its first min(count, cap)
+ * slots hold distinct canonical pairs {a, b}, in unspecified order; nothing is written at or behind slot cap; cap == 0 only
+ * counts (out_pairs may then be NULL).  The pair SET is a function of the inputs alone: it does not depend on how the same
+ * entries are split between lists and extras, on their order or on duplicates; slot numbers are not promised.  The workspace is
+ * left holding the set (pair -> slot) for the two calls below.  Asynchronous on `stream`; never allocates; the workspace --
+ * ms_cluster_pairs_workspace_bytes(n, k, m) bytes (0 for n outside [1, 2^31 - 1], k < 0, m < 0 or n k + m >= 2^31), 16-byte
+ * aligned -- is initialised by the call itself and serves the next ms_cluster_pairs call without clean-up.
+ *
+ * ms_cluster_pairs_apply: the same graph arguments (n, k and m as in the building call), written in place; keep uint8 [count]
+ * (device), indexed by slot; the workspace as ms_cluster_pairs left it.  Every VALID directed entry whose pair has
+ * keep[slot] == 0 is overwritten: a list entry becomes (-inf, -1), an extra edge_dst = -1, edge_score = -inf.  A valid entry is
+ * removed as well (fail closed) when its pair is not in the set, when its slot is >= count, or >= the cap of the building call.
+ * Invalid entries are left bit for bit as they were.  *out_removed (int64 [1], device) = the directed entries removed.  After
+ * it the cluster calls above see exactly the graph without the rejected pairs, in both directions.  Asynchronous.
+ *
+ * ms_cluster_pairs_find: a / b int64 [cnt] (device); out_slot[e] (int64 [cnt], device) = the slot of the unordered pair
+ * {a[e], b[e]}, in either order; -1 when the pair is not in the set (or was counted behind cap), when a row is outside [0, n)
+ * and when a[e] == b[e].  n as in the building call; the set is found through the workspace's own head.  Asynchronous.
+ *
+ * MS_ERR_ARG: what ms_cluster_greedy_edges refuses, a negative cap / count / cnt, a workspace that is not 16-byte aligned;
+ * MS_ERR_RANGE: n k + m >= 2^31; MS_ERR_WORKSPACE: a workspace that is too small.
+ * Backward compatible additions: ms_version() stays 210. */
+size_t ms_cluster_pairs_workspace_bytes(int64_t n, int k, int64_t m);
+int ms_cluster_pairs(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                     const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
+                     float mincov, int32_t *out_pairs, int64_t cap, int64_t *out_count, void *workspace, size_t workspace_bytes,
+                     ms_stream_t stream);
+int ms_cluster_pairs_apply(int64_t *nbr_idx, float *nbr_score, int64_t n, int k, const int64_t *edge_src, int64_t *edge_dst,
+                           float *edge_score, int64_t m, const int32_t *lengths, float min_score, float mincov,
+                           const uint8_t *keep, int64_t count, const void *workspace, size_t workspace_bytes,
+                           int64_t *out_removed, ms_stream_t stream);
+int ms_cluster_pairs_find(const int64_t *a, const int64_t *b, int64_t cnt, const int32_t *lengths, int64_t n,
+                          const void *workspace, size_t workspace_bytes, int64_t *out_slot, ms_stream_t stream);
+
 /* The score matrices of the multi-domain search's `exhaustive_cosine` mode: step 3 of dbsearch_fulllength.py (:468-483) with
  * the search's own score in place of TM-align -- the "embscore mode" that file leaves as a TODO (:202-203, :558-571).
  * Candidate c = cand[c] = {q0, nqd, t_off, nhd} is one (query chain, target chain) pair: its query domains are rows

@@ -82,6 +82,10 @@ SIGNATURES = {
     "ms_cluster_greedy_edges": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ms_cluster_components_workspace_bytes": (_sz, [_i64]),
     "ms_cluster_components": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ms_cluster_pairs_workspace_bytes": (_sz, [_i64, _int, _i64]),
+    "ms_cluster_pairs": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ms_cluster_pairs_apply": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "ms_cluster_pairs_find": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp, _vp]),
     "ms_threshold_edges_workspace_bytes": (_sz, [_i64, _int]),
     "ms_threshold_edges": (_int, [_vp, _i64, _i64, _vp, _int, _int, _vp, _vp, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ms_md_chain_scores_workspace_bytes": (_sz, [_int]),

@@ -21,15 +21,14 @@
 // assign step get a second launch over them, with i read instead of derived from the entry's place; ms_cluster_greedy is that
 // call with m == 0 -- the launches it always made, in their order.
 //
-// How the file is laid out: where a directed entry comes from is an ENTRY SOURCE (ms_cl_lists, ms_cl_edges), and every per-entry
+// How the file is laid out: where a directed entry comes from is an ENTRY SOURCE (ms_cl_lists, ms_cl_edges; they, the validity rule and
+// the priority live in ms_cluster_entries.h, which ms_cluster_pairs.hip reads the same graph through), and every per-entry
 // step -- mark and assign here, hook and link of ms_cluster_components below -- is ONE kernel template over the source, launched
 // over the lists and then over the extras by MS_CL_LAUNCH_ENTRIES.  The three entry points share their argument checks
 // (ms_cl_check_args), the host loop over the rounds (ms_cl_rounds) and the read-back behind the finish launch (ms_cl_read_head).
 // Another way of reading the graph is another per-entry function.
-#include "ms_common.h"
+#include "ms_cluster_entries.h"
 
-#define MS_CL_THREADS 256
-#define MS_CL_MAX_BLOCKS (1 << 20)     // grid-stride above this many workgroups (2^28 threads: inside HIP's 2^32 per launch)
 #define MS_CL_GROUP 4                  // rounds enqueued between two looks at the undecided counts
 #define MS_CL_HEAD_BYTES 64            // counters in front of the per-row arrays
 
@@ -65,22 +64,7 @@ static inline ms_cl_view ms_cl_carve(void *workspace, int64_t n) {
     return v;
 }
 
-// Priority: the longer domain, the smaller row on equal length.
-__device__ __forceinline__ bool ms_cl_before(int32_t la, int64_t a, int32_t lb, int64_t b) { return la > lb || (la == lb && a < b); }
-
 __device__ __forceinline__ bool ms_cl_is_rep(uint8_t st) { return st >= MS_CL_REP_NEW; }
-
-// A directed entry i->j counts when j is a row other than i, the score is a number at or above min_score and the shorter
-// domain covers mincov of the longer one (fp32, this operand order).  lengths[j] is read only behind the range check.
-__device__ __forceinline__ bool ms_cl_valid(int64_t i, int64_t j, float s, int64_t n, const int32_t *lengths, int32_t li,
-                                            float min_score, float mincov, int32_t *lj_out) {
-    if (j < 0 || j >= n || j == i) return false;
-    if (!(s >= min_score)) return false;                                  // (NaN fails every comparison)
-    const int32_t lj = lengths[j];
-    *lj_out = lj;
-    const int32_t lmin = li < lj ? li : lj, lmax = li < lj ? lj : li;
-    return (float)lmin >= mincov * (float)lmax;
-}
 
 // {score, row} as one unsigned key: a larger score wins, then the smaller row; -0.0 ranks as +0.0; never 0 for a real entry.
 __device__ __forceinline__ unsigned long long ms_cl_key(float s, int64_t row) {
@@ -88,47 +72,6 @@ __device__ __forceinline__ unsigned long long ms_cl_key(float s, int64_t row) {
     b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     return ((unsigned long long)b << 32) | (unsigned long long)(~(uint32_t)row);
 }
-
-// A grid-stride pass over `total` entries: the thread works on entry e = base + thread.
-#define MS_CL_FOR_ENTRIES(total)                                                                                   \
-    for (int64_t base = (int64_t)blockIdx.x * MS_CL_THREADS; base < (total); base += (int64_t)gridDim.x * MS_CL_THREADS)
-
-// The row i of entry base + thread of the [n,k] lists (one 64-bit division per workgroup and pass, a 32-bit one per thread).
-__device__ __forceinline__ int64_t ms_cl_entry_row(int64_t base, int k) {
-    const int64_t row0 = base / k;
-    const uint32_t local = (uint32_t)(base - row0 * k) + threadIdx.x;      // < k + 256
-    return row0 + (int64_t)(local / (uint32_t)k);
-}
-
-// The two ENTRY SOURCES, passed to the per-entry kernels by value: entry e of total() is i -> dst[e] with score[e], and row(base) is
-// the i of the thread's entry e = base + thread, or -1: no such entry, or an i outside [0, n) -- nothing may be looked up with it.
-struct ms_cl_lists {                   // the [n,k] lists: i is DERIVED from the entry's place
-    const int64_t *__restrict__ dst;
-    const float *__restrict__ score;
-    int64_t n;
-    int k;
-    static constexpr bool owns_cut = true;                                 // an entry that is not valid sets cut[i]
-    __device__ __forceinline__ int64_t total() const { return n * (int64_t)k; }
-    __device__ __forceinline__ int64_t row(int64_t base) const {
-        const int64_t i = ms_cl_entry_row(base, k);
-        return i < n ? i : -1;
-    }
-};
-
-struct ms_cl_edges {                   // the m extra entries src[e] -> dst[e]: i is READ, and range-checked before it is used
-    const int64_t *__restrict__ src, *__restrict__ dst;
-    const float *__restrict__ score;
-    int64_t n, m;
-    static constexpr bool owns_cut = false;                                // (`cut`, and with it out_saturated, is the lists' alone:
-                                                                           // an extra entry that is not valid says nothing about a LIST)
-    __device__ __forceinline__ int64_t total() const { return m; }
-    __device__ __forceinline__ int64_t row(int64_t base) const {
-        const int64_t e = base + threadIdx.x;
-        if (e >= m) return -1;
-        const int64_t i = src[e];
-        return i >= 0 && i < n ? i : -1;
-    }
-};
 
 // The mark step of ONE directed entry i -> j with score s (i inside [0, n)): what the header comment calls push, pull and cover.
 __device__ __forceinline__ void ms_cl_mark_entry(int64_t i, const int64_t *__restrict__ jp, const float *__restrict__ sp, int64_t n,
@@ -244,11 +187,6 @@ __global__ __launch_bounds__(MS_CL_THREADS) void ms_cluster_finish_kernel(int64_
 extern "C" size_t ms_cluster_workspace_bytes(int64_t n) {
     if (n < 1 || n > 2147483647LL) return 0;
     return MS_CL_HEAD_BYTES + 8 * (size_t)n + 4 * ms_cl_rows_bytes(n);
-}
-
-static inline unsigned ms_cl_blocks(int64_t items) {
-    const int64_t b = (items + MS_CL_THREADS - 1) / MS_CL_THREADS;
-    return (unsigned)(b < MS_CL_MAX_BLOCKS ? b : MS_CL_MAX_BLOCKS);
 }
 
 // What all three entry points are handed: the lists ([n,k]; lists_only: k >= 1 and never NULL, else k >= 0), the extra entries

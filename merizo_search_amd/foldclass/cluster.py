@@ -14,6 +14,11 @@ graph ("The complete graph").
 (ms_cluster_components; DESIGN.md section 5.8, "Connected components"): the longest domain of a component represents it, and the
 third column is each member's strongest own link.
 
+`-m/--mintm` (run_cluster(mintm=...)) verifies every edge with TM-align before anything is clustered (DESIGN.md section 5.8,
+"Structure-verified edges"): ms_cluster_pairs reads the distinct unordered pairs off the lists and extras on the device, the
+batched aligner scores them, ms_cluster_pairs_apply takes the pairs below the cut out of the graph in both directions, and the
+cluster call runs on what is left.  The greedy TSV gains a fourth column, the TM-score of (representative, member).
+
 The clustering's definition is the header's (include/merizo_search_amd.h, ms_cluster_greedy): an edge needs a cosine at or
 above --mincos in either direction and the shorter domain to cover --mincov of the longer; the longer domain is the
 representative (cd-hit's greedy order), every other domain goes to its best-scoring adjacent representative.  Coverage is that
@@ -36,16 +41,19 @@ from .target import Target, score_mode
 logger = logging.getLogger(__name__)
 
 
-def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, header: bool, score_name: str = "emb_score") -> None:
+def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, header: bool, score_name: str = "emb_score",
+                      tm_score: Optional[np.ndarray] = None) -> None:
     """Clusters by the representative's row; its own line first, then its members by row.  The cosine column is formatted as
-    results.write_search_results formats emb_score; score_name: its name in the header line."""
+    results.write_search_results formats emb_score; score_name: its name in the header line.  tm_score: a fourth column
+    `tm_score` per row, formatted the same way (`cluster --mintm`, greedy mode)."""
     rows = np.arange(rep.shape[0], dtype=np.int64)
     order = np.lexsort((rows, rows != rep, rep))
     with open(path, "w") as handle:
         if header:
-            handle.write("representative\tmember\t%s\n" % score_name)
+            handle.write("representative\tmember\t%s%s\n" % (score_name, "" if tm_score is None else "\ttm_score"))
         for r in order:
-            handle.write("%s\t%s\t%s\n" % (names[int(rep[r])], names[int(r)], "{:.4f}".format(rep_score[r])))
+            tm = "" if tm_score is None else "\t" + "{:.4f}".format(tm_score[r])
+            handle.write("%s\t%s\t%s%s\n" % (names[int(rep[r])], names[int(r)], "{:.4f}".format(rep_score[r]), tm))
 
 
 MAX_EDGES = 2 ** 27        # directed entries the edge pass of --complete may hold: a memory budget (20 B each: 2.7 GB), not a measurement
@@ -97,10 +105,67 @@ def _edge_pass(engine, target: Target, qdb, in_place: bool, full_rows: np.ndarra
     return buf[0][:used], buf[1][:used], buf[2][:used], found, rescored
 
 
+def _verify_edges(engine, qdb, graph, lengths: np.ndarray, mincos: float, mincov: float, mintm: float, fastmode: bool,
+                  tm_batchsize: int):
+    """The TM-align stage of `cluster --mintm` on graph = (nbr_idx, nbr_score, edge_src, edge_dst, edge_score), device tensors that
+    are EDITED: the distinct canonical pairs (engine.cluster_pairs: chain 1 is the would-be representative) are aligned in batches of
+    tm_batchsize, longest first -- each batch fetches the coordinates and sequences of its rows once (Records) and converts each
+    row's coordinates once (tmalign.pdb_values) -- and a pair is kept when the aligner reports TM_OK and max(qtm, ttm), on the
+    5-decimal values tmalign.printed_values returns (what `search --tmalign_backend hip` compares), is >= mintm.  A pair with a chain
+    of <= 5 residues or a non-finite coordinate is not aligned and not kept.  engine.cluster_pairs_apply then takes the pairs that are
+    not kept out of the lists and extras.  -> (workspace holding the set, tm float64 [pairs] by slot (max(qtm, ttm), -1.0 where not
+    aligned), info: saturated (before the edit), tm_pairs, tm_rejected_pairs (not kept), tm_unaligned_pairs (of those: never aligned
+    or refused by the aligner), tm_removed_entries (directed entries overwritten))."""
+    from .._lib import TM_OK
+    from . import tmalign
+    torch = engine.torch
+    pairs, counts, workspace = engine.cluster_pairs(*graph, lengths, mincos, mincov)
+    count, saturated = (int(c) for c in counts.cpu().numpy())
+    pairs = pairs[:count].cpu().numpy().astype(np.int64)
+    tm = np.full(count, -1.0, dtype=np.float64)
+    keep = np.zeros(count, dtype=np.uint8)
+    unaligned = 0
+    work = lengths[pairs[:, 0]].astype(np.int64) * lengths[pairs[:, 1]].astype(np.int64)
+    order = np.argsort(-work, kind="stable")                              # longest first, as the aligner orders a launch
+    for b0 in range(0, count, int(tm_batchsize)):
+        slots = order[b0:b0 + int(tm_batchsize)]
+        rows, local = np.unique(pairs[slots], return_inverse=True)
+        local = local.reshape(-1, 2)
+        coords, seqs = qdb.coords(rows), qdb.seqs(rows)
+        missing = [int(r) for r, c in zip(rows, coords) if c is None]
+        if missing:
+            _refuse("cluster --mintm needs the coordinates of every row: database row %d has none." % missing[0])
+        with np.errstate(over="ignore"):                                  # (the fp32 cast turns |v| > 3.4e38 into inf)
+            good = np.array([len(c) > 5 and bool(np.isfinite(np.asarray(c, dtype=np.float32)).all()) for c in coords], dtype=bool)
+        alignable = good[local[:, 0]] & good[local[:, 1]]
+        unaligned += int((~alignable).sum())
+        if not alignable.any():
+            continue
+        used = np.unique(local[alignable])                                # only the rows that are aligned are converted and uploaded
+        place = np.full(len(rows), -1, dtype=np.int64)
+        place[used] = np.arange(used.shape[0])
+        got = engine.tmalign_batch([tmalign.pdb_values(coords[r]) for r in used], [seqs[r] for r in used], place[local[alignable]],
+                                   fast=bool(fastmode))
+        for p, slot in enumerate(slots[alignable]):
+            if got["status"][p] != TM_OK:
+                unaligned += 1
+                continue
+            v = tmalign.printed_values(got["qtm"][p], got["ttm"][p], got["rmsd"][p], got["n_ali8"][p], got["n_identical"][p])
+            tm[slot] = max(v["qtm"], v["ttm"])
+            keep[slot] = tm[slot] >= mintm
+    if unaligned:
+        logger.warning("cluster: %d of %d pairs have a chain of 5 residues or fewer or with a non-finite coordinate: TM-align cannot "
+                       "score them, and they are treated as below --mintm." % (unaligned, count))
+    removed = engine.cluster_pairs_apply(*graph, lengths, mincos, mincov, engine.to_device(keep), workspace)
+    return workspace, tm, {"saturated": saturated, "tm_pairs": count, "tm_rejected_pairs": int(count - keep.sum()),
+                           "tm_unaligned_pairs": unaligned, "tm_removed_entries": int(removed.cpu().numpy()[0])}
+
+
 def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 20, mincos: Optional[float] = None,
                 mincov: float = 0.7, query_batchsize: int = 4096, search_batchsize: int = 262144, header: bool = False,
                 engine=None, timings: Optional[dict] = None, complete: bool = False, max_edges: int = MAX_EDGES,
-                edge_room: int = 2 ** 20, mode: str = "greedy"):
+                edge_room: int = 2 ** 20, mode: str = "greedy", mintm: Optional[float] = None, fastmode: bool = False,
+                tm_batchsize: int = 65536):
     """Cluster the rows of database `db_name` and write `<output>_cluster.tsv`.  topk: neighbours kept per row (the search
     fetches topk + 1 and drops the row itself); a row whose topk entries all count as edges may have neighbours the clustering
     never sees (`saturated`: raise -k).  Under several ranks every rank scans its shard of the rows; rank 0 alone keeps the
@@ -116,7 +181,13 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     mode: 'greedy' (above) or 'connected': the connected components of the same graph (ms_cluster_components on the lists, plus the
     edge pass's entries under complete) -- rep[i] the longest row of i's component, rep_score[i] the row's strongest own link (the
     TSV's third column is then headed `link_score`); info holds `n_components` in place of `n_reps`, and `largest`, the rows of the
-    largest component.  Without complete a list that -k cut short may split a component.  info gains `mode` in both."""
+    largest component.  Without complete a list that -k cut short may split a component.  info gains `mode` in both.
+    mintm: None (nothing changes), or the TM-score in (0, 1] an edge must reach: on rank 0, once the lists (and under complete the
+    gathered extras) are on the device, _verify_edges aligns every distinct pair (fastmode: TM-align -fast; tm_batchsize: pairs per
+    launch) and takes the pairs below mintm out of the graph before the cluster call, which is unchanged.  info['saturated'] is then
+    the count BEFORE the edit, info gains tm_pairs, tm_rejected_pairs, tm_unaligned_pairs and tm_removed_entries, timings 'tm_ms';
+    the greedy TSV gains a fourth column `tm_score`: max(qtm, ttm) of (representative, member), 1.0000 on a representative's line.
+    The connected mode keeps its three columns (a member need not be adjacent to its representative)."""
     from .dbquery import QueryDB
 
     if engine is None:
@@ -132,6 +203,10 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         _refuse("cluster mode must be 'greedy' or 'connected', got %r." % (mode,))
     if int(max_edges) < 1 or int(edge_room) < 1:
         _refuse("--max_edges must be >= 1, got %r." % (max_edges,))
+    if mintm is not None and not 0.0 < float(mintm) <= 1.0:               # (NaN fails both comparisons)
+        _refuse("-m/--mintm must lie in (0, 1], got %r." % (mintm,))
+    if mintm is not None and int(tm_batchsize) < 1:
+        _refuse("--tm_batchsize must be >= 1, got %r." % (tm_batchsize,))
     _require_database(db_name)
     target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
     qdb = QueryDB(db_name, loaded=target_db if not target_db["faiss"] else None)
@@ -189,8 +264,14 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         times.finish()
         qdb.close()
         return None, None, info
-    t0 = times.mark()
     e_src, e_dst, e_score = edges if edges is not None else (None, None, None)
+    verified = None
+    if mintm is not None:
+        t0 = times.mark()
+        verified = _verify_edges(engine, qdb, (nbr_i, nbr_s, e_src, e_dst, e_score), lengths, float(mincos), float(mincov), float(mintm),
+                                 fastmode, tm_batchsize)
+        times.add("tm", t0)
+    t0 = times.mark()
     if mode == "connected":
         rep, rep_score, found = engine.cluster_components(nbr_i, nbr_s, e_src, e_dst, e_score, lengths, float(mincos), float(mincov))
     elif complete:
@@ -202,7 +283,18 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     rep, rep_score = rep.cpu().numpy(), rep_score.cpu().numpy()
     sizes = np.bincount(rep, minlength=n)
     info.update(found, singletons=int((sizes == 1).sum()))
-    write_cluster_tsv(out_path, qdb.names(0, n), rep, rep_score, header, "link_score" if mode == "connected" else "emb_score")
+    tm_score = None
+    if verified is not None:
+        workspace, tm, tm_info = verified
+        info.update(tm_info)                                              # ('saturated': the lists as the search left them)
+        logger.info("cluster: TM-align on %d distinct pairs: %d below --mintm %s (%d of them not alignable), %d directed entries removed"
+                    % (info["tm_pairs"], info["tm_rejected_pairs"], mintm, info["tm_unaligned_pairs"], info["tm_removed_entries"]))
+        if mode == "greedy":                                              # (a member is adjacent to its representative: the pair has a slot)
+            members = np.nonzero(rep != np.arange(n))[0]
+            slots = engine.cluster_pairs_find(rep[members], members, lengths, workspace).cpu().numpy()
+            tm_score = np.ones(n, dtype=np.float64)
+            tm_score[members] = np.where(slots >= 0, tm[np.maximum(slots, 0)], -1.0) if tm.shape[0] else -1.0
+    write_cluster_tsv(out_path, qdb.names(0, n), rep, rep_score, header, "link_score" if mode == "connected" else "emb_score", tm_score)
     qdb.close()
     if mode == "connected":
         info["largest"] = int(sizes.max())

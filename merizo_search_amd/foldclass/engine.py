@@ -21,6 +21,9 @@ Engine interface (tensors are torch tensors on the engine's device):
     merge_gathered(PackedExchange)                          -> (scores [nq,k], idx [nq,k])  multi-rank merge
     topk_drop_ranges(scores, idx, lo, hi, kout, min_score)  -> (scores [nq,kout], idx [nq,kout], count int32 [nq]): the lists without
                                                                the rows [lo[q], hi[q]) and without scores below min_score (db-search)
+    cluster_pairs / cluster_pairs_apply / cluster_pairs_find  the distinct pairs of the cluster graph, a verdict per pair written back
+                                                               onto it, the slot of given pairs (`cluster --mintm`)
+    tmalign_batch(coords_list, seqs, pairs, fast)           -> dict of numpy arrays per pair (qtm, ttm, rmsd, n_ali8, n_identical, status)
     md_chain_scores(db, q, mode, cand, trows, mat_off, min_score, lengths, qlen, mincov) -> (scores [total], match int32 [ncand,2]):
                                                                the multi-domain search's score matrices in the search's own arithmetic
     md_best_mappings(scores, cand, mat_off)                 -> (status [ncand,2], total int64 [ncand,2], path [ncand,2,64], cell [ncand,2,64]):
@@ -260,6 +263,23 @@ class HipEngine:
     def cluster_components(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0):
         """Connected components of the same graph (ms_cluster_components) -> (rep, link_score, info)."""
         return self._ops.cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
+
+    def cluster_pairs(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, cap=None):
+        """The distinct canonical pairs of the graph the cluster calls read (ms_cluster_pairs) -> (pairs int32 [cap,2], count int64
+        [2] = (distinct pairs, rows whose list entries are all valid), workspace): device tensors, nothing read back."""
+        return self._ops.cluster_pairs(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov, cap=cap)
+
+    def cluster_pairs_apply(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float, keep, workspace):
+        """The pairs with keep[slot] == 0 taken out of the lists and extras in place (ms_cluster_pairs_apply) -> removed int64 [1]."""
+        return self._ops.cluster_pairs_apply(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov, keep, workspace)
+
+    def cluster_pairs_find(self, a, b, lengths, workspace):
+        """The slots of the unordered pairs {a[e], b[e]} in cluster_pairs' set (ms_cluster_pairs_find) -> int64 [cnt], -1: none."""
+        return self._ops.cluster_pairs_find(a, b, lengths, workspace)
+
+    def tmalign_batch(self, coords_list, seqs, pairs, fast: bool = False) -> dict:
+        """TM-align of the pairs (s1, s2) of a structure list in one launch (ops.tmalign_batch on this engine's device)."""
+        return self._ops.tmalign_batch(coords_list, seqs, pairs, fast=fast, device=self.device)
 
     def threshold_edges(self, db, q, mode: str, min_score: float, lo=None, hi=None, row_offset: int = 0, row_norm_bound=None, out=None,
                         stats=None):

@@ -506,11 +506,10 @@ def cluster_greedy(nbr_idx, nbr_score, lengths, min_score: float, mincov: float 
                     mincov, out, workspace)
 
 
-def _cluster(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edges, lengths, min_score, mincov, out, workspace):
-    """The three cluster calls: one argument check, one call shape (`entry`, `workspace_bytes`: the library's names; count_key: what
-    the first count is called in info).  edges: (edge_src, edge_dst, edge_score), or None for ms_cluster_greedy, whose entry point
-    takes no edge arguments and needs lists of k >= 1."""
-    import ctypes
+def _cluster_graph(who, nbr_idx, nbr_score, edges, lengths):
+    """The graph arguments every cluster call takes, checked once: lists int64 / float32 [n,k] or None None, edges = (edge_src,
+    edge_dst, edge_score) int64 / int64 / float32 [m] or None (an entry point without edge arguments: its lists need k >= 1),
+    lengths int32 [n] (a tensor, or a host array that is uploaded).  -> (lengths tensor, n, k, m)."""
     torch = _lib.require_gpu()
     edge_src, edge_dst, edge_score = edges or (None, None, None)
     device = next((x.device for x in (nbr_score, edge_score, lengths) if isinstance(x, torch.Tensor) and x.is_cuda), None)
@@ -539,14 +538,32 @@ def _cluster(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edges, 
         m = int(edge_src.numel())
         if edge_dst.numel() != m or edge_score.numel() != m:
             raise MerizoHipError(f"{who}: edge_src, edge_dst and edge_score must have one length")
+    return t, n, k, m
+
+
+def _graph_call(entry, nbr_idx, nbr_score, edges, t, n, k, m, min_score, mincov, others, rest):
+    """One call shape for every entry point that takes the graph: lists, n, k[, extras, m], lengths, min_score, mincov, then `rest`
+    (a function of the stream) -- on the device of the graph's tensors and of `others`."""
+    edge_src, edge_dst, edge_score = edges or (None, None, None)
+    extra = () if edges is None else (ptr(edge_src) if m else 0, ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m)
+    with _on(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, t, *others) as dev:
+        check(getattr(_lib.load(), entry)(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, *extra, ptr(t), float(min_score),
+                                          float(mincov), *rest(dev.stream)), entry)
+
+
+def _cluster(who, entry, workspace_bytes, count_key, nbr_idx, nbr_score, edges, lengths, min_score, mincov, out, workspace):
+    """The three cluster calls: one argument check (_cluster_graph), one call shape (`entry`, `workspace_bytes`: the library's names;
+    count_key: what the first count is called in info).  edges: (edge_src, edge_dst, edge_score), or None for ms_cluster_greedy,
+    whose entry point takes no edge arguments and needs lists of k >= 1."""
+    import ctypes
+    torch = _lib.require_gpu()
+    t, n, k, m = _cluster_graph(who, nbr_idx, nbr_score, edges, lengths)
     rep, rep_score = _outputs(who, ((torch.int64, (n,)), (torch.float32, (n,))), out, t.device)
     workspace = _workspace(who, workspace_bytes, (n,), workspace, t.device)
     n_reps, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
-    extra = () if edges is None else (ptr(edge_src) if m else 0, ptr(edge_dst) if m else 0, ptr(edge_score) if m else 0, m)
-    with _on(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, t, rep, rep_score, workspace) as dev:
-        check(getattr(_lib.load(), entry)(ptr(nbr_idx) if k else 0, ptr(nbr_score) if k else 0, n, k, *extra, ptr(t), float(min_score),
-                                          float(mincov), ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds),
-                                          ctypes.addressof(saturated), ptr(workspace), workspace.numel(), dev.stream), entry)
+    _graph_call(entry, nbr_idx, nbr_score, edges, t, n, k, m, min_score, mincov, (rep, rep_score, workspace),
+                lambda stream: (ptr(rep), ptr(rep_score), ctypes.addressof(n_reps), ctypes.addressof(rounds), ctypes.addressof(saturated),
+                                ptr(workspace), workspace.numel(), stream))
     return rep, rep_score, {count_key: int(n_reps.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
 
 
@@ -570,6 +587,80 @@ def cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengt
     ms_cluster_components_workspace_bytes(n)."""
     return _cluster("cluster_components", "ms_cluster_components", "ms_cluster_components_workspace_bytes", "n_components", nbr_idx,
                     nbr_score, (edge_src, edge_dst, edge_score), lengths, min_score, mincov, out, workspace)
+
+
+def _pairs_workspace(who, n, k, m, workspace, device):
+    if n * k + m >= 2 ** 31:
+        raise MerizoHipError(f"{who}: n k + m = {n * k + m} directed entries, the set holds fewer than 2^31 (MS_ERR_RANGE (-4))")
+    return _workspace(who, "ms_cluster_pairs_workspace_bytes", (n, k, m), workspace, device)
+
+
+def cluster_pairs(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, cap=None, out=None,
+                  workspace=None):
+    """The distinct canonical pairs (a, b) -- a the higher-priority row -- of the graph cluster_greedy_edges clusters, with its
+    arguments (ms_cluster_pairs: the definition is the header's).  cap: slots of the pair buffer (default n k + m: every pair
+    fits; 0: count only).  -> (pairs int32 [cap,2], count int64 [2], workspace), device tensors: count[0] the distinct pairs (exact
+    whatever cap), count[1] the rows whose k list entries are all valid; pairs[:min(count[0], cap)] hold the pairs in unspecified
+    order; the workspace holds the set for cluster_pairs_apply / cluster_pairs_find.  Asynchronous: nothing is read back.
+    out: optional preallocated (pairs, count); workspace: optional uint8 tensor of ms_cluster_pairs_workspace_bytes(n, k, m)."""
+    who = "cluster_pairs"
+    torch = _lib.require_gpu()
+    edges = (edge_src, edge_dst, edge_score)
+    t, n, k, m = _cluster_graph(who, nbr_idx, nbr_score, edges, lengths)
+    if cap is None:                                      # (a caller's pair buffer says what its cap is)
+        cap = n * k + m if out is None or not isinstance(out[0], torch.Tensor) else int(out[0].shape[0])
+    cap = int(cap)
+    if cap < 0:
+        raise MerizoHipError(f"{who}: need cap >= 0, got {cap}")
+    pairs, count = _outputs(who, ((torch.int32, (cap, 2)), (torch.int64, (2,))), out, t.device)
+    workspace = _pairs_workspace(who, n, k, m, workspace, t.device)
+    _graph_call("ms_cluster_pairs", nbr_idx, nbr_score, edges, t, n, k, m, min_score, mincov, (pairs, count, workspace),
+                lambda stream: (ptr(pairs) if cap else 0, cap, ptr(count), ptr(workspace), workspace.numel(), stream))
+    return pairs, count, workspace
+
+
+def cluster_pairs_apply(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float, keep, workspace):
+    """Take the pairs with keep[slot] == 0 out of the graph IN PLACE, in both directions (ms_cluster_pairs_apply: the definition is
+    the header's): the graph arguments and thresholds of the cluster_pairs call that left `workspace`, keep uint8 [count] on the
+    device, indexed by slot.  A valid entry without a verdict (pair not in the set, slot >= count or >= that call's cap) is removed
+    too.  -> the directed entries removed, a device tensor int64 [1].  Asynchronous."""
+    who = "cluster_pairs_apply"
+    torch = _lib.require_gpu()
+    edges = (edge_src, edge_dst, edge_score)
+    t, n, k, m = _cluster_graph(who, nbr_idx, nbr_score, edges, lengths)
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype != torch.uint8 or keep.dim() != 1 or not keep.is_contiguous():
+        raise MerizoHipError(f"{who}: keep: expected a contiguous uint8 CUDA/HIP tensor [count]")
+    if workspace is None:
+        raise MerizoHipError(f"{who}: needs the workspace cluster_pairs returned")
+    workspace = _pairs_workspace(who, n, k, m, workspace, t.device)
+    removed = torch.empty((1,), dtype=torch.int64, device=t.device)
+    count = int(keep.numel())
+    _graph_call("ms_cluster_pairs_apply", nbr_idx, nbr_score, edges, t, n, k, m, min_score, mincov, (keep, workspace, removed),
+                lambda stream: (ptr(keep) if count else 0, count, ptr(workspace), workspace.numel(), ptr(removed), stream))
+    return removed
+
+
+def cluster_pairs_find(a, b, lengths, workspace):
+    """The slot of every unordered pair {a[e], b[e]} in the set cluster_pairs left in `workspace` (ms_cluster_pairs_find): a / b
+    int64 [cnt] tensors or host arrays, lengths int32 [n] as in that call.  -> slot int64 [cnt] on the device; -1: not in the set,
+    a row outside [0, n), or a[e] == b[e].  Asynchronous."""
+    who = "cluster_pairs_find"
+    torch = _lib.require_gpu()
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda:
+        raise MerizoHipError(f"{who}: needs the workspace cluster_pairs returned")
+    t = _int_desc(lengths, np.int32, "lengths", workspace.device, who)
+    n = int(t.numel())
+    if n < 1:
+        raise MerizoHipError(f"{who}: lengths: expected n >= 1 integers, got none")
+    a = _int_desc(a, np.int64, "a", workspace.device, who)
+    b = _int_desc(b, np.int64, "b", workspace.device, who, length=int(a.numel()))
+    workspace = _pairs_workspace(who, n, 0, 0, workspace, workspace.device)
+    cnt = int(a.numel())
+    slot = torch.empty((cnt,), dtype=torch.int64, device=workspace.device)
+    with _on(a, b, t, workspace, slot) as dev:
+        check(_lib.load().ms_cluster_pairs_find(ptr(a) if cnt else 0, ptr(b) if cnt else 0, cnt, ptr(t), n, ptr(workspace), workspace.numel(),
+                                                ptr(slot) if cnt else 0, dev.stream), "ms_cluster_pairs_find")
+    return slot
 
 
 THRESHOLD_EDGES_CAP = 1 << 16      # slots of threshold_edges' first launch when the caller names none (it launches again beyond)

@@ -99,7 +99,8 @@ size_t ms_ip_topk_workspace_bytes(int64_t n, int nq, int k);
  * Output: out_scores float32 [nq,k], out_idx int64 [nq,k] = row_offset + row, sorted by score
  * descending, ties by ascending row (torch.topk / faiss leave tie order unspecified).  If
  * n < k the tail is (-inf, -1), like faiss.  Any k >= 1 is accepted (k > 64 costs
- * ceil(k/64) scans).  n must be < 2^31. */
+ * ceil(k/64) scans; ms_ip_topk_large below returns the same lists from one filtered pass).
+ * n must be < 2^31. */
 int ms_ip_topk(const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
                const float *inv_norm, const float *lengths, const float *qlen, float mincov, float *out_scores,
                int64_t *out_idx, void *workspace, size_t workspace_bytes, ms_stream_t stream);
@@ -121,6 +122,61 @@ int ms_ip_topk_scan(const float *db, int64_t n, const float *q, int nq, int k, i
                     ms_stream_t stream);
 int ms_ip_topk_finish(int64_t n, int64_t row_offset, int nq, int k, float *out_scores, int64_t *out_idx,
                       void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
+/* ---- large k: the lists of ms_ip_topk for 64 < k <= MS_LARGE_K_MAX from ONE filtered pass over the rows ----
+ *
+ * ms_ip_topk serves k > 64 with ceil(k/64) fp32 scans.  This entry point returns the same [nq,k] lists, bit for bit, from one
+ * fp32 read (the bound) and one read behind the 16-bit matrix pipe (the emission), for the queries it can serve; it says per
+ * query whether it did.
+ * EXACTNESS.  For query q take ANY threshold t[q] and put every row whose exact score is >= t[q] into a bin of
+ * MS_LARGE_K_CAND slots.  If the bin received at least k rows and did not overflow, the best k of the bin in the search's total
+ * order (score descending, row ascending, -0.0 == +0.0) are the best k of the whole database: every row outside the bin scores
+ * below t[q], hence below k rows of the bin.  Nothing else is assumed of t[q].  The call's own t[q]: the rows are cut into
+ * G = ceil(k/64) contiguous groups, ms_ip_topk (k = 64, the call's mode and mask) runs on each -- one read of the database in
+ * all -- and t[q] is the k-th largest of those 64 G scores: at least k real rows reach it.  The emission is ms_threshold_edges'
+ * with a cut per query: a cell whose fp16 score is below t[q] - E * row_norm_bound * |q| is proved below the cut, every other
+ * cell is scored with the exact chain of 128 fmaf (ms_ip_topk's score, bit for bit), masked, and emitted iff score >= t[q]
+ * (NaN fails, +inf passes, -0.0 counts as 0.0).  A masked search filters on the UNMASKED score; that is sound only while
+ * t[q] > 0 (a masked row scores +-0.0, which a non-positive cut would have to emit): a masked query whose t[q] is not > 0 is
+ * status 2 and emits nothing.
+ *   mode             MS_MODE_IP_PRENORM, MS_MODE_IP_NORMQ, or MS_MODE_COSINE_UNIT with or without the length mask (lengths float32
+ *                    [n] and qlen float32 [nq] go together, NULL NULL = no mask; NULL in the other modes).  MS_MODE_COSINE_RAW:
+ *                    MS_ERR_ARG, as in the prefiltered search.
+ *   row_norm_bound   as in ms_threshold_edges: NaN, <= 0 or outside [2^-40, 2^40] is MS_ERR_RANGE; it need not hold (a row above it,
+ *                    or a query the fp16 filter cannot take, has all its cells scored exactly).
+ *   out_scores / out_idx   ms_ip_topk's contract exactly: float32 / int64 [nq,k], row_offset + row, (-inf, -1) padding, +inf scores
+ *                    first, NaN and -inf never returned.
+ *   out_status       int32 [nq]: 0 = row q of the outputs is final.  1 = the bin overflowed: row q of the outputs is (-inf, -1)
+ *                    throughout and out_lb[q] is the k-th best of the MS_LARGE_K_CAND buffered entries -- real rows with exact
+ *                    scores, so a valid and tighter threshold for a second call.  2 = not served, the caller must use ms_ip_topk
+ *                    for this query (row q is (-inf, -1) throughout): t[q] is NaN or -inf (fewer than k returnable rows); the
+ *                    bin overflowed for a query the fp16 filter cannot take; a masked search whose t[q] is not > 0; a given
+ *                    threshold that left the bin below k entries.
+ *   out_lb           float32 [nq]: status 0 or 2: the threshold that was used; status 1: see above.
+ *   lb_in            NULL, or float32 [nq] thresholds that replace the call's own (the second round: lb_in = the out_lb of the
+ *                    first).  A NaN or -inf entry is status 2; one that is too high (fewer than k rows reach it) is status 2,
+ *                    never a wrong answer.
+ *   out_stats        int64 [4], may be NULL: [0] [1] [2] the queries with status 0, 1, 2, [3] the cells sent to the exact chain;
+ *                    written by the call's last launch, the counters reset by the call.
+ * Shapes the route does not take -- k <= 64, k > MS_LARGE_K_MAX, n < 128 G (n = 0 included) -- are answered by ms_ip_topk inside
+ * the call: status 0 for every query, out_lb = -inf, out_stats[3] = -1 (lb_in is ignored).  The workspace covers that route too:
+ * ms_ip_topk_large_workspace_bytes(n, nq, k) bytes, 16-byte aligned (0 for nq < 1, n < 0, k < 1 or n >= 2^31 - 1).
+ * MS_ERR_ARG: another mode, nq < 1, n < 0, k < 1, NULL pointers, lengths / qlen outside MS_MODE_COSINE_UNIT or only one of them,
+ * db or workspace not 16-byte aligned; MS_ERR_RANGE: the bound, n >= 2^31 - 1; MS_ERR_WORKSPACE: a short workspace.  Nothing is
+ * launched on an error.
+ * Asynchronous on `stream`, never allocates, never synchronises.  Every counter lives in the workspace and is reset by the
+ * call: a workspace serves the next call, with another nq or k, without clean-up.  Vector stores and vector atomics only (one
+ * global atomic per emitted cell, one per wave for out_stats[3], one per query for the status counts); no scratch memory.
+ * MS_LARGE_K_CAND = 8192: one 64 KB sort of 8-byte keys in LDS per query.
+ * Backward compatible additions: ms_version() stays 210. */
+#define MS_LARGE_K_MAX 2048   /* 64 G <= 2048 group-list scores per query */
+#define MS_LARGE_K_CAND 8192  /* candidates a query's bin holds */
+size_t ms_ip_topk_large_workspace_bytes(int64_t n, int nq, int k);
+int ms_ip_topk_large(const float *db, int64_t n, int64_t row_offset, const float *q, int nq, int k, int mode,
+                     const float *lengths, const float *qlen, float mincov, float row_norm_bound,
+                     const float *lb_in, float *out_scores, int64_t *out_idx,
+                     int32_t *out_status, float *out_lb, int64_t *out_stats,
+                     void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
 /* ---- the prefiltered search: the same results as ms_ip_topk bit for bit, several times faster for large batches ----
  *

@@ -21,6 +21,8 @@ MODE_IP_NORMQ = 3
 DIM = 128
 PREFILTER_MAX_K = 48       # MS_PREFILTER_MAX_K (include/merizo_search_amd.h): the prefiltered search serves k up to this
 PREFILTER_MIN_ROWS = 65536
+LARGE_K_MAX = 2048         # MS_LARGE_K_MAX: ms_ip_topk_large serves 64 < k <= this
+LARGE_K_CAND = 8192        # MS_LARGE_K_CAND: the candidates a query's bin holds
 
 
 class MerizoHipError(RuntimeError):
@@ -61,6 +63,8 @@ SIGNATURES = {
     "ms_ip_topk_prepare": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
     "ms_ip_topk_scan": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _vp, _vp, _f, _vp, _sz, _vp]),
     "ms_ip_topk_finish": (_int, [_i64, _i64, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "ms_ip_topk_large_workspace_bytes": (_sz, [_i64, _int, _int]),
+    "ms_ip_topk_large": (_int, [_vp, _i64, _i64, _vp, _int, _int, _int, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ms_pf_image_bytes": (_sz, [_i64, _int]),
     "ms_pf_build_image": (_int, [_vp, _i64, _int, _f, _vp, _vp]),
     "ms_pf_err_coef": (_f, [_int]),

@@ -106,6 +106,7 @@ class HipEngine:
         self._state_dict = state_dict
         self._ws = ops.TopKWorkspace(self.device)
         self._pws = ops.PrefilterWorkspace(self.device)
+        self._lws = ops.LargeKWorkspace(self.device)
 
     # -- encoder ---------------------------------------------------------------------
     def load_weights(self, state_dict: dict) -> None:
@@ -168,6 +169,9 @@ class HipEngine:
         if image is not None:
             return ops.ip_topk_prefiltered(rows, q, k, self.UNIT_ROW_BOUND, mode=ops.MODE_COSINE_UNIT, row_offset=row_offset,
                                            workspace=self._pws, image=image, lengths=lengths, qlen=qlen, mincov=mincov)
+        if ops.large_k_serves(rows.shape[0], q.shape[0], k):      # (64 < k: one filtered pass instead of ceil(k/64) scans, same lists)
+            return ops.ip_topk_large(rows, q, k, self.UNIT_ROW_BOUND, mode=ops.MODE_COSINE_UNIT, lengths=lengths, qlen=qlen,
+                                     mincov=mincov, row_offset=row_offset, workspace=self._lws)
         return ops.ip_topk(rows, q, k, mode=ops.MODE_COSINE_UNIT, lengths=lengths, qlen=qlen, mincov=mincov,
                            row_offset=row_offset, workspace=self._ws)
 
@@ -183,6 +187,8 @@ class HipEngine:
         if row_norm_bound is not None and (image is not None or ops.prefilter_serves(db.shape[0], q.shape[0], k)):
             return ops.ip_topk_prefiltered(db, q, k, float(row_norm_bound), mode=mode, row_offset=row_offset, workspace=self._pws,
                                            image=image)
+        if row_norm_bound is not None and ops.large_k_serves(db.shape[0], q.shape[0], k):
+            return ops.ip_topk_large(db, q, k, float(row_norm_bound), mode=mode, row_offset=row_offset, workspace=self._lws)
         return ops.ip_topk(db, q, k, mode=mode, row_offset=row_offset, workspace=self._ws)
 
     def _image_for(self, pf_image, n: int, nq: int, k: int):

@@ -89,6 +89,27 @@ def normalized_database(n: int, seed: int) -> np.ndarray:
     return (db / nrm).astype(np.float32)
 
 
+def family_sorted_database(n: int, nq: int, seed: int, families: int = 50, spread: float = 0.08, subspace: int = 4
+                           ) -> Tuple[np.ndarray, np.ndarray]:
+    """A database ORDERED BY FAMILY, the adversary of a per-group bound: (unit rows float32 [n,128], unit
+    queries float32 [nq,128]).  `families` centres are unit vectors of a `subspace`-dimensional subspace, so the cosines between
+    centres spread over [-1, 1]; family f is the contiguous run of rows [f n / families, (f + 1) n / families), each row
+    normalize(centre + spread * N(0, I)) (|noise| ~ 0.9: rows of a family have cosine ~ 0.55 to each other); query j is drawn the
+    same way from family j % families.  A contiguous group of rows then holds a few families only, and the best rows of a group of
+    far families score far below what most rows of the near families score."""
+    rng = np.random.default_rng(seed)
+    basis = np.linalg.qr(rng.standard_normal((DIM, subspace)))[0].T                     # [subspace,128], orthonormal rows
+    centres = rng.standard_normal((families, subspace))
+    centres = (centres / np.linalg.norm(centres, axis=1, keepdims=True)) @ basis
+
+    def draw(fam):
+        x = centres[fam] + spread * rng.standard_normal((len(fam), DIM))
+        return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+
+    rows = draw(np.minimum(np.arange(n, dtype=np.int64) * families // max(n, 1), families - 1))
+    return rows, draw(np.arange(nq) % families)
+
+
 def plant_neighbours(db: np.ndarray, q: np.ndarray, per_query: int, seed: int, sigma: float = 0.05,
                      normalize: bool = True) -> np.ndarray:
     """Overwrite `per_query` rows per query with q + sigma*noise (known, tie-free neighbours).

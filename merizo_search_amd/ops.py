@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Optional, Sequence, Tuple
 
+import logging
 import os
 
 import numpy as np
@@ -223,6 +224,111 @@ def ip_topk_finish(n: int, nq: int, k: int, ws, out_s, out_i, row_offset: int = 
     with _on(ws, out_s, out_i) as dev:
         check(_lib.load().ms_ip_topk_finish(n, row_offset, nq, k, ptr(out_s), ptr(out_i), ptr(ws), ws.numel(),
                                             dev.stream), "ms_ip_topk_finish")
+
+
+class LargeKWorkspace(TopKWorkspace):
+    """Scratch buffer for ms_ip_topk_large (operands, group lists, one bin per query, and the plain search's workspace)."""
+    _sizing = "ms_ip_topk_large_workspace_bytes"
+
+
+# The fewest rows from which the searches route 64 < k <= LARGE_K_MAX to ip_topk_large (large_k_serves); read once from
+# MS_LARGE_K_MIN_ROWS.  The default is what tools/time_large_k.py measured (DESIGN.md section 5.13); a test sets the attribute.
+LARGE_K_MIN_ROWS = int(os.environ.get("MS_LARGE_K_MIN_ROWS", "200000"))
+# k = 65..128 is two scans on the old path against two reads of the fp32 rows on this one: it pays from this many queries on
+# (measured: 0.83-0.93x for one query, 1.06-2.1x for eight; profiles/large_k_timing.log).  A module attribute, as the row count.
+LARGE_K_TWO_SCAN_MIN_NQ = 8
+LARGE_K_FALLBACK_NOTE = 0.1        # more than this share of a call's queries on the fallback: one INFO line
+
+
+def large_k_serves(n: int, nq: int, k: int) -> bool:
+    """The shapes the searches hand to ip_topk_large: 64 < k <= MS_LARGE_K_MAX, at least 128 rows in each of the G = ceil(k / 64)
+    groups of the bound (what ms_ip_topk_large itself takes), at least LARGE_K_MIN_ROWS rows, and for k <= 128 at least
+    LARGE_K_TWO_SCAN_MIN_NQ queries (from where it is no slower than ms_ip_topk's ceil(k / 64) scans).  ONE statement of the rule
+    for the engine, the drivers and the tests."""
+    groups = -(-int(k) // 64)
+    return (64 < k <= _lib.LARGE_K_MAX and n >= 128 * groups and n >= LARGE_K_MIN_ROWS and nq >= 1
+            and (k > 128 or nq >= LARGE_K_TWO_SCAN_MIN_NQ))
+
+
+def _large_k_rounds(call, fallback, q, qlen, stats=None):
+    """The rounds of ip_topk_large on any device (the CPU tests drive it with stubs).  call(q, qlen, lb_in) -> (scores [nq,k], idx
+    [nq,k], status int32 [nq], lb float32 [nq], st int64 [4]) is one ms_ip_topk_large; fallback(q, qlen) -> (scores, idx) is ip_topk.
+    First round on all queries; the status-1 queries once more with lb_in = their out_lb; whatever is then not status 0 goes to
+    the fallback; everything is scattered back into the first round's outputs.  One read-back per round."""
+    def pick(t, rows):
+        return None if t is None else t.index_select(0, rows).contiguous()
+
+    nq = q.shape[0]
+    out_s, out_i, status, lb, st = call(q, qlen, None)
+    c = [int(x) for x in st.tolist()]                       # (the one sync of the round)
+    info = {"first_round": c[0], "second_round": 0, "fallback": 0, "rescored": max(c[3], 0), "forwarded": c[3] < 0}
+    left = c[1] + c[2]
+    if c[1] > 0:
+        again = (status == 1).nonzero().flatten()
+        s2, i2, status2, _, st2 = call(pick(q, again), pick(qlen, again), pick(lb, again))
+        c2 = [int(x) for x in st2.tolist()]
+        out_s.index_copy_(0, again, s2)                     # (a row that is not final is padding, and the fallback's to fill)
+        out_i.index_copy_(0, again, i2)
+        status.index_copy_(0, again, status2)
+        info["second_round"] = c2[0]
+        info["rescored"] += max(c2[3], 0)
+        left -= c2[0]
+    if left > 0:
+        rest = (status != 0).nonzero().flatten()
+        sf, jf = fallback(pick(q, rest), pick(qlen, rest))
+        out_s.index_copy_(0, rest, sf)
+        out_i.index_copy_(0, rest, jf)
+        info["fallback"] = left
+    if info["first_round"] + info["second_round"] + info["fallback"] != nq:
+        raise MerizoHipError(f"ip_topk_large: the rounds account for {info} of {nq} queries")
+    if info["fallback"] > LARGE_K_FALLBACK_NOTE * nq:
+        logging.info(f"large-k search: {info['fallback']} of {nq} queries took the ceil(k/64)-scan path (a database ordered by family "
+                     "weakens the per-group bound and overflows the candidate bins; the results are exact either way).")
+    if stats is not None:
+        stats.update(info)
+    return out_s, out_i
+
+
+def ip_topk_large(db, q, k: int, row_norm_bound: float, mode: int = MODE_IP_PRENORM, lengths=None, qlen=None, mincov: float = 0.0,
+                  row_offset: int = 0, workspace=None, out=None, stats=None):
+    """ip_topk for 64 < k <= MS_LARGE_K_MAX with the same results bit for bit, from one fp32 read of the rows and one read behind
+    the fp16 matrix pipe instead of ceil(k / 64) fp32 scans (ms_ip_topk_large: the definition and the exactness argument are the
+    header's).  Always the complete exact answer: queries whose bin overflowed get a second round with the tighter bound the first
+    left, and whatever is still open goes to ip_topk.  Shapes the route does not take are ip_topk inside the first call.
+    row_norm_bound: an upper bound on every row's L2 norm (1.0 + 1e-6 for unit rows; it need not hold).  Synchronises once per
+    round (it reads the status counts back).  workspace: a LargeKWorkspace or a uint8 tensor of ms_ip_topk_large_workspace_bytes;
+    stats: a dict that receives 'first_round', 'second_round' and 'fallback' (queries answered by each; they add up to nq),
+    'rescored' (cells sent to the exact chain) and 'forwarded' (the first call was ip_topk's)."""
+    torch = _lib.require_gpu()
+    _f32_cuda(db, "db", DIM)
+    _f32_cuda(q, "q", DIM)
+    if mode not in (MODE_IP_PRENORM, MODE_IP_NORMQ, MODE_COSINE_UNIT):
+        raise MerizoHipError("ip_topk_large: MODE_IP_PRENORM, MODE_IP_NORMQ or MODE_COSINE_UNIT")
+    if mode != MODE_COSINE_UNIT and (lengths is not None or qlen is not None):
+        raise MerizoHipError("ip_topk_large: lengths / qlen go with MODE_COSINE_UNIT")
+    n, k = db.shape[0], int(k)
+    _row_vectors(("lengths", lengths, n), ("qlen", qlen, q.shape[0]))
+    shared = workspace if isinstance(workspace, LargeKWorkspace) else LargeKWorkspace(db.device)
+
+    def call(qs, qls, lb_in):
+        nqs = qs.shape[0]
+        first = lb_in is None
+        if first and isinstance(workspace, torch.Tensor):
+            ws = _workspace("ip_topk_large", "ms_ip_topk_large_workspace_bytes", (n, nqs, k), workspace, db.device)
+        else:
+            ws = shared.get(n, nqs, k)
+        out_s, out_i = _out_pair(nqs, k, db.device, out if first else None, "ip_topk_large")
+        status, lb, st = _outputs("ip_topk_large", ((torch.int32, (nqs,)), (torch.float32, (nqs,)), (torch.int64, (4,))), None, db.device)
+        with _on(db, qs, lengths, qls, lb_in, ws, out_s, out_i) as dev:
+            check(_lib.load().ms_ip_topk_large(ptr(db), n, int(row_offset), ptr(qs), nqs, k, int(mode), ptr(lengths), ptr(qls), float(mincov),
+                                               float(row_norm_bound), ptr(lb_in), ptr(out_s), ptr(out_i), ptr(status), ptr(lb), ptr(st),
+                                               ptr(ws), ws.numel(), dev.stream), "ms_ip_topk_large")
+        return out_s, out_i, status, lb, st
+
+    def fallback(qs, qls):
+        return ip_topk(db, qs, k, mode=mode, lengths=lengths, qlen=qls, mincov=mincov, row_offset=row_offset)
+
+    return _large_k_rounds(call, fallback, q, qlen, stats)
 
 
 class PrefilterWorkspace(TopKWorkspace):
@@ -474,7 +580,7 @@ def topk_excluding(db, q, k: int, lo, hi, mode: int = MODE_IP_PRENORM, row_norm_
     """Exact top-k of q against db WITHOUT the rows [lo[q], hi[q]) of each query (global row numbers, as the search
     reports them: row_offset + row) -> (scores [nq,k], idx [nq,k], count [nq]).  The search runs with
     k' = k + max(hi - lo) -- the prefiltered search when a row_norm_bound is given and prefilter_serves(n, nq, k', image),
-    ms_ip_topk otherwise -- and ms_topk_drop_ranges takes the excluded rows out again (exactness: the header).
+    ip_topk_large when one is given and large_k_serves(n, nq, k'), ms_ip_topk otherwise -- and ms_topk_drop_ranges takes the excluded rows out again (exactness: the header).
     lo / hi: int64 [nq], host arrays or tensors; max_excluded: max(hi - lo) when the caller knows it (a device tensor
     costs a sync to find it).  min_score: also drop the entries scoring below it."""
     torch = _lib.require_gpu()
@@ -490,6 +596,9 @@ def topk_excluding(db, q, k: int, lo, hi, mode: int = MODE_IP_PRENORM, row_norm_
     if row_norm_bound is not None and prefilter_serves(n, nq, kk, image):
         s, i = ip_topk_prefiltered(db, q, kk, float(row_norm_bound), mode=mode, row_offset=row_offset, image=image, lengths=lengths,
                                    qlen=qlen, mincov=mincov, workspace=workspace if isinstance(workspace, PrefilterWorkspace) else None)
+    elif row_norm_bound is not None and mode != MODE_COSINE_RAW and large_k_serves(n, nq, kk):
+        s, i = ip_topk_large(db, q, kk, float(row_norm_bound), mode=mode, lengths=lengths, qlen=qlen, mincov=mincov, row_offset=row_offset,
+                             workspace=workspace if isinstance(workspace, LargeKWorkspace) else None)
     else:
         s, i = ip_topk(db, q, kk, mode=mode, lengths=lengths, qlen=qlen, mincov=mincov, row_offset=row_offset,
                        workspace=workspace if isinstance(workspace, TopKWorkspace) and not isinstance(workspace, PrefilterWorkspace) else None)

@@ -383,6 +383,35 @@ int ms_cluster_components(const int64_t *nbr_idx, const float *nbr_score, int64_
                           float mincov, int64_t *out_rep, float *out_link_score, int64_t *out_n_components, int32_t *out_rounds,
                           int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
 
+/* The single-linkage tree of the SAME graph: what `cluster --tree` and `cluster --levels` run.  The inputs are those of
+ * ms_cluster_components, entry for entry: the same validity rule, an edge_src or a row outside [0, n) never dereferenced, i ~ j when
+ * either direction is valid, the larger of the valid directed scores as weight (-0.0 counts as +0.0), k == 0 with NULL lists and
+ * m == 0 with NULL edge arrays allowed.
+ * Order the undirected edges STRICTLY: weight descending, then (min(i,j), max(i,j)) ascending.  The FOREST is the spanning forest
+ * Kruskal's algorithm builds in that order (the maximum spanning forest; the order makes it unique).  Cutting it at any T >=
+ * min_score -- keeping its edges of weight >= T -- gives exactly the connected components of the graph cut at T, and the largest
+ * weight among a row's own forest edges >= T is the largest among its own graph edges >= T (every row's best edge is in the forest):
+ * ms_cluster_components on the forest's edges as extra entries (k == 0) returns, at every such T, what it returns on the graph.
+ * The forest is a function of the SET of valid entries alone: not of how they are split between lists and extras, of their order,
+ * of duplicates, of timing or of the run.
+ * Outputs (device): out_pairs int32 [n][2], out_weight float32 [n], all n slots written by the call.  A row stops being the root of
+ * its tree at most once; the edge it hooked by is stored in the row's OWN slot r: out_pairs[r] = {a, b} with a < b, out_weight[r]
+ * its weight.  {-1, -1} and -inf mark a row that never hooked (one per component).  Which row holds which edge: in a round every
+ * tree selects its first outgoing edge in the order and its root hooks by it; when two trees select the same edge, the root with
+ * the LARGER row hooks and the smaller stays a root.  (So the slots, too, are a function of the entry set.)
+ * HOST pointers: *out_n_edges = filled slots = n - components; *out_saturated as in ms_cluster_components; *out_rounds = rounds up
+ * to and including the first that found no entry between two trees.  Every tree with such an entry merges in every round, so
+ * *out_rounds <= floor(log2 n) + 1, and it is a function of the entry set: PROMISED, unlike ms_cluster_components' count.
+ * workspace: ms_cluster_tree_workspace_bytes(n) bytes (0 for n outside [1, 2^31 - 1]), 16-byte aligned, initialised by the call; a
+ * used one serves the next call with another n.  MS_ERR_ARG: what ms_cluster_greedy_edges refuses; nothing is launched on an error.
+ * Synchronises like ms_cluster_components: one 16-byte read-back per group of rounds, and it returns after all its work on
+ * `stream` has finished.  Backward compatible addition: ms_version() stays 210. */
+size_t ms_cluster_tree_workspace_bytes(int64_t n);
+int ms_cluster_tree(const int64_t *nbr_idx, const float *nbr_score, int64_t n, int k, const int64_t *edge_src,
+                    const int64_t *edge_dst, const float *edge_score, int64_t m, const int32_t *lengths, float min_score,
+                    float mincov, int32_t *out_pairs, float *out_weight, int64_t *out_n_edges, int32_t *out_rounds,
+                    int64_t *out_saturated, void *workspace, size_t workspace_bytes, ms_stream_t stream);
+
 /* The distinct unordered pairs of the SAME graph, and a verdict per pair written back onto it: what `cluster --mintm` runs around
  * its TM-align stage.  The graph arguments are those of ms_cluster_greedy_edges -- lists [n,k] (k == 0 with NULL lists: none), m
  * extra directed entries (m == 0 with NULL arrays: none), lengths, min_score, mincov -- a directed entry is VALID under exactly

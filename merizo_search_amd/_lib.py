@@ -86,6 +86,8 @@ SIGNATURES = {
     "ms_cluster_greedy_edges": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ms_cluster_components_workspace_bytes": (_sz, [_i64]),
     "ms_cluster_components": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ms_cluster_tree_workspace_bytes": (_sz, [_i64]),
+    "ms_cluster_tree": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ms_cluster_pairs_workspace_bytes": (_sz, [_i64, _int, _i64]),
     "ms_cluster_pairs": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ms_cluster_pairs_apply": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _f, _f, _vp, _i64, _vp, _sz, _vp, _vp]),

@@ -9,7 +9,7 @@ chopping as an input (--chopping / --segment_tsv) instead of predicting it.
     python -m merizo_search_amd.cli easy-search <pdb...> <db_name> <output> <tmp> --chopping "71-189,190-290"
     python -m merizo_search_amd.cli db-search <query_db> <target_db> <output> <tmp> [-k 10] [--exclude_self] ...
     python -m merizo_search_amd.cli chain-search <query_db> <target_db> <output> <tmp> [-s 0.5] [--exclude_same_chain] ...
-    python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] [--complete] [--cluster_mode connected] [-m 0.5 [-f]] ...
+    python -m merizo_search_amd.cli cluster <db_name> <output> <tmp> -s 0.8 [-k 20] [-c 0.7] [--complete] [--cluster_mode connected [--tree] [--levels 0.85,0.9]] [-m 0.5 [-f]] ...
 
 `--multi_domain_search` (search, easy-search, db-search) also writes `<output>_search_multi_dom.tsv`: the target chains that match
 every domain of a query chain.  `--multi_domain_mode exhaustive_tmalign` (the reference's; search and easy-search) aligns every
@@ -433,6 +433,12 @@ def cluster(argv) -> None:
                    help="Verify every edge with TM-align on the GPU: two domains are neighbours only if max(q_tm, t_tm) reaches this "
                         "value, in (0, 1]. Off when not given: the embedding cosine alone decides.")
     p.add_argument("-f", "--fastmode", action="store_true", default=False, help="--mintm: run TM-align in its fast mode (-fast).")
+    p.add_argument("--tree", action="store_true", default=False,
+                   help="--cluster_mode connected: also write <output>_cluster_tree.tsv, the single-linkage tree of the neighbour graph "
+                        "(its maximum spanning forest): cut at any cosine >= --mincos it gives the components at that cosine.")
+    p.add_argument("--levels", type=str, default=None, metavar="T1,T2,...",
+                   help="--cluster_mode connected: cut the tree at these cosines (each >= --mincos) and write "
+                        "<output>_cluster_<T>.tsv per level: the file a run at --mincos T writes, from one search. Implies --tree.")
     args = p.parse_args(argv)
     _join_process_group(args)
     tmp = munge_tmp_with_uuid(args.tmp)
@@ -442,7 +448,8 @@ def cluster(argv) -> None:
     run_cluster(db_name=args.db_name, output=args.output, tmp=tmp, device=args.device, topk=args.topk, mincos=args.mincos,
                 mincov=args.mincov, query_batchsize=args.query_batchsize, search_batchsize=args.search_batchsize,
                 header=args.output_headers, complete=args.complete, max_edges=args.max_edges, mode=args.cluster_mode,
-                mintm=args.mintm, fastmode=args.fastmode)
+                mintm=args.mintm, fastmode=args.fastmode, tree=args.tree,
+                levels=None if args.levels is None else args.levels.split(","))
     logging.info(f"Finished cluster in {time.time() - t0:.3f} seconds.")
     shutil.rmtree(tmp, ignore_errors=True)
 

@@ -29,7 +29,7 @@ from __future__ import annotations
 import logging
 import math
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -56,7 +56,40 @@ def write_cluster_tsv(path: str, names, rep: np.ndarray, rep_score: np.ndarray, 
             handle.write("%s\t%s\t%s%s\n" % (names[int(rep[r])], names[int(r)], "{:.4f}".format(rep_score[r]), tm))
 
 
-MAX_EDGES = 2 ** 27        # directed entries the edge pass of --complete may hold: a memory budget (20 B each: 2.7 GB), not a measurement
+def write_tree_tsv(path: str, names, a: np.ndarray, b: np.ndarray, weight: np.ndarray, header: bool) -> None:
+    """The single-linkage tree, one line per forest edge: member_a, member_b (a the smaller row), link_score -- in the forest's own
+    order, weight descending, then rows ascending.  The weight is printed with %.9g: a float32 round-trips, and other programs cut
+    this file at thresholds of their own."""
+    order = np.lexsort((b, a, -weight.astype(np.float64)))
+    with open(path, "w") as handle:
+        if header:
+            handle.write("member_a\tmember_b\tlink_score\n")
+        for e in order:
+            handle.write("%s\t%s\t%.9g\n" % (names[int(a[e])], names[int(b[e])], float(weight[e])))
+
+
+def _check_levels(levels, mincos: float):
+    """`--levels` as given (strings as typed, or numbers) -> [(label, T)]: the label names the level's file.  Refused: a level that is
+    no number, NaN, below mincos, or given twice."""
+    checked = []
+    for item in levels:
+        label = item.strip() if isinstance(item, str) else str(item)
+        try:
+            value = float(item)
+        except (TypeError, ValueError):
+            _refuse("--levels: %r is not a number." % (item,))
+        if math.isnan(value):
+            _refuse("--levels: a level is NaN.")
+        if value < float(mincos):
+            _refuse("--levels: level %s lies below -s/--mincos %s: the neighbour graph holds no edge below --mincos, and the tree "
+                    "cannot be cut there. Lower --mincos to the smallest level." % (label, mincos))
+        if any(value == seen or label == name for name, seen in checked):
+            _refuse("--levels: level %s is given twice." % label)
+        checked.append((label, value))
+    return checked
+
+
+MAX_EDGES = 2 ** 27       # directed entries the edge pass of --complete may hold: a memory budget (20 B each: 2.7 GB), not a measurement
 
 
 def _edge_pass(engine, target: Target, qdb, in_place: bool, full_rows: np.ndarray, mincos: float, query_batchsize: int,
@@ -161,11 +194,32 @@ def _verify_edges(engine, qdb, graph, lengths: np.ndarray, mincos: float, mincov
                            "tm_unaligned_pairs": unaligned, "tm_removed_entries": int(removed.cpu().numpy()[0])}
 
 
+def _write_tree(engine, forest, levels, names, lengths: np.ndarray, mincov: float, output: str, header: bool, info: dict) -> None:
+    """The files of `cluster --tree / --levels` from forest = engine.cluster_tree(...): `<output>_cluster_tree.tsv`, and per level
+    (label, T) `<output>_cluster_<label>.tsv` -- the components of the forest's edges at T (engine.cluster_components with k = 0: the
+    edges as extras, which stay on the device), written as the connected mode writes its own file.  info gains tree_edges,
+    tree_rounds and levels."""
+    torch = engine.torch
+    pairs, weight, found = forest
+    filled = pairs[:, 0] >= 0
+    a, b, w = pairs[filled, 0].to(torch.int64).contiguous(), pairs[filled, 1].to(torch.int64).contiguous(), weight[filled].contiguous()
+    info.update(tree_edges=int(found["n_edges"]), tree_rounds=int(found["rounds"]), levels={})
+    tree_path = output + "_cluster_tree.tsv"
+    write_tree_tsv(tree_path, names, a.cpu().numpy(), b.cpu().numpy(), w.cpu().numpy(), header)
+    logger.info("cluster: single-linkage tree of %d edges in %d rounds -> %s" % (info["tree_edges"], info["tree_rounds"], tree_path))
+    for label, level in levels:
+        rep, link, cut = engine.cluster_components(None, None, a, b, w, lengths, float(level), mincov)
+        info["levels"][label] = int(cut["n_components"])
+        path = "%s_cluster_%s.tsv" % (output, label)
+        write_cluster_tsv(path, names, rep.cpu().numpy(), link.cpu().numpy(), header, "link_score")
+        logger.info("cluster: level %s: %d components -> %s" % (label, info["levels"][label], path))
+
+
 def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 20, mincos: Optional[float] = None,
                 mincov: float = 0.7, query_batchsize: int = 4096, search_batchsize: int = 262144, header: bool = False,
                 engine=None, timings: Optional[dict] = None, complete: bool = False, max_edges: int = MAX_EDGES,
                 edge_room: int = 2 ** 20, mode: str = "greedy", mintm: Optional[float] = None, fastmode: bool = False,
-                tm_batchsize: int = 65536):
+                tm_batchsize: int = 65536, tree: bool = False, levels: Optional[Sequence] = None):
     """Cluster the rows of database `db_name` and write `<output>_cluster.tsv`.  topk: neighbours kept per row (the search
     fetches topk + 1 and drops the row itself); a row whose topk entries all count as edges may have neighbours the clustering
     never sees (`saturated`: raise -k).  Under several ranks every rank scans its shard of the rows; rank 0 alone keeps the
@@ -187,7 +241,12 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     launch) and takes the pairs below mintm out of the graph before the cluster call, which is unchanged.  info['saturated'] is then
     the count BEFORE the edit, info gains tm_pairs, tm_rejected_pairs, tm_unaligned_pairs and tm_removed_entries, timings 'tm_ms';
     the greedy TSV gains a fourth column `tm_score`: max(qtm, ttm) of (representative, member), 1.0000 on a representative's line.
-    The connected mode keeps its three columns (a member need not be adjacent to its representative)."""
+    The connected mode keeps its three columns (a member need not be adjacent to its representative).
+    tree (connected mode only): after the unchanged steps ms_cluster_tree builds the single-linkage tree of the same graph -- its
+    maximum spanning forest -- and `<output>_cluster_tree.tsv` holds it (write_tree_tsv).  levels (implies tree): thresholds at or
+    above mincos, numbers or strings as typed; for each one ms_cluster_components runs on the forest's edges alone (k = 0, extras)
+    and `<output>_cluster_<level>.tsv` is the file a separate run at that --mincos would write, without a second search.  info gains
+    tree_edges (= n - n_components), tree_rounds and levels ({level: n_components}), timings 'tree_ms' (the ms_cluster_tree call)."""
     from .dbquery import QueryDB
 
     if engine is None:
@@ -207,6 +266,10 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
         _refuse("-m/--mintm must lie in (0, 1], got %r." % (mintm,))
     if mintm is not None and int(tm_batchsize) < 1:
         _refuse("--tm_batchsize must be >= 1, got %r." % (tm_batchsize,))
+    tree = bool(tree) or levels is not None
+    if tree and mode != "connected":
+        _refuse("--tree and --levels read the single-linkage tree: they need --cluster_mode connected, got %r." % (mode,))
+    levels = _check_levels(levels, float(mincos)) if levels is not None else []
     _require_database(db_name)
     target_db = read_database(db_name=db_name)                            # (host side only: nothing is uploaded yet)
     qdb = QueryDB(db_name, loaded=target_db if not target_db["faiss"] else None)
@@ -279,6 +342,11 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
     else:
         rep, rep_score, found = engine.cluster_greedy(nbr_i, nbr_s, lengths, float(mincos), float(mincov))
     times.add("cluster", t0)
+    forest = None
+    if tree:
+        t0 = times.mark()
+        forest = engine.cluster_tree(nbr_i, nbr_s, e_src, e_dst, e_score, lengths, float(mincos), float(mincov))
+        times.add("tree", t0)
     times.finish()
     rep, rep_score = rep.cpu().numpy(), rep_score.cpu().numpy()
     sizes = np.bincount(rep, minlength=n)
@@ -295,6 +363,8 @@ def run_cluster(db_name: str, output: str, tmp: str, device="cuda", topk: int = 
             tm_score = np.ones(n, dtype=np.float64)
             tm_score[members] = np.where(slots >= 0, tm[np.maximum(slots, 0)], -1.0) if tm.shape[0] else -1.0
     write_cluster_tsv(out_path, qdb.names(0, n), rep, rep_score, header, "link_score" if mode == "connected" else "emb_score", tm_score)
+    if forest is not None:
+        _write_tree(engine, forest, levels, qdb.names(0, n), lengths, float(mincov), output, header, info)
     qdb.close()
     if mode == "connected":
         info["largest"] = int(sizes.max())

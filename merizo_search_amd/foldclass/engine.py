@@ -270,6 +270,10 @@ class HipEngine:
         """Connected components of the same graph (ms_cluster_components) -> (rep, link_score, info)."""
         return self._ops.cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
 
+    def cluster_tree(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0):
+        """The single-linkage tree of the same graph (ms_cluster_tree) -> (pairs int32 [n,2], weight float32 [n], info)."""
+        return self._ops.cluster_tree(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score, mincov)
+
     def cluster_pairs(self, nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, cap=None):
         """The distinct canonical pairs of the graph the cluster calls read (ms_cluster_pairs) -> (pairs int32 [cap,2], count int64
         [2] = (distinct pairs, rows whose list entries are all valid), workspace): device tensors, nothing read back."""

@@ -698,6 +698,28 @@ def cluster_components(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengt
                     nbr_score, (edge_src, edge_dst, edge_score), lengths, min_score, mincov, out, workspace)
 
 
+def cluster_tree(nbr_idx, nbr_score, edge_src, edge_dst, edge_score, lengths, min_score: float, mincov: float = 0.0, out=None,
+                 workspace=None):
+    """The single-linkage tree of the graph cluster_components reads (ms_cluster_tree: the definition is the header's), with its
+    arguments: the maximum spanning forest under the order weight descending, then (min row, max row) ascending.  -> (pairs int32
+    [n,2], weight float32 [n], info): slot r holds the edge {a, b}, a < b, by which row r stopped being the root of its tree, and
+    its weight; (-1, -1) and -inf: the row never hooked.  info = {'n_edges' (= n - components), 'rounds' (<= floor(log2 n) + 1, a
+    function of the entries), 'saturated'}.  Cutting the forest at any T >= min_score gives the components of the graph at T.
+    Synchronises.  out: optional preallocated (pairs, weight); workspace: optional uint8 tensor of ms_cluster_tree_workspace_bytes(n)."""
+    import ctypes
+    who = "cluster_tree"
+    torch = _lib.require_gpu()
+    edges = (edge_src, edge_dst, edge_score)
+    t, n, k, m = _cluster_graph(who, nbr_idx, nbr_score, edges, lengths)
+    pairs, weight = _outputs(who, ((torch.int32, (n, 2)), (torch.float32, (n,))), out, t.device)
+    workspace = _workspace(who, "ms_cluster_tree_workspace_bytes", (n,), workspace, t.device)
+    n_edges, rounds, saturated = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int64(0)
+    _graph_call("ms_cluster_tree", nbr_idx, nbr_score, edges, t, n, k, m, min_score, mincov, (pairs, weight, workspace),
+                lambda stream: (ptr(pairs), ptr(weight), ctypes.addressof(n_edges), ctypes.addressof(rounds), ctypes.addressof(saturated),
+                                ptr(workspace), workspace.numel(), stream))
+    return pairs, weight, {"n_edges": int(n_edges.value), "rounds": int(rounds.value), "saturated": int(saturated.value)}
+
+
 def _pairs_workspace(who, n, k, m, workspace, device):
     if n * k + m >= 2 ** 31:
         raise MerizoHipError(f"{who}: n k + m = {n * k + m} directed entries, the set holds fewer than 2^31 (MS_ERR_RANGE (-4))")

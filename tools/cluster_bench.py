@@ -18,6 +18,10 @@ Prints one JSON line:
                                   edges_first_ms: the first, which loads the kernel), are added
   --cluster_mode connected        run `cluster --cluster_mode connected`: cluster_ms is then ms_cluster_components, rounds its hook /
                                   compress rounds, clusters its components; `largest` (the rows of the largest component) is added
+  --tree                          run `cluster --cluster_mode connected --tree`: tree_ms (ms_cluster_tree inside the driver), tree_rounds
+                                  and tree_edges are added, and tree_calls_ms / components_calls_ms: ms_cluster_tree and
+                                  ms_cluster_components called alternately on the driver's graph tensors, seven times each, HIP events
+                                  around each call (the first of each includes what a first call loads)
 Unit rows drawn at random have cosines ~ N(0, 1/128): at --mincos 0.4 a row of a 1M-row database has a handful of neighbours.
 Needs an MI355X from the start: the rows of the database file are generated on the device (dbsearch_bench.write_database).
 Compare `cluster_ms` with `scan_ms` of the same run."""
@@ -64,7 +68,10 @@ def main():
     ap.add_argument("--families", type=int, default=50, help="planted families, when --family_size is given")
     ap.add_argument("--complete", action="store_true", help="cluster the full threshold graph (cluster --complete)")
     ap.add_argument("--cluster_mode", type=str, default="greedy", choices=("greedy", "connected"), help="what is read off the graph")
+    ap.add_argument("--tree", action="store_true", help="time ms_cluster_tree on the driver's graph (implies --cluster_mode connected)")
     args = ap.parse_args()
+    if args.tree:
+        args.cluster_mode = "connected"
     import logging
     logging.getLogger().setLevel(logging.WARNING)
     from dbsearch_bench import write_database
@@ -82,13 +89,32 @@ def main():
         print("[cluster_bench] database of %d rows ready in %.1f s" % (args.rows, time.perf_counter() - t0), file=sys.stderr, flush=True)
         engine = ds.engine_setup("cuda:0")
         times = {}
+        graph = []
+        if args.tree:                                                     # keep the driver's graph tensors: the calls are repeated on them
+            driver_call = engine.cluster_tree
+            engine.cluster_tree = lambda *a: (graph.append(a), driver_call(*a))[1]
         t0 = time.perf_counter()
         _rep, _score, info = cluster.run_cluster(prefix, os.path.join(work, "out"), os.path.join(work, "tmp"), "cuda:0", topk=args.k,
                                                  mincos=args.mincos, mincov=args.mincov, query_batchsize=args.batch, engine=engine,
-                                                 timings=times, complete=args.complete, mode=args.cluster_mode)
+                                                 timings=times, complete=args.complete, mode=args.cluster_mode, tree=args.tree)
         wall = time.perf_counter() - t0
         extra = {"family_size": args.family_size, "families": args.families if args.family_size > 0 else 0, "complete": args.complete,
                  "full_lists": info["full_lists"], "cluster_mode": args.cluster_mode}
+        if args.tree:
+            import torch
+            spans = {"tree": [], "components": []}
+            graph[0] = graph[0][:5] + (engine.to_device(graph[0][5].astype("int32")),) + graph[0][6:]      # (the lengths: uploaded once, not per call)
+            for _call in range(7):                                        # alternately, HIP events around each call (both synchronise)
+                for name, call in (("tree", driver_call), ("components", engine.cluster_components)):
+                    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    start.record()
+                    found = call(*graph[0])[2]
+                    end.record()
+                    torch.cuda.synchronize()
+                    spans[name].append(round(start.elapsed_time(end), 3))
+                    assert name != "tree" or (found["n_edges"], found["rounds"]) == (info["tree_edges"], info["tree_rounds"])
+            extra.update(tree_ms=round(times["tree_ms"], 3), tree_rounds=info["tree_rounds"], tree_edges=info["tree_edges"],
+                         tree_calls_ms=spans["tree"], components_calls_ms=spans["components"])
         if args.cluster_mode == "connected":
             extra["largest"] = info["largest"]
         if args.complete:

@@ -11,7 +11,9 @@
  * (FoldClassNet(128), reference programs/Foldclass/dbsearch.py:40).
  * Threading: entry points may be called from any host thread; a WORKSPACE serves one stream at a time (calls that share a workspace
  * must be ordered on one stream: the searches keep lists, counters and the exact pass's launch plan in it between their launches) --
- * concurrent searches take one workspace each.  A prefiltered search whose bookkeeping was disturbed all the same (a second stream on
+ * concurrent searches take one workspace each.  One exception to "never allocate, never synchronise": the FIRST search on a workspace
+ * (and the first after its record was handed on, ms_wsstate.h) allocates the library's own 512-byte block of counters for it and
+ * waits until the null stream has zeroed it, once, before anything is launched on `stream`.  A prefiltered search whose bookkeeping was disturbed all the same (a second stream on
  * its workspace, a launch aborted half way) does not answer: the exact pass queued behind it finds the re-scoring's verdict missing
  * and TRAPS (round 6; ms_debug_prefilter_poison is the test's way in).  For the same reason the prefiltered entry points
  * (ms_ip_topk_prefiltered and its _prepare / _scan / _finish stages) CANNOT BE CAPTURED INTO A GRAPH: the base of the compaction's ticket

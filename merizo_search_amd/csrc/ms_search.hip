@@ -727,12 +727,15 @@ __global__ __launch_bounds__(64) void ms_kway_merge_any_kernel(const float *scor
 // (the switches, the launch plan, the workspace carve and the rules shared below: ms_plan.h)
 // The device behind the per-workspace records (ms_wsstate.h: everything the host remembers about a workspace between calls)
 int ms_wsstate::current_device() { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : -1; }
+// Both zero the block on the null stream and WAIT for it: the search that asked launches next on the caller's stream, which may be a
+// non-blocking one that the null stream does not order itself with (a memset of device memory need not have finished when it returns)
+static bool zero_now(void *block, size_t bytes) { return hipMemset(block, 0, bytes) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess; }
 void *ms_wsstate::alloc_zeroed(size_t bytes) {
     void *mem = nullptr;
-    if (hipMalloc(&mem, bytes) == hipSuccess && hipMemset(mem, 0, bytes) != hipSuccess) { (void)hipFree(mem); mem = nullptr; }
+    if (hipMalloc(&mem, bytes) == hipSuccess && !zero_now(mem, bytes)) { (void)hipFree(mem); mem = nullptr; }
     return mem;
 }
-bool ms_wsstate::drain_and_zero(void *block, size_t bytes) { return hipDeviceSynchronize() == hipSuccess && hipMemset(block, 0, bytes) == hipSuccess; }
+bool ms_wsstate::drain_and_zero(void *block, size_t bytes) { return hipDeviceSynchronize() == hipSuccess && zero_now(block, bytes); }
 namespace {
 
 // CU count of HIP's current device (the device the caller's tensors live on: the Python front end

@@ -1008,6 +1008,12 @@ class EgnnEncoder:
     ``embed(list of [N,3] arrays)`` -> float32 [B,128] tensor on the device.  Replaces
     ``network(x)`` of the reference (dbsearch.py:97-98, :299-301; makedb.py:75-79) for a whole
     ragged batch per launch.
+
+    Streams: an encoder owns ONE device staging buffer and ONE workspace, which the kernels of a call read and write until the
+    last of them has finished.  ``embed`` runs on torch's current stream, records an event behind its last launch, and the next
+    call makes ITS stream wait on that event before the staging copy and before it reuses the workspace: calls on different
+    streams are correct and run one after the other.  For embeddings that overlap on the device take one encoder per stream; one
+    encoder serves one host thread at a time.
     """
 
     def __init__(self, weights: np.ndarray, pe: np.ndarray, device="cuda:0"):
@@ -1030,6 +1036,7 @@ class EgnnEncoder:
         self._ws = None
         self._last = None          # (nb, total, sum_sq) of the last embed: where its node features lie in the workspace
         self._stage = self._stage_dev = self._stage_free = None
+        self._done = None          # event behind the last launch of the last embed: staging buffer and workspace are free from there on
 
     def embed(self, coords_list: Sequence[np.ndarray]):
         torch = _lib.require_gpu()
@@ -1066,6 +1073,8 @@ class EgnnEncoder:
                 flat[pos: pos + int(n)] = np.asarray(c, dtype=np.float32).reshape(-1, 3)
                 pos += int(n)
             stream = torch.cuda.current_stream(self.device)
+            if self._done is not None:
+                stream.wait_event(self._done)             # the previous call's kernels, on whatever stream, have left staging buffer and workspace
             self._stage_dev[:nbytes].copy_(self._stage[:nbytes], non_blocking=True)
             self._stage_free = stream.record_event()
             offs_ptr = self._stage_dev.data_ptr()
@@ -1079,6 +1088,7 @@ class EgnnEncoder:
             check(lib.ms_egnn_embed(ptr(self.prepared), ptr(self.pe), self.max_len, coords_ptr, offs_ptr,
                                     offsets.ctypes.data, nb, ptr(out), ptr(self._ws), self._ws.numel(), stream.cuda_stream),
                   "ms_egnn_embed")
+            self._done = stream.record_event()
             self._last = (nb, total, sum_sq)
         return out
 
@@ -1105,7 +1115,9 @@ def tmalign_batch(coords_list: Sequence[np.ndarray], seqs: Sequence[bytes], pair
     the values of its %8.3f PDB text).  Returns numpy arrays indexed like `pairs`: qtm (TM-score normalised by chain 1),
     ttm (by chain 2), rmsd, n_ali8, n_identical, status (_lib.TM_*), and invmap ([npairs, max chain-2 length], -1 = gap)
     if asked.  A structure longer than _lib.TMALIGN_MAX_LEN or with a non-finite coordinate raises; pairs with a chain of
-    <= 5 residues get TM_ERR_SHORT."""
+    <= 5 residues get TM_ERR_SHORT.  Runs on torch's current stream and returns when the results are on the host.  The scratch is
+    shared per device (_tm_ws): calls from one host thread follow each other whatever their streams; two host threads must not
+    call it for one device at the same time."""
     for s, c in enumerate(coords_list):                  # checked before the device: NaN / inf never reach the kernel
         if not np.isfinite(np.asarray(c, dtype=np.float64)).all():
             raise MerizoHipError(f"tmalign_batch: structure {s} has a non-finite coordinate")
